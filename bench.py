@@ -9,7 +9,14 @@ advances `inner_steps` VecEnv steps (auto-reset inside, random-agent actions
 drawn on the device, observation / reward / done planes streamed to HBM).
 value = total env-steps of all ranks / max-over-ranks wall time.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload kuka|mobile]
+A plain run sets up, warms up, times K steps and prints one JSON line.  --full adds
+everything else this file measures: the CPU baselines, the secondary legs of the
+default command (other workloads, sizes and the lumped model), the live rocprofv3
+PMC passes and the pixel path's per-kernel timings.  --dump-outputs DIR writes what
+the timed path returned in its last step as DIR/<name>.npy (float32 / float64; a
+fixed, seeded sample of envs when the planes exceed 48 MB).
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload kuka|mobile] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -60,7 +67,46 @@ def parse():
     ap.add_argument("--device-ids", default=None, help="--per-step: GPUs of the sharded HipVecEnv ('all' or e.g. 0,1,2,3; default: device 0)")
     ap.add_argument("--no-live-pmc", action="store_true",
                     help="roofline.traffic / issue_util from the committed profiles/ summaries only (no rocprofv3 --pmc child passes)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: CPU baselines, the secondary legs, live rocprofv3 --pmc "
+                         "passes, the pixel path's per-kernel timings (--no-cpu-baseline / --no-secondary / --no-live-pmc trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_BUDGET_BYTES = 48 << 20     # --dump-outputs: at most this much in all (a seeded sample of envs beyond it)
+
+
+def dump_outputs(out_dir, planes, n):
+    """Write each plane of `planes` (name -> (torch tensor or ndarray, env axis)) as out_dir/<name>.npy: float64 stays float64,
+    everything else becomes float32 (the integer planes are action indices and done flags, exact in float32).  When all planes
+    together exceed DUMP_BUDGET_BYTES, a fixed sample of env indices (RandomState(0), sorted) is kept on every plane; env_index.npy
+    holds the env indices written either way."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def nbytes(a):
+        if torch.is_tensor(a):
+            return a.numel() * (8 if a.dtype == torch.float64 else 4)
+        a = np.asarray(a)
+        return a.size * (8 if a.dtype == np.float64 else 4)
+    total = sum(nbytes(a) for a, _ in planes.values())
+    if total <= DUMP_BUDGET_BYTES:
+        idx = np.arange(n)
+    else:
+        idx = np.sort(np.random.RandomState(0).choice(n, max(1, DUMP_BUDGET_BYTES * n // total), replace=False))
+    for name, (a, axis) in planes.items():
+        if torch.is_tensor(a):
+            a = a.index_select(axis, torch.from_numpy(idx).to(a.device)).cpu().numpy()
+        else:
+            a = np.take(np.asarray(a), idx, axis=axis)
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+    np.save(os.path.join(out_dir, "env_index.npy"), idx.astype(np.float64))
 
 
 def self_launch(args):
@@ -91,7 +137,7 @@ _LIVE_PMC = {}      # workload -> {kernel: {counter: (sum, dispatches)}} measure
 def live_pmc(args, workload):
     """HBM traffic and instruction counters of THIS run's kernels: the same command (short: 1 warm-up + 2 steps) re-run as child
     processes under `rocprofv3 --pmc`, one pass per counter set and no tracing options (MI355X_MICROARCH.md, HBM / rocprofv3
-    section), aggregated per kernel like profiles/summarize_pmc.py.  Rank 0 of an N = 1 run only; None (-> the committed
+    section), aggregated per kernel like profiles/summarize_pmc.py.  Rank 0 of an N = 1 --full run only; None (-> the committed
     summaries) when rocprofv3 is missing, a pass fails, or we ARE such a child."""
     import csv
     import re
@@ -101,7 +147,7 @@ def live_pmc(args, workload):
     if workload in _LIVE_PMC:
         return _LIVE_PMC[workload]
     _LIVE_PMC[workload] = None
-    if args.no_live_pmc or os.environ.get("SRLHIP_BENCH_CHILD") or shutil.which("rocprofv3") is None:
+    if not args.full or args.no_live_pmc or os.environ.get("SRLHIP_BENCH_CHILD") or shutil.which("rocprofv3") is None:
         return None
     sets = ["FETCH_SIZE", "WRITE_SIZE"] + (["SQ_WAVES SQ_INSTS_VALU"] if workload == "kuka" else [])
     agg = {}
@@ -226,7 +272,7 @@ def pixel_cpu_baseline(enc, env, budget_s=3.0, phys=None):
                       "sequential stages".format(budget_s, phys["value"], raster_rate, n, enc_rate)}
 
 
-def bench_pixels(args, rank, local_rank, world, dev, K=None, W=None, cpu=True, phys_baseline=None):
+def bench_pixels(args, rank, local_rank, world, dev, K=None, W=None, cpu=True, phys_baseline=None, dump=None):
     """BASELINE config 4/5: KukaButtonGymEnv raw_pixels 64x64 -> tile rasteriser -> SRL encoder forward
     (fused HIP kernel, csrc/encoder.hip) on the same device.  One bench step = `inner` VecEnv steps of this rank's shard."""
     from srlhip import _lib, sharding
@@ -243,10 +289,12 @@ def bench_pixels(args, rank, local_rank, world, dev, K=None, W=None, cpu=True, p
     env.reset()
     gathered = torch.zeros((world * n,), dtype=torch.float32, device=dev) if world > 1 else None
     ret = torch.zeros((n,), dtype=torch.float32, device=dev)
+    last = {}
 
     def one_step():
         for _ in range(inner):
             states, rew, done = env.step()
+        last["states"], last["reward"], last["done"] = states, rew, done
         if world > 1:
             env.h.episode_stats_device(last_return=ret.data_ptr())     # enqueued on the stepper's stream
             torch.cuda.current_stream(dev).wait_stream(env._stream)
@@ -269,6 +317,26 @@ def bench_pixels(args, rank, local_rank, world, dev, K=None, W=None, cpu=True, p
     dt_own = time.perf_counter() - t0
     dt_ranks = sharding.per_rank(dt_own, device=dev)
     dt = sharding.max_over_ranks(dt_own, device=dev)
+    if dump and rank == 0:
+        dump_outputs(dump, {k: (v, 0) for k, v in last.items()}, n)
+    value = world * n * inner * K / dt
+    step_ms = dt * 1e3 / (K * inner)
+    hip_encoder = enc.hip is not None
+    line = {"metric": "env steps/sec (whole node), KukaButtonGymEnv {} envs/GPU".format(n), "value": value,
+            "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": dt * 1e3 / K,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64 dynamics, f32 raster, f32-accurate split-f16 MFMA encoder" if hip_encoder else "f64 dynamics, f32 raster/encoder",
+            "data": "synthetic",
+            "config": {"workload": "KukaButtonGymEnv-v0 raw_pixels {}x{}, {} envs per GPU, rasteriser + srl_zoo CustomCNN "
+                                   "forward (random init) on the same device, random-agent actions".format(S, S, n),
+                       "envs_per_gpu": n, "inner_steps": inner, "parallelism": "env-shard x{}".format(world),
+                       "encoder_backend": enc.backend, "ms_per_vecenv_step": step_ms,
+                       "x_vs_published_250fps_cpu": value / PUBLISHED_REFERENCE_FPS}}
+    if world > 1:      # stragglers: every rank's own time for the K steps (value uses the maximum)
+        line["config"]["ms_per_step_ranks"] = {"min": min(dt_ranks) * 1e3 / K, "max": max(dt_ranks) * 1e3 / K, "all": [x * 1e3 / K for x in dt_ranks]}
+    if not args.full:       # what follows takes runs of its own
+        env.close()
+        return line
     # per-kernel shares, each timed alone with HIP events on the stepper's own stream (the stream all three run on)
     # (`reps` launches captured in a HIP graph and replayed between the two events: the figure does not depend on how fast this
     #  process can enqueue — a busy host once made the eagerly-enqueued "alone" time longer than the whole step that contains it)
@@ -292,11 +360,8 @@ def bench_pixels(args, rank, local_rank, world, dev, K=None, W=None, cpu=True, p
             env.h.graph_destroy(g)
 
     raster_ms = graph_ms(lambda: env.h.render(out=env.images.data_ptr()))
-    hip_encoder = enc.hip is not None
     enc_ms = graph_ms(lambda: enc.getStates(env.images, stream=env._stream_ptr, out=env.states)) if hip_encoder else None
     stepper_ms = graph_ms(lambda: env.h.rollout(1, out=(0, env.rewards.data_ptr(), env.dones.data_ptr(), env.actions.data_ptr())))
-    value = world * n * inner * K / dt
-    step_ms = dt * 1e3 / (K * inner)
     raster_gbs = n * S * S * 3 / (raster_ms * 1e-3) / 1e9
     raster_roof = {"bound": "hbm", "kernel": "raster_k", "achieved": raster_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                    "frac": raster_gbs / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": raster_ms,
@@ -324,20 +389,10 @@ def bench_pixels(args, rank, local_rank, world, dev, K=None, W=None, cpu=True, p
                     "raster_k": raster_roof}
     else:
         roofline = raster_roof
-    line = {"metric": "env steps/sec (whole node), KukaButtonGymEnv {} envs/GPU".format(n), "value": value,
-            "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": dt * 1e3 / K,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64 dynamics, f32 raster, f32-accurate split-f16 MFMA encoder" if hip_encoder else "f64 dynamics, f32 raster/encoder",
-            "data": "synthetic",
-            "config": {"workload": "KukaButtonGymEnv-v0 raw_pixels {}x{}, {} envs per GPU, rasteriser + srl_zoo CustomCNN "
-                                   "forward (random init) on the same device, random-agent actions".format(S, S, n),
-                       "envs_per_gpu": n, "inner_steps": inner, "parallelism": "env-shard x{}".format(world),
-                       "encoder_backend": enc.backend, "ms_per_vecenv_step": step_ms,
-                       "kernel_ms": {"raster_k": raster_ms, "encoder_fwd_k": enc_ms, "stepper_single_step_launch": stepper_ms,
-                                     "stepper_and_launch_gaps": step_ms - raster_ms - (enc_ms or 0.0),
-                                     "how": "each kernel alone: {} launches replayed from one HIP graph between two events on the stepper's stream".format(reps)},
-                       "x_vs_published_250fps_cpu": value / PUBLISHED_REFERENCE_FPS},
-            "roofline": roofline}
+    line["config"]["kernel_ms"] = {"raster_k": raster_ms, "encoder_fwd_k": enc_ms, "stepper_single_step_launch": stepper_ms,
+                                   "stepper_and_launch_gaps": step_ms - raster_ms - (enc_ms or 0.0),
+                                   "how": "each kernel alone: {} launches replayed from one HIP graph between two events on the stepper's stream".format(reps)}
+    line["roofline"] = roofline
     if world == 1 and rank == 0 and S == 64:
         # HBM bytes per launch of the two pixel-path kernels, re-measured now: this command as child processes under rocprofv3 --pmc
         # (separate FETCH_SIZE / WRITE_SIZE passes, MI355X_MICROARCH.md's HBM section), FETCH_SIZE x2 + WRITE_SIZE in KiB
@@ -349,8 +404,6 @@ def bench_pixels(args, rank, local_rank, world, dev, K=None, W=None, cpu=True, p
             raster_roof["traffic_over_algorithmic"] = t_r / float(n * S * S * 3)
         if t_e is not None and hip_encoder:
             roofline["traffic"] = t_e; roofline["traffic_source"] = src
-    if world > 1:      # stragglers: every rank's own time for the K steps (value uses the maximum)
-        line["config"]["ms_per_step_ranks"] = {"min": min(dt_ranks) * 1e3 / K, "max": max(dt_ranks) * 1e3 / K, "all": [x * 1e3 / K for x in dt_ranks]}
     if rank == 0 and world == 1 and cpu and not args.no_cpu_baseline and S == 64:
         try:
             line["cpu_baseline"] = pixel_cpu_baseline(enc, env, phys=phys_baseline)
@@ -381,7 +434,7 @@ def pmc_issue_util(kernel, avg_launch_s, clock_hz=2.35e9):      # (the PMC pass'
             "issue_util": per_wave * 4.0 / (avg_launch_s * clock_hz), "source": os.path.basename(files[-1])}
 
 
-def bench_stepper(args, workload, rank, local_rank, world, dev, K=None, W=None, cpu=True, backend="nccl"):
+def bench_stepper(args, workload, rank, local_rank, world, dev, K=None, W=None, cpu=True, backend="nccl", dump=None):
     """BASELINE configs 2 / 3: the ground-truth stepper alone.  Returns the bench line (dict)."""
     from srlhip import _lib, sharding
     n = args.envs_per_gpu
@@ -452,6 +505,8 @@ def bench_stepper(args, workload, rank, local_rank, world, dev, K=None, W=None, 
     dt = time.perf_counter() - t0
     dt_ranks = sharding.per_rank(dt, device=dev)
     dt = sharding.max_over_ranks(dt, device=dev)
+    if dump and rank == 0:      # the planes of the last timed rollout, [T][n] (this rank's shard)
+        dump_outputs(dump, {"obs": (obs, 1), "reward": (rew, 1), "done": (done, 1), "actions": (act, 1)}, n)
 
     total_env_steps = world * n * inner * K
     value = total_env_steps / dt
@@ -553,7 +608,7 @@ def bench_stepper(args, workload, rank, local_rank, world, dev, K=None, W=None, 
         line["config"]["ms_per_step_ranks"] = {"min": min(dt_ranks) * 1e3 / K, "max": max(dt_ranks) * 1e3 / K, "all": [x * 1e3 / K for x in dt_ranks]}
         line["config"]["episode_returns_allgathered"] = {"count": int(gathered.numel()), "mean": float(gathered.mean().item()),
                                                          "collective": "all_gather_into_tensor float32[{}] per rank, once per rollout ({})".format(n, backend)}
-    if rank == 0 and world == 1 and cpu and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and cpu and args.full and not args.no_cpu_baseline:
         try:
             line["cpu_baseline"] = cpu_baseline(workload, n, full=args.kuka_model == "full")
             line["cpu_baseline"]["host"] = "{} logical cores".format(os.cpu_count())
@@ -574,7 +629,7 @@ def bench_per_step(args, emit=True):
     K = args.steps if args.steps is not None else 2000
     W = args.warmup if args.warmup is not None else 300
 
-    def run(ids, persistent=None):
+    def run(ids, persistent=None, dump=None):
         n = args.envs_per_gpu * len(ids)
         env = HipVecEnv(env_id, n, seed=0, env_kwargs={"srl_model": "ground_truth"}, device_ids=ids, rng_mode=args.rng, persistent=persistent)
         env.reset()
@@ -588,15 +643,17 @@ def bench_per_step(args, emit=True):
             t0 = time.perf_counter()
             env.step_async(acts[t % 64])
             t1 = time.perf_counter()
-            env.step_wait()
+            obs, rew, dones, _ = env.step_wait()
             t2 = time.perf_counter()
             ta += t1 - t0; tw += t2 - t1; lat[t] = t2 - t0
         dt = time.perf_counter() - t_begin
+        if dump:       # what the last timed step_wait returned
+            dump_outputs(dump, {"obs": (obs, 0), "reward": (rew, 0), "done": (dones, 0)}, n)
         env.close()
         return {"n": n, "value": n * K / dt, "us_per_step_mean": dt / K * 1e6, "us_per_step_median": float(np.median(lat)) * 1e6,
                 "us_in_step_async": ta / K * 1e6, "us_in_step_wait": tw / K * 1e6}
 
-    r = run(device_ids, True if args.persistent else None)
+    r = run(device_ids, True if args.persistent else None, dump=args.dump_outputs if emit else None)
     line = {"metric": "env steps/sec, per-step VecEnv API (HipVecEnv.step{}), {} {} envs per shard x {} shard(s)".format(
                 ", persistent stepping" if args.persistent else "", env_id.split("-")[0], args.envs_per_gpu, len(device_ids)),
             "value": r["value"], "unit": "env-steps/s", "n_gpus": len(set(device_ids)), "steps": K, "warmup": W, "ms_per_step": r["us_per_step_mean"] / 1e3,
@@ -636,12 +693,12 @@ def main():
     # "auto" = the configuration the metric is quoted on (BASELINE config 3).  No fallback: a missing library / GPU raises.
     workload = "kuka" if args.workload == "auto" else args.workload
     if workload == "kuka_pixels":
-        line = bench_pixels(args, rank, local_rank, world, dev)
+        line = bench_pixels(args, rank, local_rank, world, dev, dump=args.dump_outputs)
     else:
-        line = bench_stepper(args, workload, rank, local_rank, world, dev, backend=backend)
+        line = bench_stepper(args, workload, rank, local_rank, world, dev, backend=backend, dump=args.dump_outputs)
     line["config"]["ranks_seen"] = world
     line["config"]["dist_backend"] = ("{} (RCCL over xGMI)".format(backend) if backend == "nccl" else backend) if world > 1 else None
-    if args.workload == "auto" and world == 1 and not args.no_secondary and args.envs_per_gpu == 4096:
+    if args.full and args.workload == "auto" and world == 1 and not args.no_secondary and args.envs_per_gpu == 4096:
         # BASELINE configs 2 and 4, briefly, in the same driver-run line (their own value / roofline / cpu_baseline)
         sec = {}
         saved = args.inner_steps

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 for w in kuka mobile kuka_pixels; do
   rm -rf /tmp/prof_$w
   # the kernel-stats run is the full default command (cpu_baseline leg included)
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$w -o $w -- python $R/bench.py --workload $w > $OUT/bench_$w.json 2>/dev/null
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$w -o $w -- python $R/bench.py --workload $w --full > $OUT/bench_$w.json 2>/dev/null
   cp $(find /tmp/prof_$w -name "*kernel_stats.csv" | head -1) $OUT/${w}_kernel_stats.csv
 done
 # the layered encoder (224x224x3 and 6-channel frames) and the rasteriser on their own
@@ -28,12 +28,12 @@ for w in kuka mobile; do
   done
 done
 # the lane-per-env Kuka kernel at the same size, for the before / after comparison
-SRLHIP_KUKA_KERNEL=lane timeout 300 python $R/bench.py --workload kuka --no-cpu-baseline --steps 5 > $OUT/bench_kuka_lane_kernel.json 2>/dev/null
+SRLHIP_KUKA_KERNEL=lane timeout 300 python $R/bench.py --workload kuka --full --no-cpu-baseline --steps 5 > $OUT/bench_kuka_lane_kernel.json 2>/dev/null
 # N-sweep of the Kuka stepper: default kernel choice per batch size
 for n in 1024 4096 16384 65536; do
-  timeout 300 python $R/bench.py --workload kuka --no-cpu-baseline --envs-per-gpu $n --steps 3 --inner-steps 1024 >> $OUT/nsweep_kuka.jsonl 2>/dev/null
+  timeout 300 python $R/bench.py --workload kuka --full --no-cpu-baseline --envs-per-gpu $n --steps 3 --inner-steps 1024 >> $OUT/nsweep_kuka.jsonl 2>/dev/null
 done
 for n in 4096 65536 1048576; do
-  timeout 300 python $R/bench.py --workload mobile --no-cpu-baseline --envs-per-gpu $n --steps 5 --inner-steps 1024 >> $OUT/nsweep_mobile.jsonl 2>/dev/null
+  timeout 300 python $R/bench.py --workload mobile --full --no-cpu-baseline --envs-per-gpu $n --steps 5 --inner-steps 1024 >> $OUT/nsweep_mobile.jsonl 2>/dev/null
 done
 ls -la $OUT

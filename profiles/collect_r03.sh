@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/profiles
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # (1) the default command exactly as the driver runs it: headline + secondary legs + cpu baselines, one JSON line
-timeout 900 python $R/bench.py > $OUT/bench_default.json 2>/dev/null
+timeout 900 python $R/bench.py --full > $OUT/bench_default.json 2>/dev/null
 # (2) kernel stats per workload, each traced alone so that a kernel's average launch duration is that of ONE launch shape
 #     (the default command mixes 2048-step rollouts and single steps of the same kernel)
 for w in kuka mobile kuka_pixels; do

@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/profiles
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # (1) the default command exactly as the driver runs it: one JSON line
-timeout 900 python $R/bench.py > $OUT/bench_default.json 2>/dev/null
+timeout 900 python $R/bench.py --full > $OUT/bench_default.json 2>/dev/null
 # (2) kernel stats per workload, each traced alone
 for w in kuka mobile kuka_pixels; do
   rm -rf /tmp/prof_$w
@@ -39,7 +39,7 @@ cd $R
 timeout 300 python profiles/probes/kuka_launch_cost.py > $OUT/kuka_launch_cost.txt 2>&1
 timeout 300 python profiles/probes/vecenv_latency.py > $OUT/vecenv_latency.txt 2>&1
 # (7) BASELINE config 5 exactly as stated (raw_pixels, 8 ranks x 4096 envs), dry run of the N > 1 path on this ONE device (gloo)
-SRLHIP_SINGLE_DEVICE=1 SRLHIP_DIST_BACKEND=gloo timeout 600 python bench.py --workload kuka_pixels --gpus 8 2>/dev/null | grep "^{" > $OUT/bench_pixels_gpus8_single_device.json
+SRLHIP_SINGLE_DEVICE=1 SRLHIP_DIST_BACKEND=gloo timeout 600 python bench.py --workload kuka_pixels --gpus 8 --full 2>/dev/null | grep "^{" > $OUT/bench_pixels_gpus8_single_device.json
 # (8) where a step of the tree kernel goes (profiling build: shader-clock stamps)
 if [ -f robotics-rl-srl_amd/csrc/build/libsrlhip_prof.so ]; then
   SRLHIP_LIB=$R/robotics-rl-srl_amd/csrc/build/libsrlhip_prof.so timeout 300 python profiles/probes/kuka_tree_phases.py 2048 > $OUT/kuka_tree_phases.txt 2>&1

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/profiles_final
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 900 python $R/bench.py > $OUT/bench_default.json 2>/dev/null
+timeout 900 python $R/bench.py --full > $OUT/bench_default.json 2>/dev/null
 for w in kuka kuka_pixels; do
   rm -rf /tmp/prof_$w
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$w -o $w -- python $R/bench.py --workload $w --no-cpu-baseline --no-secondary --no-live-pmc > $OUT/bench_$w.json 2>/dev/null

@@ -2,7 +2,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/profiles_final5
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 900 python $R/bench.py > $OUT/bench_default.json 2>/dev/null
+timeout 900 python $R/bench.py --full > $OUT/bench_default.json 2>/dev/null
 rm -rf /tmp/prof_kuka
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kuka -o kuka -- python $R/bench.py --workload kuka --no-cpu-baseline --no-secondary --no-live-pmc > $OUT/bench_kuka.json 2>/dev/null
 cp $(find /tmp/prof_kuka -name "*kernel_stats.csv" | head -1) $OUT/kuka_kernel_stats.csv

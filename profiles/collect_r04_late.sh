@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/profiles_late
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 900 python $R/bench.py > $OUT/bench_default.json 2>/dev/null
+timeout 900 python $R/bench.py --full > $OUT/bench_default.json 2>/dev/null
 rm -rf /tmp/prof_mobile
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_mobile -o mobile -- python $R/bench.py --workload mobile --no-cpu-baseline --no-secondary --no-live-pmc > $OUT/bench_mobile.json 2>/dev/null
 cp $(find /tmp/prof_mobile -name "*kernel_stats.csv" | head -1) $OUT/mobile_kernel_stats.csv

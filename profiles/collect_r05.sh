@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/profiles_r05
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 900 python $R/bench.py > $OUT/bench_default.json 2>$OUT/bench_default.err
+timeout 900 python $R/bench.py --full > $OUT/bench_default.json 2>$OUT/bench_default.err
 for w in kuka mobile kuka_pixels; do
   rm -rf /tmp/prof_$w
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$w -o $w -- python $R/bench.py --workload $w --no-cpu-baseline --no-secondary --no-live-pmc > $OUT/bench_$w.json 2>/dev/null
@@ -30,7 +30,7 @@ timeout 300 python profiles/probes/kuka_launch_cost.py > $OUT/kuka_launch_cost.t
 timeout 300 python profiles/probes/vecenv_latency.py > $OUT/vecenv_latency.txt 2>&1
 timeout 300 python profiles/probes/ik_crossing_extent.py > $OUT/ik_crossing_extent.json 2>$OUT/ik_crossing_extent.err
 timeout 300 python profiles/encoder_microbench.py > $OUT/encoder_microbench.txt 2>&1
-SRLHIP_SINGLE_DEVICE=1 SRLHIP_DIST_BACKEND=gloo timeout 600 python bench.py --workload kuka_pixels --gpus 8 2>/dev/null | grep "^{" > $OUT/bench_pixels_gpus8_single_device.json
+SRLHIP_SINGLE_DEVICE=1 SRLHIP_DIST_BACKEND=gloo timeout 600 python bench.py --workload kuka_pixels --gpus 8 --full 2>/dev/null | grep "^{" > $OUT/bench_pixels_gpus8_single_device.json
 if [ -f robotics-rl-srl_amd/csrc/build/libsrlhip_prof.so ]; then
   SRLHIP_LIB=$R/robotics-rl-srl_amd/csrc/build/libsrlhip_prof.so timeout 300 python profiles/probes/kuka_tree_phases.py 2048 > $OUT/kuka_tree_phases.txt 2>&1
 fi

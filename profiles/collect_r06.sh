@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/profiles_r06
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 1200 python $R/bench.py > $OUT/bench_default.json 2>$OUT/bench_default.err
+timeout 1200 python $R/bench.py --full > $OUT/bench_default.json 2>$OUT/bench_default.err
 for w in kuka mobile kuka_pixels; do
   rm -rf /tmp/prof_$w
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$w -o $w -- python $R/bench.py --workload $w --no-cpu-baseline --no-secondary --no-live-pmc > $OUT/bench_$w.json 2>/dev/null
@@ -55,7 +55,7 @@ for n in 1 2 3 4 5 6; do
   [ -f robotics-rl-srl_amd/csrc/build/libsrlhip_egx$n.so ] && SRLHIP_LIB=$R/robotics-rl-srl_amd/csrc/build/libsrlhip_egx$n.so timeout 200 python profiles/probes/encoder_general_layer_times.py 2>&1 | grep "ms per" >> $OUT/encoder_general_experiments.txt
 done
 timeout 200 python profiles/probes/encoder_general_layer_times.py 2>&1 | grep "ms per" >> $OUT/encoder_general_experiments.txt
-SRLHIP_SINGLE_DEVICE=1 SRLHIP_DIST_BACKEND=gloo timeout 600 python bench.py --workload kuka_pixels --gpus 8 2>/dev/null | grep "^{" > $OUT/bench_pixels_gpus8_single_device.json
+SRLHIP_SINGLE_DEVICE=1 SRLHIP_DIST_BACKEND=gloo timeout 600 python bench.py --workload kuka_pixels --gpus 8 --full 2>/dev/null | grep "^{" > $OUT/bench_pixels_gpus8_single_device.json
 for n in 4096 16384 65536; do
   timeout 300 python bench.py --workload kuka --no-cpu-baseline --no-secondary --no-live-pmc --envs-per-gpu $n --steps 3 --inner-steps 1024 >> $OUT/nsweep_kuka.jsonl 2>/dev/null
 done
