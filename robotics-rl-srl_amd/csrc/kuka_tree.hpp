@@ -408,63 +408,126 @@ template <int K> SRL_G void msum_step(double &acc, double x, const double m[NJ])
     if constexpr (K + 1 < NJ) msum_step<K + 1>(acc, x, m);
 }
 SRL_G double msum(double x, const double m[NJ], double base = 0.0) { double acc = base; msum_step<0>(acc, x, m); return acc; }
-// three masked sums at once: a serial chain of 12 dependent v_fmac_f64_dpp costs ~9 cycles per term (+ the DPP hazard nop); with
-// three independent chains interleaved in one statement per source lane every instruction issues back to back
-template <int K> SRL_G void msum3_step(double &a0, double &a1, double &a2, double x0, double x1, double x2, const double m[NJ]) {
-#if SRL_G_DEVICE
-    asm("s_nop 1\n\tv_fmac_f64_dpp %0, %3, %6 row_newbcast:%7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %1, %4, %6 row_newbcast:%7 row_mask:0xf bank_mask:0xf\n\t"
-        "v_fmac_f64_dpp %2, %5, %6 row_newbcast:%7 row_mask:0xf bank_mask:0xf"
-        : "+v"(a0), "+v"(a1), "+v"(a2) : "v"(x0), "v"(x1), "v"(x2), "v"(m[K]), "n"(K));
-#else
-    a0 = fma(grp::host_exchange(x0, K), m[K], a0); a1 = fma(grp::host_exchange(x1, K), m[K], a1); a2 = fma(grp::host_exchange(x2, K), m[K], a2);
-#endif
-    if constexpr (K + 1 < NJ) msum3_step<K + 1>(a0, a1, a2, x0, x1, x2, m);
-}
+// ---- the DPP statements of the dynamics.  A v_fmac_f64_dpp may not read a VGPR that one of the two VALU instructions before it
+// wrote: a statement opens with `s_nop 1` (the compiler may have written an operand just before it), which with one wavefront per
+// SIMD costs two of its issue slots.  Each helper below is therefore ONE statement per call, ordered so that inside it no input operand
+// is written and every accumulator is re-read at least three instructions after its write (two independent instructions between):
+// one hazard nop per call where there was one per source lane (the nine msum3 of the dynamics, CRBA and the IK's J^T J paid ~210 of
+// them per step, profiles/NOTES.md section AB).
+// Every accumulator still sums the same products in the same order as the one-instruction-per-statement form (fmac_bcast).
+// The outputs are early-clobber ("+&v"): a statement writes accumulators before it has read all of its inputs, so no input may
+// share a register with an output (without the `&` the register allocator did put low[j] on M[j] in transpose_low, equal SSA
+// values after `W[k] = low[k]`, and rows j = 1..5 read the updated M[j]).  profiles/probes/dpp_statement_lint.py checks on the built
+// objects that no instruction of such a statement reads a register an earlier one of it wrote (tests/test_isa_lint_dpp_statements.py).
+// The operand numbers below are written out for 12 joint lanes and 7 arm joints.
+static_assert(NJ == 12 && NA == 7, "the DPP statements of msum3 / dot6_all12 / dot6_arm / transpose_low are spelled out for NJ = 12, NA = 7");
+#define SRL_D(D, S, W, K) "v_fmac_f64_dpp %" #D ", %" #S ", %" #W " row_newbcast:" #K " row_mask:0xf bank_mask:0xf\n\t"
+// three masked sums at once: out[j] = base_j + sum_k bcast_k(x[j]) * m[k] (k = 0..11 in order, base = 0, 0, base2); three
+// independent chains interleaved, so every instruction issues back to back (a dependent f64 DPP FMA issues every ~9 cycles)
 SRL_G void msum3(const double x[3], const double m[NJ], double out[3], double base2 = 0.0) {
     double a0 = 0.0, a1 = 0.0, a2 = base2;
-    msum3_step<0>(a0, a1, a2, x[0], x[1], x[2], m);
+#if SRL_G_DEVICE
+    asm("s_nop 1\n\t"
+        SRL_D(0, 3, 6, 0) SRL_D(1, 4, 6, 0) SRL_D(2, 5, 6, 0) SRL_D(0, 3, 7, 1) SRL_D(1, 4, 7, 1) SRL_D(2, 5, 7, 1)
+        SRL_D(0, 3, 8, 2) SRL_D(1, 4, 8, 2) SRL_D(2, 5, 8, 2) SRL_D(0, 3, 9, 3) SRL_D(1, 4, 9, 3) SRL_D(2, 5, 9, 3)
+        SRL_D(0, 3, 10, 4) SRL_D(1, 4, 10, 4) SRL_D(2, 5, 10, 4) SRL_D(0, 3, 11, 5) SRL_D(1, 4, 11, 5) SRL_D(2, 5, 11, 5)
+        SRL_D(0, 3, 12, 6) SRL_D(1, 4, 12, 6) SRL_D(2, 5, 12, 6) SRL_D(0, 3, 13, 7) SRL_D(1, 4, 13, 7) SRL_D(2, 5, 13, 7)
+        SRL_D(0, 3, 14, 8) SRL_D(1, 4, 14, 8) SRL_D(2, 5, 14, 8) SRL_D(0, 3, 15, 9) SRL_D(1, 4, 15, 9) SRL_D(2, 5, 15, 9)
+        SRL_D(0, 3, 16, 10) SRL_D(1, 4, 16, 10) SRL_D(2, 5, 16, 10) SRL_D(0, 3, 17, 11) SRL_D(1, 4, 17, 11) SRL_D(2, 5, 17, 11)
+        : "+&v"(a0), "+&v"(a1), "+&v"(a2)
+        : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]), "v"(m[4]), "v"(m[5]), "v"(m[6]), "v"(m[7]),
+          "v"(m[8]), "v"(m[9]), "v"(m[10]), "v"(m[11]));
+#else
+    for (int k = 0; k < NJ; k++) {
+        a0 = fma(grp::host_exchange(x[0], k), m[k], a0); a1 = fma(grp::host_exchange(x[1], k), m[k], a1);
+        a2 = fma(grp::host_exchange(x[2], k), m[k], a2);
+    }
+#endif
     out[0] = a0; out[1] = a1; out[2] = a2;
 }
 template <int K, int N> SRL_G void ball_step(double x, double *out) {
     out[K] = bcast<K>(x);
     if constexpr (K + 1 < N) ball_step<K + 1, N>(x, out);
 }
-// out[K] = sum_c a[c] * bcast_K(b[c]) for K = 0..11, accumulated column by column: twelve independent chains per statement
+// out[K] = sum_c a[c] * bcast_K(b[c]) for K = 0..11, accumulated column by column (c = 0..5): twelve independent chains
 SRL_G void dot6_all12(const double a[6], const double b[6], double out[NJ]) {
 #pragma unroll
     for (int k = 0; k < NJ; k++) out[k] = 0.0;
-#pragma unroll
-    for (int c = 0; c < 6; c++) {
 #if SRL_G_DEVICE
-#define SRL_F(K) "v_fmac_f64_dpp %" #K ", %12, %13 row_newbcast:" #K " row_mask:0xf bank_mask:0xf\n\t"
-        asm("s_nop 1\n\t" SRL_F(0) SRL_F(1) SRL_F(2) SRL_F(3) SRL_F(4) SRL_F(5) SRL_F(6) SRL_F(7) SRL_F(8) SRL_F(9) SRL_F(10) SRL_F(11)
-            : "+v"(out[0]), "+v"(out[1]), "+v"(out[2]), "+v"(out[3]), "+v"(out[4]), "+v"(out[5]), "+v"(out[6]), "+v"(out[7]), "+v"(out[8]),
-              "+v"(out[9]), "+v"(out[10]), "+v"(out[11])
-            : "v"(b[c]), "v"(a[c]));
-#undef SRL_F
+    asm("s_nop 1\n\t"
+        SRL_D(0, 12, 18, 0) SRL_D(1, 12, 18, 1) SRL_D(2, 12, 18, 2) SRL_D(3, 12, 18, 3) SRL_D(4, 12, 18, 4) SRL_D(5, 12, 18, 5)
+        SRL_D(6, 12, 18, 6) SRL_D(7, 12, 18, 7) SRL_D(8, 12, 18, 8) SRL_D(9, 12, 18, 9) SRL_D(10, 12, 18, 10)
+        SRL_D(11, 12, 18, 11) SRL_D(0, 13, 19, 0) SRL_D(1, 13, 19, 1) SRL_D(2, 13, 19, 2) SRL_D(3, 13, 19, 3)
+        SRL_D(4, 13, 19, 4) SRL_D(5, 13, 19, 5) SRL_D(6, 13, 19, 6) SRL_D(7, 13, 19, 7) SRL_D(8, 13, 19, 8) SRL_D(9, 13, 19, 9)
+        SRL_D(10, 13, 19, 10) SRL_D(11, 13, 19, 11) SRL_D(0, 14, 20, 0) SRL_D(1, 14, 20, 1) SRL_D(2, 14, 20, 2)
+        SRL_D(3, 14, 20, 3) SRL_D(4, 14, 20, 4) SRL_D(5, 14, 20, 5) SRL_D(6, 14, 20, 6) SRL_D(7, 14, 20, 7) SRL_D(8, 14, 20, 8)
+        SRL_D(9, 14, 20, 9) SRL_D(10, 14, 20, 10) SRL_D(11, 14, 20, 11) SRL_D(0, 15, 21, 0) SRL_D(1, 15, 21, 1)
+        SRL_D(2, 15, 21, 2) SRL_D(3, 15, 21, 3) SRL_D(4, 15, 21, 4) SRL_D(5, 15, 21, 5) SRL_D(6, 15, 21, 6) SRL_D(7, 15, 21, 7)
+        SRL_D(8, 15, 21, 8) SRL_D(9, 15, 21, 9) SRL_D(10, 15, 21, 10) SRL_D(11, 15, 21, 11) SRL_D(0, 16, 22, 0)
+        SRL_D(1, 16, 22, 1) SRL_D(2, 16, 22, 2) SRL_D(3, 16, 22, 3) SRL_D(4, 16, 22, 4) SRL_D(5, 16, 22, 5) SRL_D(6, 16, 22, 6)
+        SRL_D(7, 16, 22, 7) SRL_D(8, 16, 22, 8) SRL_D(9, 16, 22, 9) SRL_D(10, 16, 22, 10) SRL_D(11, 16, 22, 11)
+        SRL_D(0, 17, 23, 0) SRL_D(1, 17, 23, 1) SRL_D(2, 17, 23, 2) SRL_D(3, 17, 23, 3) SRL_D(4, 17, 23, 4) SRL_D(5, 17, 23, 5)
+        SRL_D(6, 17, 23, 6) SRL_D(7, 17, 23, 7) SRL_D(8, 17, 23, 8) SRL_D(9, 17, 23, 9) SRL_D(10, 17, 23, 10)
+        SRL_D(11, 17, 23, 11)
+        : "+&v"(out[0]), "+&v"(out[1]), "+&v"(out[2]), "+&v"(out[3]), "+&v"(out[4]), "+&v"(out[5]), "+&v"(out[6]), "+&v"(out[7]), "+&v"(out[8]),
+          "+&v"(out[9]), "+&v"(out[10]), "+&v"(out[11])
+        : "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(b[4]), "v"(b[5]), "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]));
 #else
+    for (int c = 0; c < 6; c++)
         for (int k = 0; k < NJ; k++) out[k] = fma(grp::host_exchange(b[c], k), a[c], out[k]);
 #endif
-    }
 }
-template <int K, int N> SRL_G void dot6_step(const double a[6], const double b[6], double *out) {
-    double acc = 0.0;
+// out[K] = sum_c a[c] * bcast_K(b[c]) for K = 0..NA-1 (the IK's J^T J rows), c = 0..5 in order: seven independent chains
+SRL_G void dot6_arm(const double a[6], const double b[6], double out[NA]) {
 #pragma unroll
-    for (int c = 0; c < 6; c++) fmac_bcast<K>(acc, b[c], a[c]);
-    out[K] = acc;
-    if constexpr (K + 1 < N) dot6_step<K + 1, N>(a, b, out);
+    for (int k = 0; k < NA; k++) out[k] = 0.0;
+#if SRL_G_DEVICE
+    asm("s_nop 1\n\t"
+        SRL_D(0, 7, 13, 0) SRL_D(1, 7, 13, 1) SRL_D(2, 7, 13, 2) SRL_D(3, 7, 13, 3) SRL_D(4, 7, 13, 4) SRL_D(5, 7, 13, 5)
+        SRL_D(6, 7, 13, 6) SRL_D(0, 8, 14, 0) SRL_D(1, 8, 14, 1) SRL_D(2, 8, 14, 2) SRL_D(3, 8, 14, 3) SRL_D(4, 8, 14, 4)
+        SRL_D(5, 8, 14, 5) SRL_D(6, 8, 14, 6) SRL_D(0, 9, 15, 0) SRL_D(1, 9, 15, 1) SRL_D(2, 9, 15, 2) SRL_D(3, 9, 15, 3)
+        SRL_D(4, 9, 15, 4) SRL_D(5, 9, 15, 5) SRL_D(6, 9, 15, 6) SRL_D(0, 10, 16, 0) SRL_D(1, 10, 16, 1) SRL_D(2, 10, 16, 2)
+        SRL_D(3, 10, 16, 3) SRL_D(4, 10, 16, 4) SRL_D(5, 10, 16, 5) SRL_D(6, 10, 16, 6) SRL_D(0, 11, 17, 0) SRL_D(1, 11, 17, 1)
+        SRL_D(2, 11, 17, 2) SRL_D(3, 11, 17, 3) SRL_D(4, 11, 17, 4) SRL_D(5, 11, 17, 5) SRL_D(6, 11, 17, 6) SRL_D(0, 12, 18, 0)
+        SRL_D(1, 12, 18, 1) SRL_D(2, 12, 18, 2) SRL_D(3, 12, 18, 3) SRL_D(4, 12, 18, 4) SRL_D(5, 12, 18, 5) SRL_D(6, 12, 18, 6)
+        : "+&v"(out[0]), "+&v"(out[1]), "+&v"(out[2]), "+&v"(out[3]), "+&v"(out[4]), "+&v"(out[5]), "+&v"(out[6])
+        : "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(b[4]), "v"(b[5]), "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]));
+#else
+    for (int c = 0; c < 6; c++)
+        for (int k = 0; k < NA; k++) out[k] = fma(grp::host_exchange(b[c], k), a[c], out[k]);
+#endif
 }
-// M[K] on lane j < K takes lane K's low[j] (the mirrored half of the mass matrix).  Ordered by j, then K: the targets M[K] of
-// consecutive instructions are independent (ordered by K, every M[K] was a serial chain of K dependent DPP FMAs).
-template <int J, int K> SRL_G void transpose_inner(const TL &L, const double low[NJ], double M[NJ]) {
-    fmac_bcast<K>(M[K], low[J], L.e(J));
-    if constexpr (K + 1 < NJ) transpose_inner<J, K + 1>(L, low, M);
+// M[K] on lane j < K takes lane K's low[j] (the mirrored half of the mass matrix): M[K] += bcast_K(low[j]) * e_j, j = 0..K-1 in order.
+// Ordered by j, then K, so that consecutive instructions write different M[K]; two statements (j < 6, j >= 6: at most 23 operands
+// each), and in the second the short tail of j = 9, 10 gets the two wait states its re-read accumulators need from nops.
+SRL_G void transpose_low(const TL &L, const double low[NJ], double M[NJ]) {
+#if SRL_G_DEVICE
+    asm("s_nop 1\n\t"
+        SRL_D(0, 11, 17, 1) SRL_D(1, 11, 17, 2) SRL_D(2, 11, 17, 3) SRL_D(3, 11, 17, 4) SRL_D(4, 11, 17, 5) SRL_D(5, 11, 17, 6)
+        SRL_D(6, 11, 17, 7) SRL_D(7, 11, 17, 8) SRL_D(8, 11, 17, 9) SRL_D(9, 11, 17, 10) SRL_D(10, 11, 17, 11)
+        SRL_D(1, 12, 18, 2) SRL_D(2, 12, 18, 3) SRL_D(3, 12, 18, 4) SRL_D(4, 12, 18, 5) SRL_D(5, 12, 18, 6) SRL_D(6, 12, 18, 7)
+        SRL_D(7, 12, 18, 8) SRL_D(8, 12, 18, 9) SRL_D(9, 12, 18, 10) SRL_D(10, 12, 18, 11) SRL_D(2, 13, 19, 3)
+        SRL_D(3, 13, 19, 4) SRL_D(4, 13, 19, 5) SRL_D(5, 13, 19, 6) SRL_D(6, 13, 19, 7) SRL_D(7, 13, 19, 8) SRL_D(8, 13, 19, 9)
+        SRL_D(9, 13, 19, 10) SRL_D(10, 13, 19, 11) SRL_D(3, 14, 20, 4) SRL_D(4, 14, 20, 5) SRL_D(5, 14, 20, 6)
+        SRL_D(6, 14, 20, 7) SRL_D(7, 14, 20, 8) SRL_D(8, 14, 20, 9) SRL_D(9, 14, 20, 10) SRL_D(10, 14, 20, 11)
+        SRL_D(4, 15, 21, 5) SRL_D(5, 15, 21, 6) SRL_D(6, 15, 21, 7) SRL_D(7, 15, 21, 8) SRL_D(8, 15, 21, 9)
+        SRL_D(9, 15, 21, 10) SRL_D(10, 15, 21, 11) SRL_D(5, 16, 22, 6) SRL_D(6, 16, 22, 7) SRL_D(7, 16, 22, 8)
+        SRL_D(8, 16, 22, 9) SRL_D(9, 16, 22, 10) SRL_D(10, 16, 22, 11)
+        : "+&v"(M[1]), "+&v"(M[2]), "+&v"(M[3]), "+&v"(M[4]), "+&v"(M[5]), "+&v"(M[6]), "+&v"(M[7]), "+&v"(M[8]), "+&v"(M[9]), "+&v"(M[10]), "+&v"(M[11])
+        : "v"(low[0]), "v"(low[1]), "v"(low[2]), "v"(low[3]), "v"(low[4]), "v"(low[5]),
+          "v"(L.e(0)), "v"(L.e(1)), "v"(L.e(2)), "v"(L.e(3)), "v"(L.e(4)), "v"(L.e(5)));
+    asm("s_nop 1\n\t"
+        SRL_D(0, 5, 10, 7) SRL_D(1, 5, 10, 8) SRL_D(2, 5, 10, 9) SRL_D(3, 5, 10, 10) SRL_D(4, 5, 10, 11) SRL_D(1, 6, 11, 8)
+        SRL_D(2, 6, 11, 9) SRL_D(3, 6, 11, 10) SRL_D(4, 6, 11, 11) SRL_D(2, 7, 12, 9) SRL_D(3, 7, 12, 10) SRL_D(4, 7, 12, 11)
+        "s_nop 0\n\t" SRL_D(3, 8, 13, 10) SRL_D(4, 8, 13, 11) "s_nop 1\n\t" SRL_D(4, 9, 14, 11)
+        : "+&v"(M[7]), "+&v"(M[8]), "+&v"(M[9]), "+&v"(M[10]), "+&v"(M[11])
+        : "v"(low[6]), "v"(low[7]), "v"(low[8]), "v"(low[9]), "v"(low[10]), "v"(L.e(6)), "v"(L.e(7)), "v"(L.e(8)), "v"(L.e(9)), "v"(L.e(10)));
+#else
+    for (int j = 0; j < NJ - 1; j++)
+        for (int k = j + 1; k < NJ; k++) M[k] = fma(grp::host_exchange(low[j], k), L.e(j), M[k]);
+#endif
 }
-template <int J> SRL_G void transpose_step(const TL &L, const double low[NJ], double M[NJ]) {
-    transpose_inner<J, J + 1>(L, low, M);
-    if constexpr (J + 2 < NJ) transpose_step<J + 1>(L, low, M);
-}
+#undef SRL_D
 template <int K, int N> SRL_G void rdot_step(double &acc, const double *row, double x) {
     fmac_bcast<K>(acc, x, row[K]);
     if constexpr (K + 1 < N) rdot_step<K + 1, N>(acc, row, x);
@@ -1518,7 +1581,7 @@ SRL_G void tdynamics(const TL &L, const GState &g, const double S[6], double qd,
 #pragma unroll
             for (int k = 0; k < NJ; k++) { low[k] *= le[k] * L.jm; W[k] = low[k]; }
         }
-        transpose_step<0>(L, low, W);
+        transpose_low(L, low, W);
         SRL_TSTAMP(4);                      // mass matrix (CRBA)
         double unused = 0.0;
         gj_step<0, NJ, true>(L, W, unused);
@@ -1600,7 +1663,7 @@ SRL_G void tphysics_step(Env &e, GState &g, const double *tab, const Cfg &cfg, d
             dS[3] = angle * ax; dS[4] = angle * ay; dS[5] = angle * az;
         }
         double A[NA], bb = 0.0;
-        dot6_step<0, NA>(J, J, A);
+        dot6_arm(J, J, A);
         const double damping = cfg.two ? kIkDampingDefault : kIkDamping;
 #pragma unroll
         for (int k = 0; k < NA; k++) A[k] = fma(damping, L.e(k), A[k]);
@@ -2079,7 +2142,7 @@ SRL_G void tphysics_post2(Env &e, GState &g, const double *tab, const Cfg &cfg, 
             dS[3] = angle * ax; dS[4] = angle * ay; dS[5] = angle * az;
         }
         double A[NA], bb = 0.0;
-        dot6_step<0, NA>(J, J, A);
+        dot6_arm(J, J, A);
         const double damping = cfg.two ? kIkDampingDefault : kIkDamping;
 #pragma unroll
         for (int k = 0; k < NA; k++) A[k] = fma(damping, L.e(k), A[k]);
