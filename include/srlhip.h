@@ -152,7 +152,12 @@ int srlhip_reset_rand_count(srlhip_handle h);
 /* Replaces VecEnv.step / <Env>.step (mobile_robot_env.py:235-280,
  * kuka_button_gym_env.py:293-368) for the whole batch.
  * actions: discrete -> int32[num_envs], value -1 == the reference's `None`
- *          action (kuka_button_gym_env.py:295-299);  continuous -> float[num_envs][adim].
+ *          action (kuka_button_gym_env.py:295-299);  continuous -> float[num_envs][adim].  On a Kuka handle a
+ *          continuous row whose every component is NaN is that same `None` (no noise draw; Cartesian mode: zero
+ *          increment, joint mode: targets held at the initial joint positions).  Host-pointer calls return SRLHIP_EINVAL
+ *          for every other non-finite value (a partly NaN row, an infinity) and for any NaN on a MobileRobot handle
+ *          (whose reference step has no continuous `None`); device-pointer calls own their buffers, and there the
+ *          kernels look at component 0 only.
  * host_noise: RNG_HOST only — double[num_envs], value of np_random.normal(...) per env.
  * obs_out [num_envs][obs], reward_out float[num_envs], done_out uint8[num_envs].
  * With cfg.auto_reset the observation of a finished env is the first one of its
@@ -198,14 +203,16 @@ int srlhip_step_pending(srlhip_handle h);
  * holds one wavefront slot and 40 KB of LDS on every SIMD it uses (all of them at 4096 envs): use it when the policy runs on
  * the host or on another device (a random agent, ARS / CMA-ES with a numpy policy, a policy server) and answers within park_us.
  * A workgroup that could not become resident shows up as a step that never completes: srlhip_step_wait then parks the kernel
- * and fails with SRLHIP_EHIP after ~20 s instead of hanging.  on = 0 switches back to launches. */
+ * and fails with SRLHIP_EHIP after ~20 s instead of hanging.  on = 0 switches back to launches.  The actions are those of
+ * srlhip_step: -1, or a continuous row of NaNs, is `None` (the part of the step run before the action holds for it too). */
 int srlhip_set_persistent(srlhip_handle h, int32_t on, int32_t park_us);
 
 /* Fused rollout: T consecutive steps with auto-reset, outputs streamed as
  * [T][num_envs] planes.  Replaces the random-agent hot loop
  * (rl_baselines/random_agent.py:35-42, dataset_generator.py:91-105).
  * actions_TN: int32/float [T][num_envs]([adim]) or NULL -> uniform random
- * actions drawn on the device (returned in act_out_TN if not NULL).
+ * actions drawn on the device (returned in act_out_TN if not NULL).  `None` rows as in srlhip_step
+ * (-1; on a Kuka handle with continuous actions a row of NaNs), checked the same way on host pointers.
  * Requires cfg.auto_reset and rng_mode != HOST.  Any output may be NULL. */
 int srlhip_rollout(srlhip_handle h, int32_t T, const void *actions_TN,
                    void *obs_TN, float *reward_TN, uint8_t *done_TN, void *act_out_TN);

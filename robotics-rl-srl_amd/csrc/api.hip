@@ -200,6 +200,22 @@ __global__ void episode_stats_k(EpisodeStats st, int n, float *ret, int32_t *len
 // np.clip / pybullet would raise or saturate).  Device-pointer callers own their buffers' contents.
 bool all_finite_f32(const float *p, size_t count) { for (size_t i = 0; i < count; i++) if (!std::isfinite(p[i])) return false; return true; }
 bool all_finite_f64(const double *p, size_t count) { for (size_t i = 0; i < count; i++) if (!std::isfinite(p[i])) return false; return true; }
+// Continuous actions of a Kuka handle, rows of `dim`: every row all finite, or all NaN (the reference's `None`, include/srlhip.h).
+// One pass; a partly NaN row and any infinity fail.
+bool kuka_rows_ok(const float *p, size_t rows, int dim) {
+    for (size_t r = 0; r < rows; r++, p += dim) {
+        int fin = 0, nan = 0;
+        for (int j = 0; j < dim; j++) { fin += std::isfinite(p[j]) ? 1 : 0; nan += std::isnan(p[j]) ? 1 : 0; }
+        if (fin != dim && nan != dim) return false;
+    }
+    return true;
+}
+// the host-pointer check of a continuous action plane: MobileRobot takes finite values only (its step has no `None` branch for
+// continuous actions: `action[0]` on None raises), Kuka finite or NaN rows
+bool continuous_actions_ok(const Handle *h, const float *p, size_t rows) {
+    const int dim = action_dim_of(h->cfg);
+    return is_mobile(h->cfg.env_kind) ? all_finite_f32(p, rows * (size_t)dim) : kuka_rows_ok(p, rows, dim);
+}
 
 int field_lookup(Handle *h, int field, void **dptr, size_t *elem, int *count) {
     *count = 1;
@@ -449,8 +465,8 @@ int host_step_begin(Handle *h, const void *actions, const double *host_noise, bo
     const int n = h->n;
     const StepLayout L = step_layout(h);
     int rc;
-    if (!h->cfg.is_discrete && !all_finite_f32(static_cast<const float *>(actions), L.ab / sizeof(float)))
-        return h->fail(SRLHIP_EINVAL, "step: non-finite continuous action");
+    if (!h->cfg.is_discrete && !continuous_actions_ok(h, static_cast<const float *>(actions), (size_t)n))
+        return h->fail(SRLHIP_EINVAL, "step: non-finite continuous action (a Kuka env's `None` is a row of NaNs)");
     if (host_noise && !all_finite_f64(host_noise, (size_t)n)) return h->fail(SRLHIP_EINVAL, "step: non-finite host_noise");
     if ((rc = ensure_pinned(h, &h->pin_in, &h->pin_in_sz, L.in_total)) || (rc = ensure_pinned(h, &h->pin_out, &h->pin_out_sz, L.out_total)))
         return rc;
@@ -703,8 +719,8 @@ int srlhip_rollout(srlhip_handle hh, int32_t T, const void *actions_TN, void *ob
     void *d_act_out = act_out_TN;
     const size_t ob = obs_bytes_per_env(h) * tn, ab = action_bytes(h) * (size_t)T;
     if (!h->cfg.io_device) {
-        if (actions_TN && !h->cfg.is_discrete && !all_finite_f32(static_cast<const float *>(actions_TN), ab / sizeof(float)))
-            return h->fail(SRLHIP_EINVAL, "rollout: non-finite continuous action");
+        if (actions_TN && !h->cfg.is_discrete && !continuous_actions_ok(h, static_cast<const float *>(actions_TN), tn))
+            return h->fail(SRLHIP_EINVAL, "rollout: non-finite continuous action (a Kuka env's `None` is a row of NaNs)");
         if (actions_TN) { if ((rc = stage_in(h, &h->st_actions, &h->st_actions_sz, actions_TN, ab))) return rc; d_act = h->st_actions; }
         else if (act_out_TN) { if ((rc = ensure(h, &h->st_actions, &h->st_actions_sz, ab))) return rc; d_act_out = h->st_actions; }
         if (obs_TN) { if ((rc = ensure(h, &h->st_obs, &h->st_obs_sz, ob))) return rc; d_obs = h->st_obs; }

@@ -244,6 +244,15 @@ SRL_HD void step_command(Env &e, const Cfg &cfg, R &rng, int action, const float
     }
     e.motor_on = 1;
 }
+// A continuous action row whose component 0 is a NaN is the reference's `None` (include/srlhip.h; host-pointer calls pass only all-NaN
+// rows).  Tested by its bits: the full-model objects are built with -fno-honor-nans, where isnan(x) and x != x may fold to false.  Mapped
+// to the discrete `None` (action -1: no draw, step_command above) with the row zeroed, so that no NaN reaches floating-point code.
+SRL_HD void continuous_none(int &action, float (&ca)[7]) {
+    const bool none = (__builtin_bit_cast(uint32_t, ca[0]) & 0x7fffffffu) > 0x7f800000u;
+    action = none ? -1 : action;
+#pragma unroll
+    for (int j = 0; j < 7; j++) ca[j] = none ? 0.f : ca[j];
+}
 // joint target of joint j in joints mode: float32 action * python float stays float32, + float64 list -> float64
 SRL_HD double joint_target(const StepCmd &c, float a, double q0) {
 #pragma clang fp contract(off)

@@ -66,7 +66,10 @@ kuka_group_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, in
         int a = 0; float ca[7] = {0, 0, 0, 0, 0, 0, 0};
         if constexpr (GIVEN) {
             if (cfg.is_discrete) a = static_cast<const int32_t *>(actions)[row];
-            else for (int j = 0; j < adim; j++) ca[j] = static_cast<const float *>(actions)[row * adim + j];
+            else {
+                for (int j = 0; j < adim; j++) ca[j] = static_cast<const float *>(actions)[row * adim + j];
+                continuous_none(a, ca);                    // a NaN row is `None` (kuka_env.hpp)
+            }
         } else {
             if (cfg.is_discrete) a = gact.next(5);
             else for (int j = 0; j < adim; j += 2) {

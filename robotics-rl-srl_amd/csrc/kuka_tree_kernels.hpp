@@ -329,10 +329,16 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
             if constexpr (kLaunchSplit) {
             } else if constexpr (PERSIST) {           // the same mapped row every step: re-read, never cached in a register
                 if (cfg.is_discrete) a = __hip_atomic_load(reinterpret_cast<const int32_t *>(given_p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                else for (int j = 0; j < adim; j++) ca[j] = __hip_atomic_load(reinterpret_cast<const float *>(given_p) + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                else {
+                    for (int j = 0; j < adim; j++) ca[j] = __hip_atomic_load(reinterpret_cast<const float *>(given_p) + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    continuous_none(a, ca);                // a NaN row is `None` (kuka_env.hpp)
+                }
             } else {
                 if (cfg.is_discrete) a = *reinterpret_cast<const int32_t *>(given_p);
-                else for (int j = 0; j < adim; j++) ca[j] = reinterpret_cast<const float *>(given_p)[j];
+                else {
+                    for (int j = 0; j < adim; j++) ca[j] = reinterpret_cast<const float *>(given_p)[j];
+                    continuous_none(a, ca);
+                }
                 given_p += act_stride;
             }
         } else {

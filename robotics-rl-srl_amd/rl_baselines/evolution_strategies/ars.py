@@ -6,14 +6,18 @@ The reference evaluates the 2 x n_population perturbed linear policies with a Py
 SubprocVecEnv step (ars.py:152-186).  Here the population is the batch: env 2k runs M + noise * delta_k, env 2k+1 runs
 M - noise * delta_k; one batched matmul + argmax (or softmax sampling) produces all actions as an int32 tensor that the
 stepper reads in place (DeviceVecEnv, io_device = 1), on the stepper's own HIP stream — no host round trip per step.
-Finished directions receive the `None` action (-1) exactly like the reference ("do nothing, as we are done")."""
+Finished directions receive the `None` action exactly like the reference ("do nothing, as we are done"): -1 with discrete actions,
+a row of NaNs with continuous actions on the Kuka envs (include/srlhip.h), whose step then draws no noise.  MobileRobot envs with
+continuous actions get zero rows instead: the reference's MobileRobotGymEnv.step has no continuous `None` (action[0] raises)."""
 import pickle
 import time
 
 import numpy as np
 import torch
 
+from srlhip import _lib
 from srlhip.device_env import DeviceVecEnv, DeviceVecFrameStack, DeviceVecNormalize
+from srlhip.envs import ENV_CLASSES
 
 
 class ARSModel(object):
@@ -98,14 +102,18 @@ class ARSModel(object):
         return envs
 
     @staticmethod
-    def batched_actions(obs, M, delta, noise, active, continuous, deterministic, generator=None):
+    def batched_actions(obs, M, delta, noise, active, continuous, deterministic, generator=None, none_rows=False):
         """obs [2P, D] (env 2k = +delta_k, env 2k+1 = -delta_k), M [D, A], delta [P, D, A] -> actions for every env.
-        Discrete: int32 [2P] with -1 for finished directions.  Continuous: float32 [2P, A] (zeros when finished)."""
+        Discrete: int32 [2P] with -1 (the reference's `None`) for finished directions.  Continuous: float32 [2P, A]; a finished
+        direction gets a row of NaNs with `none_rows` (the Kuka envs' `None`, include/srlhip.h: no noise draw, as in the reference,
+        ars.py:168-172) and zeros otherwise (MobileRobot: the reference's step has no continuous `None`)."""
         P = delta.shape[0]
         sign = torch.tensor([1.0, -1.0], dtype=M.dtype, device=M.device).view(1, 2, 1, 1)
         W = M.unsqueeze(0).unsqueeze(0) + noise * sign * delta.unsqueeze(1)              # [P, 2, D, A]
         out = torch.matmul(obs.view(P, 2, 1, -1).to(M.dtype), W).view(2 * P, -1)       # [2P, A]
         if continuous:
+            if none_rows:
+                return torch.where(active.unsqueeze(-1), out, torch.full_like(out, float("nan"))).to(torch.float32).contiguous()
             return (out * active.unsqueeze(-1).to(out.dtype)).to(torch.float32).contiguous()
         if deterministic:
             a = torch.argmax(out, dim=1)
@@ -120,6 +128,7 @@ class ARSModel(object):
         env = self.makeEnv(args, env_kwargs)
         args.__dict__.update(train_kwargs or {})
         continuous = bool(getattr(args, "continuous_actions", False))
+        none_rows = continuous and ENV_CLASSES[args.env].ENV_KIND >= _lib.ENV_KUKA_BUTTON      # finished directions: `None` where the reference has it
         action_space = int(np.prod(env.action_space.shape)) if continuous else env.action_space.n
         obs_dim = int(np.prod(env.observation_space.shape))
         self.n_population, self.top_population = args.num_population, args.top_population
@@ -145,7 +154,7 @@ class ARSModel(object):
                 obs = env.reset()
                 while True:
                     actions = self.batched_actions(obs, M, delta, self.exploration_noise, ~done, continuous,
-                                                   self.deterministic, gen)
+                                                   self.deterministic, gen, none_rows)
                     live_steps += (~done).any().to(torch.int64)
                     obs, reward, new_done = env.step(actions)
                     step += P

@@ -3,7 +3,9 @@ getAction / getActionProba / makeEnv / train / save / load, cma_es.py:24-140), e
 
 The reference asks the `cma` package for `num_population` parameter vectors of a small PyTorch MLP (observation -> 100 ->
 actions, cma_es.py:98-105,307-326), then loops over the population in Python — set the parameters, forward ONE observation
-— around a SubprocVecEnv step, `None` for finished members (cma_es.py:114-135).  Here the population is the batch:
+— around a SubprocVecEnv step, `None` for finished members (cma_es.py:114-135; here -1 with discrete actions, a row of NaNs with
+continuous actions on the Kuka envs — include/srlhip.h, no noise draw — and a zero row on MobileRobot envs, whose reference step has
+no continuous `None`).  Here the population is the batch:
 member k drives env k, all forwards are two batched matmuls on the stepper's own HIP stream (DeviceVecEnv, io_device = 1),
 the int32 action tensor is read by the stepper in place, and the only host read is a `done.all()` every 16 steps.
 
@@ -18,7 +20,9 @@ import time
 import numpy as np
 import torch
 
+from srlhip import _lib
 from srlhip.device_env import DeviceVecEnv, DeviceVecFrameStack, DeviceVecNormalize
+from srlhip.envs import ENV_CLASSES
 
 
 class CMAES(object):
@@ -184,6 +188,7 @@ class CMAESModel(object):
         env = self.makeEnv(args, env_kwargs=env_kwargs)
         args.__dict__.update(train_kwargs or {})
         continuous = bool(getattr(args, "continuous_actions", False))
+        none_rows = continuous and ENV_CLASSES[args.env].ENV_KIND >= _lib.ENV_KUKA_BUTTON      # finished members: `None` (Kuka)
         action_space = int(np.prod(env.action_space.shape)) if continuous else env.action_space.n
         self.policy = BatchedMLP(int(np.prod(env.observation_space.shape)), action_space)
         self.n_population, self.mu, self.sigma = args.num_population, args.mu, args.sigma
@@ -207,7 +212,9 @@ class CMAESModel(object):
                 k = 0
                 while True:
                     scores = self.policy.forward(population, obs)
-                    if continuous:
+                    if none_rows:
+                        actions = torch.where(done.unsqueeze(-1), torch.full_like(scores, float("nan")), scores).to(torch.float32).contiguous()
+                    elif continuous:
                         actions = (scores * (~done).unsqueeze(-1).to(scores.dtype)).to(torch.float32).contiguous()
                     else:
                         a = torch.argmax(scores, dim=1) if self.deterministic else \

@@ -241,7 +241,7 @@ class Handle(object):
             a = np.ascontiguousarray(actions, dtype=np.int32)
             assert a.shape == lead, (a.shape, lead)
         else:
-            a = np.ascontiguousarray(actions, dtype=np.float32)
+            a = np.ascontiguousarray(none_rows(actions, self.action_dim, len(lead)), dtype=np.float32)
             assert a.shape == lead + (self.action_dim,), (a.shape, lead)
         return a
 
@@ -458,6 +458,21 @@ class Handle(object):
 
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def none_rows(actions, dim, lead_ndim=1):
+    """Continuous actions that may hold the reference's `None` -> float32 [..., dim] with a row of NaNs for every `None` (include/srlhip.h:
+    a Kuka env's `None`; MobileRobot handles refuse it).  `lead_ndim` leading axes ([N]: 1, [T][N]: 2).  A numeric ndarray passes as
+    it is (NaN rows included): only lists and object arrays are scanned."""
+    if isinstance(actions, np.ndarray) and actions.dtype != object:
+        return np.asarray(actions, dtype=np.float32)
+    nan_row = np.full(dim, np.nan, np.float32)
+
+    def rows(x, depth):
+        if depth == 0:
+            return nan_row if x is None else np.asarray(x, dtype=np.float32).reshape(dim)
+        return np.stack([rows(y, depth - 1) for y in x]) if len(x) else np.zeros((0, dim), np.float32)
+    return rows(actions, lead_ndim)
 
 
 def encoder_supported(img_h, img_w, n_channels):

@@ -62,7 +62,8 @@ class DeviceVecEnv(object):
         return self.obs
 
     def step(self, actions):
-        """actions: int32 tensor [N] (-1 == the reference's None) or float32 tensor [N, action_dim], on this device.
+        """actions: int32 tensor [N] (-1 == the reference's None) or float32 tensor [N, action_dim], on this device; on a Kuka env a
+        continuous row of NaNs is the reference's None (include/srlhip.h: the kernels test component 0; device buffers are not checked).
         Returns (obs, rewards, dones): tensors owned by the env, overwritten by the next call."""
         want = torch.int32 if self.cfg.is_discrete else torch.float32
         assert actions.is_cuda and actions.dtype == want and actions.is_contiguous(), (actions.dtype, actions.device)

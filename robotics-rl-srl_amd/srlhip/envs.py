@@ -382,9 +382,8 @@ class KukaButtonGymEnv(_HipEnv):
             a = np.array([-1 if action is None else int(action)], dtype=np.int32)
         else:
             dim = 7 if self.action_joints else 3
-            if action is None:
-                raise NotImplementedError("None action with continuous actions: use the discrete env or HipVecEnv")
-            a = np.asarray(action, dtype=np.float32).reshape(1, dim)
+            # None: a row of NaNs (include/srlhip.h) — no noise draw; Cartesian: zero increment, joints: targets = joint_positions[:7]
+            a = np.full((1, dim), np.nan, np.float32) if action is None else np.asarray(action, dtype=np.float32).reshape(1, dim)
         _, _, done = self._h.step(a)
         reward = self._reward_value()
         obs = self._obs()

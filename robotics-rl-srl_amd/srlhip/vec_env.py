@@ -330,15 +330,25 @@ class HipVecEnv(object):
                 np.copyto(dst, actions.reshape(n), casting="unsafe")
             else:
                 dst[:] = np.array([-1 if a is None else int(a) for a in actions], dtype=np.int32)
-            # (range check: host-pointer handles do it inside srlhip_step_async while copying — no reductions over the batch here; the
-            #  device-pointer path of a learned SRL model checks below)
-            if self._fast is None and dst.size and (dst.min() < -1 or dst.max() >= nact):
+            # (range check: a single host-pointer handle does it inside srlhip_step_async while copying — no reductions over the batch
+            #  here; with several shards, or on the device-pointer path of a learned SRL model, the whole batch is checked before any
+            #  shard launches, so that a bad action cannot leave the shards at different steps)
+            if (self._fast is None or len(self._shards) > 1) and dst.size and (dst.min() < -1 or dst.max() >= nact):
                 raise IndexError("discrete action out of range [0, {}) (None/-1 = no-op)".format(nact))
         else:
-            # (a numeric ndarray cannot hold None: the per-element scan below would cost a 4096-iteration Python loop per step)
-            if not (isinstance(actions, np.ndarray) and actions.dtype != object) and any(a is None for a in actions):
-                raise NotImplementedError("None actions need a discrete action space")
-            dst[...] = np.asarray(actions, dtype=np.float32).reshape(n, self._shards[0].h.action_dim)
+            # `None` entries (lists, object arrays) become rows of NaNs, the Kuka envs' `None` (include/srlhip.h); a numeric ndarray is
+            # taken as it is, NaN rows included.  (A numeric ndarray cannot hold None: no per-element Python scan on that path.)
+            kuka = self.cfg.env_kind >= _lib.ENV_KUKA_BUTTON
+            if not kuka and not (isinstance(actions, np.ndarray) and actions.dtype != object) and any(a is None for a in actions):
+                raise NotImplementedError("None actions need a discrete action space on MobileRobot envs (the reference's "
+                                          "MobileRobotGymEnv.step has no `None` branch for continuous actions: action[0] on None raises)")
+            dim = self._shards[0].h.action_dim
+            dst[...] = _lib.none_rows(actions, dim).reshape(n, dim)
+            # the whole batch is checked before any shard launches (srlhip_step_async's own check, made per shard, could leave the
+            # shards at different steps): every row finite or, on a Kuka env, all NaN
+            fin = np.isfinite(dst)
+            if not fin.all() and not (kuka and (fin.all(axis=1) | np.isnan(dst).all(axis=1)).all()):
+                raise _lib.SrlHipError("step: non-finite continuous action (a Kuka env's `None` is a row of NaNs)")
         self._actions = dst
         # launch: every shard's step is in flight on its own GPU / stream when this returns
         if self._fast is not None:
@@ -460,11 +470,14 @@ class HipVecEnv(object):
 
     def rollout(self, n_steps, actions=None):
         """Fused device-side rollout (no per-step host round trip): dict of [T][N] planes, global env-id order.  With several shards
-        every GPU runs its rollout at the same time (one host thread per shard: the foreign calls release the GIL)."""
+        every GPU runs its rollout at the same time (one host thread per shard: the foreign calls release the GIL).  `None` actions as in
+        step(): -1, or on a Kuka env with continuous actions `None` / a row of NaNs."""
         if self._enc is not None:
             raise NotImplementedError("fused rollouts with a learned SRL encoder: use srlhip.pixel_env.PixelStateVecEnv")
         if self._pending:
             self.step_wait()
+        if actions is not None and not self.cfg.is_discrete:
+            actions = _lib.none_rows(actions, self._h.action_dim, 2)
         if len(self._shards) == 1:
             return self._h.rollout(n_steps, actions=actions)
         acts = None if actions is None else np.asarray(actions)
