@@ -72,9 +72,7 @@ size_t obs_bytes_per_env(const Handle *h) {
     return sizeof(float) * obs_dim_of(h->cfg);
 }
 
-// ---- persistent stepping: host side of the protocol (internal.hpp PersistArgs) ---------------------------------------------------------
-struct PersistHost { volatile uint32_t seq, stop, parked; volatile uint32_t pad[13]; volatile uint32_t done[16]; };     // mapped, coherent; done[0..7]: persistent stepping, one per eighth of the workgroups;
-                                                                                                                          // done[8..15]: the early completion signal of single-step launches
+// ---- persistent stepping: host side of the protocol (step_signal.hpp) -------------------------------------------------------------------
 PersistHost *persist_ctl(Handle *h) { return static_cast<PersistHost *>(h->persist_host); }
 
 // Resident kernels of several handles on ONE device (the shards of HipVecEnv(device_ids=[0, 0])) must all fit at once: a workgroup that
@@ -88,14 +86,13 @@ void persist_release(Handle *h) {
     h->persist_reserved = 0;
 }
 
-// the mapped control block + the device words (relay, arrival counters, start barrier, the single-step signal's counters, timeline stamps)
-// shared by persistent stepping and by the early completion signal of single-step launches
+// the mapped control block + the device words shared by persistent stepping and by the early completion signal of single-step launches
 int ensure_signal_buffers(Handle *h) {
     if (h->persist_host) return 0;
     const size_t bytes = sizeof(PersistHost), blocks = ((size_t)h->n + 3) / 4;
     if (hipHostMalloc(&h->persist_host, bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return h->fail(SRLHIP_ENOMEM, "step: hipHostMalloc (control block) failed");
     memset(h->persist_host, 0, bytes);
-    const size_t words = 28 * kPersistWordStride + 16 * ((blocks + 7) / 8 * 8);
+    const size_t words = signal_words(blocks);
     if (hipMalloc(reinterpret_cast<void **>(&h->persist_relay), words * sizeof(uint32_t)) != hipSuccess) return h->fail(SRLHIP_ENOMEM, "step: hipMalloc (control words) failed");
     SRL_HIP_CHECK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->persist_relay), 0, words, h->stream));
     return 0;
@@ -123,16 +120,14 @@ int set_device(Handle *h, bool step_pair = false) {
 int persist_launch(Handle *h, uint32_t start_seq) {
     PersistHost *c = persist_ctl(h);
     c->stop = 0; c->parked = 0;
-    for (uint32_t g = 0; g < 8; g++) c->done[g] = start_seq;
-    SRL_HIP_CHECK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->persist_relay), (int)start_seq, 8 * kPersistWordStride, h->stream));
-    SRL_HIP_CHECK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->persist_relay + 8 * kPersistWordStride), 0, 12 * kPersistWordStride, h->stream));
+    for (uint32_t g = 0; g < 8; g++) c->done[kDoneResident + g] = start_seq;
+    SRL_HIP_CHECK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->persist_relay + kWordRelay), (int)start_seq, kWordCount - kWordRelay, h->stream));
+    SRL_HIP_CHECK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->persist_relay + kWordCount), 0, kWordStepCount - kWordCount, h->stream));
     void *dctl = nullptr, *din = nullptr, *dout = nullptr;
     SRL_HIP_CHECK(h, hipHostGetDevicePointer(&dctl, h->persist_host, 0));
     SRL_HIP_CHECK(h, hipHostGetDevicePointer(&din, h->pin_in, 0));
     SRL_HIP_CHECK(h, hipHostGetDevicePointer(&dout, h->pin_out, 0));
-    uint32_t *w = static_cast<uint32_t *>(dctl);
-    PersistArgs pa;
-    pa.seq = w; pa.stop = w + 1; pa.parked = w + 2; pa.done = w + 16; pa.relay = h->persist_relay; pa.count = h->persist_relay + 8 * kPersistWordStride; pa.ctrl = h->persist_relay + 16 * kPersistWordStride;
+    PersistArgs pa = signal_args(SignalKind::resident, dctl, h->persist_relay);
     pa.start_seq = start_seq;
     { const char *v = getenv("SRLHIP_PERSIST_STAGED"); pa.force_staged = v && atoi(v) != 0; }
     pa.spin_limit = h->persist_park_us / 2 + 1;        // one poll of workgroup 0: one 8-byte PCIe read + s_sleep 8, ~2 us
@@ -516,23 +511,21 @@ int host_step_begin(Handle *h, const void *actions, const double *host_noise, bo
     // the kernel reports the step's outputs per eighth of its grid (kuka_tree_kernels.hpp), host_step_finish polls those words instead
     // of synchronising the stream — the kernel's exit stores and the completion wake-up leave the step's latency.
     static const bool sig_enabled = [] { const char *v = getenv("SRLHIP_STEP_SIGNAL"); return !v || atoi(v) != 0; }();
-    PersistArgs sg{};
     h->signal_wait = false;
     if (sig_enabled && L.zero_copy && !host_noise && !ensure_signal_buffers(h)) {
         if (h->signal_seq >= 0xfffffff0u) {               // the arrival counters count in step with the sequence number: restart both
-            SRL_HIP_CHECK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->persist_relay + 20 * kPersistWordStride), 0, 8 * kPersistWordStride, h->stream));
+            SRL_HIP_CHECK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->persist_relay + kWordStepCount), 0, kWordStamps - kWordStepCount, h->stream));
             h->signal_seq = 0;
         }
         void *dctl = nullptr;
         SRL_HIP_CHECK(h, hipHostGetDevicePointer(&dctl, h->persist_host, 0));
-        uint32_t *w = static_cast<uint32_t *>(dctl);
-        sg.done = w + 16 + 8; sg.count = h->persist_relay + 20 * kPersistWordStride;       // (done[8..15]; counter + XCD tag per eighth)
-        sg.start_seq = h->signal_seq + 1;
-        h->step_signal = &sg; h->step_signal_armed = false;
+        h->step_signal = signal_args(SignalKind::single_step, dctl, h->persist_relay);
+        h->step_signal.start_seq = h->signal_seq + 1;
+        h->step_signal_armed = false;
     }
     rc = is_mobile(h->cfg.env_kind) ? mobile_step(h, din, d_noise, L.pixels ? nullptr : static_cast<float *>(d_obs), d_rew, d_done)
                                     : kuka_step(h, din, d_noise, L.pixels ? nullptr : d_obs, d_rew, d_done);
-    h->step_signal = nullptr;
+    h->step_signal = PersistArgs{};
     if (rc) return rc;
     if (h->step_signal_armed) { h->signal_seq += 1; h->signal_wait = true; h->step_signal_armed = false; }
     if (L.pixels && d_obs && (rc = raster_render(h, d_obs))) return rc;
@@ -557,7 +550,7 @@ int host_step_finish(Handle *h, void *obs_out, float *reward_out, uint8_t *done_
         const auto t0 = std::chrono::steady_clock::now();
         // (eighth g reports iff it holds a real workgroup: persist_eighths, set with the mode)
         for (uint32_t b = 0; b < 8; b++) {
-            while (((h->persist_eighths >> b) & 1u) && __atomic_load_n(&c->done[b], __ATOMIC_ACQUIRE) != want) {
+            while (((h->persist_eighths >> b) & 1u) && __atomic_load_n(&c->done[kDoneResident + b], __ATOMIC_ACQUIRE) != want) {
                 if ((++spins & 1023u) != 0) continue;
                 if (c->parked) {
                     int rc = persist_park(h);
@@ -587,7 +580,7 @@ int host_step_finish(Handle *h, void *obs_out, float *reward_out, uint8_t *done_
         bool split = false;                              // an eighth of the grid reported from more than one XCD (~want)
         for (uint32_t b = 0; seen && b < 8; b++)
             for (; (h->signal_eighths >> b) & 1u;) {
-                const uint32_t v = __atomic_load_n(&c->done[8 + b], __ATOMIC_ACQUIRE);
+                const uint32_t v = __atomic_load_n(&c->done[kDoneStep + b], __ATOMIC_ACQUIRE);
                 if (v == want) break;
                 if (v == ~want) { split = true; break; }
                 if ((++spins & 4095u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) { seen = false; break; }
@@ -665,10 +658,7 @@ int srlhip_set_persistent(srlhip_handle hh, int32_t on, int32_t park_us) {
     uint32_t eighths = 0;
     const bool mobile = is_mobile(h->cfg.env_kind);
     const int blocks = mobile ? mobile_persist_blocks(h, &capacity, &eighths) : kuka_persist_blocks(h, &capacity);
-    if (!mobile) {                  // eighth g = the contiguous workgroup range [g, g + 1) * ceil(blocks / 8) (kuka_tree_kernels.hpp)
-        const uint32_t per = ((uint32_t)(blocks > 0 ? blocks : 0) + 7) / 8;
-        for (uint32_t g = 0; g < 8 && g * per < (uint32_t)(blocks > 0 ? blocks : 0); g++) eighths |= 1u << g;
-    }
+    if (!mobile) eighths = contiguous_eighths(blocks);
     if (blocks <= 0 || !step_layout(h).zero_copy)
         return h->fail(SRLHIP_ENOTSUP, "set_persistent: needs a MobileRobot env, KukaButtonGymEnv, KukaMovingButtonGymEnv or Kuka2ButtonGymEnv (full model) on a device RNG mode, non-pixel "
                                        "observations, zero-copy step buffers, and a batch whose wavefronts are all resident at once (4096 envs on an MI355X)");
@@ -679,7 +669,7 @@ int srlhip_set_persistent(srlhip_handle hh, int32_t on, int32_t park_us) {
         if (hipMalloc(&h->persist_stage, L.out_total + 16) != hipSuccess) return h->fail(SRLHIP_ENOMEM, "set_persistent: hipMalloc failed");
     }
     if (!h->persist_reserved) {
-        const int grid = mobile ? blocks : (blocks + 7) / 8 * 8;
+        const int grid = mobile ? blocks : contiguous_grid(blocks);
         std::lock_guard<std::mutex> lk(g_persist_mu);
         if (g_persist_reserved[h->cfg.device_id & 63] + grid > capacity)
             return h->fail(SRLHIP_ENOTSUP, "set_persistent: the resident kernels of the handles already in persistent mode on this device leave no room for this one");
@@ -699,7 +689,7 @@ int srlhip_debug_persist_prof(srlhip_handle hh, uint64_t *out, int32_t blocks) {
     Handle *h = reinterpret_cast<Handle *>(hh);
     int rc = set_device(h);
     if (rc) return rc;
-    SRL_HIP_CHECK(h, hipMemcpy(out, h->persist_relay + 28 * kPersistWordStride, 64 * (size_t)blocks, hipMemcpyDeviceToHost));
+    SRL_HIP_CHECK(h, hipMemcpy(out, h->persist_relay + kWordStamps, kStampsPerBlock * sizeof(uint64_t) * (size_t)blocks, hipMemcpyDeviceToHost));
     return 0;
 }
 #endif

@@ -9,6 +9,7 @@
 
 #include "../../include/srlhip.h"
 #include "rng.hpp"
+#include "step_signal.hpp"
 
 namespace srl {
 
@@ -45,7 +46,6 @@ struct MobileParams {
 };
 
 struct Handle;
-struct PersistArgs;
 
 // mobile.hip
 int mobile_alloc(Handle *h);
@@ -58,7 +58,7 @@ int mobile_rollout(Handle *h, int T, const void *d_actions, float *d_obs, float 
 int mobile_field(Handle *h, int field, void **dptr, size_t *elem, int *count);
 int mobile_reset_rand_count(const srlhip_config &c);
 int mobile_persist_blocks(Handle *h, int *capacity, uint32_t *eighths);      // persistent stepping (mobile.hip)
-int mobile_persist_start(Handle *h, const void *d_actions, float *d_obs, float *d_rew, uint8_t *d_done, const struct PersistArgs &pa);
+int mobile_persist_start(Handle *h, const void *d_actions, float *d_obs, float *d_rew, uint8_t *d_done, const PersistArgs &pa);
 
 // kuka.hip
 int kuka_alloc(Handle *h);
@@ -78,7 +78,7 @@ int kuka_set_tree_model(Handle *h, const double *table510);
 void kuka_default_tree_model(double *table510);
 int kuka_group_probe(const double *q7_host, double *out_host, int out_doubles);
 int kuka_persist_blocks(Handle *h, int *capacity);   // persistent stepping: real workgroups of the resident kernel (0: this handle has no persistent form); capacity: how many the device holds at once
-int kuka_persist_start(Handle *h, const void *d_actions, float *d_obs, float *d_rew, uint8_t *d_done, const struct PersistArgs &pa);
+int kuka_persist_start(Handle *h, const void *d_actions, float *d_obs, float *d_rew, uint8_t *d_done, const PersistArgs &pa);
 
 // raster.hip
 int raster_render(Handle *h, void *d_img);
@@ -90,27 +90,6 @@ struct RasterGripJoint { double parent, xyz[3], Rj[9], axis[3]; };
 struct RasterKukaView { const double *sq, *cq, *bq, *bx, *by, *bz, *b2q, *b2x, *b2y, *objs, *rb, *gsq, *gcq; RasterGripJoint gj[5]; const float *grip; int64_t n; int32_t two, rand_objects, has_tm; };
 
 struct KukaState;   // defined in kuka.hip
-
-// Persistent stepping (srlhip_set_persistent): the per-step API without a launch per step.  ONE launch of the rollout kernel stays
-// resident — every wavefront keeps its envs' state in registers — and takes its steps from the host through mapped memory: the host
-// writes the actions, then a new sequence number; workgroup 0 polls that word over PCIe and relays it through a device-memory word
-// (one poller on the bus, not 1024); every wavefront steps, writes its outputs to the mapped planes and its own `done` word.  The kernel
-// PARKS (writes the state back and exits) when told to (any other API call on the handle) or when no step arrived for park_us.
-struct PersistArgs {
-    const uint32_t *seq, *stop;     // host-written (mapped, coherent): sequence number of the newest step; 1 = park now
-    uint32_t *parked;               // device-written: workgroup 0 decided to park (the host must synchronise and relaunch)
-    uint32_t *done;                 // device-written [8]: sequence number of the last step that eighth of the workgroups finished
-    uint32_t *relay;                // device memory [8 x stride]: workgroup 0's token for the others (a sequence number, or kPersistPark)
-    uint32_t *count;                // device memory [8 x stride]: arrivals per eighth of the workgroups, never reset while resident
-    uint32_t *ctrl;                 // device memory: [0] workgroups registered | XCD mismatches << 16, [stride] the start barrier's verdict
-    const uint32_t *stage;          // device memory: the staging copy of the step's output planes (same layout as the host's), dword view
-    uint32_t *host_out;             // the host's mapped output planes, dword view; reward / done planes start rew_dw / done_dw dwords in
-    uint32_t rew_dw, done_dw;
-    uint32_t start_seq, spin_limit;
-    uint32_t force_staged;          // SRLHIP_PERSIST_STAGED=1: the staging copy + copier even where the direct form is valid (tests run both)
-};
-constexpr int kPersistWordStride = 64;         // (uint32 words: 256 bytes between two relay / counter words)
-constexpr uint32_t kPersistPark = 0xffffffffu;
 
 struct Handle {
     srlhip_config cfg;
@@ -160,14 +139,15 @@ struct Handle {
     void *ep_host = nullptr;
     size_t pin_in_sz, pin_out_sz;
     bool step_pending = false;       // srlhip_step_async enqueued a step that srlhip_step_wait has not collected yet
-    // persistent stepping (PersistArgs): the mapped control block [seq, stop, parked, pad..., done[blocks]], the device relay word
+    // persistent stepping (step_signal.hpp): the mapped control block (PersistHost) and the device words
     bool persist_on = false, persist_running = false, persist_step = false;
     void *persist_host = nullptr;
     uint32_t *persist_relay = nullptr;
     void *persist_stage = nullptr;
     uint32_t persist_seq = 0, persist_blocks = 0, persist_park_us = 2000;
-    // early completion signal of single-step launches (host_step_begin / host_step_finish; kuka_tree_launch arms it where the kernel supports it)
-    const PersistArgs *step_signal = nullptr;
+    // early completion signal of single-step launches (host_step_begin / host_step_finish): step_signal.done is set while host_step_begin's
+    // launch is under way; a launcher whose kernel supports the signal passes it on and arms it
+    PersistArgs step_signal = {};
     bool step_signal_armed = false, signal_wait = false;
     uint32_t signal_seq = 0, signal_steps = 0, signal_fallbacks = 0;
     uint32_t signal_eighths = 0;     // which of the 8 `done` words the armed launch will write (set by the launcher)

@@ -105,16 +105,14 @@ int kuka_tree_launch(Handle *h, const KukaParams &p, int T, const void *d_action
         const bool occ = force ? force[0] == '1' : (h->n >= 65536 && !spec);
         if (occ && one_button && cartesian) return kuka_tree_occ_launch(h, p, T, d_actions, d_noise, obs, d_rew, d_done, d_act_out);
     }
-    dim3 grid(((h->n + kGroupEnvs - 1) / kGroupEnvs + 7) / 8 * 8), block(kGroupBlock);      // a multiple of 8: the rollout kernel maps blocks to envs XCD by XCD
+    dim3 grid(contiguous_grid((h->n + kGroupEnvs - 1) / kGroupEnvs)), block(kGroupBlock);      // a multiple of 8: the rollout kernel maps blocks to envs XCD by XCD
     const bool joints = !h->cfg.is_discrete && h->cfg.action_joints, two = h->cfg.env_kind == SRLHIP_ENV_KUKA_2BUTTON;
     // a single-step launch with the caller's actions on a handle whose host side armed the early completion signal (api.hip): this
     // kernel reports the step's outputs per eighth of the grid before it ends
     PersistArgs sig{};
-    if (h->step_signal && T == 1 && d_actions) {
-        sig = *h->step_signal; h->step_signal_armed = true;
-        const uint32_t blocks = (uint32_t)(h->n + kGroupEnvs - 1) / kGroupEnvs, per = (blocks + 7) / 8;      // eighth g = the contiguous workgroup range [g, g + 1) * per
-        h->signal_eighths = 0;
-        for (uint32_t g = 0; g < 8 && g * per < blocks; g++) h->signal_eighths |= 1u << g;
+    if (h->step_signal.done && T == 1 && d_actions) {
+        sig = h->step_signal; h->step_signal_armed = true;
+        h->signal_eighths = contiguous_eighths((h->n + kGroupEnvs - 1) / kGroupEnvs);
     }
     if (spec) {
 #define SRL_TREE_SPEC(MODE, G) hipLaunchKernelGGL((kuka_tree_rollout_k<MODE, false, G, 1, 0, 1>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, T, d_actions, d_noise, obs, d_rew, d_done, d_act_out, G ? sig : PersistArgs{})
@@ -133,7 +131,7 @@ int kuka_tree_launch(Handle *h, const KukaParams &p, int T, const void *d_action
     return 0;
 }
 
-// ---- persistent stepping (internal.hpp PersistArgs; srlhip_set_persistent) ---------------------------------------------------------
+// ---- persistent stepping (step_signal.hpp; srlhip_set_persistent) -------------------------------------------------------------------
 // Persistent instantiations exist for KukaButtonGymEnv, KukaMovingButtonGymEnv and Kuka2ButtonGymEnv on a device RNG mode: the
 // configuration-specialised kernel where kuka_tree_launch would pick it (reference ctor defaults, default solver details), the generic
 // one otherwise (random_target, shaped reward, continuous Cartesian or joint-space actions, the joints observation modes, other
@@ -164,7 +162,7 @@ int kuka_tree_persist_blocks(Handle *h, int *capacity) {
     if (capacity) *capacity = 0;
     const int kind = persist_kind(h);
     if (!kind) return 0;
-    const int real = (h->n + kGroupEnvs - 1) / kGroupEnvs, grid = (real + 7) / 8 * 8;
+    const int real = (h->n + kGroupEnvs - 1) / kGroupEnvs, grid = contiguous_grid(real);
     int per_cu = 0;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, h->cfg.device_id) != hipSuccess) return 0;
@@ -173,7 +171,7 @@ int kuka_tree_persist_blocks(Handle *h, int *capacity) {
     return (long long)per_cu * prop.multiProcessorCount >= grid ? real : 0;
 }
 int kuka_tree_persist_launch(Handle *h, const KukaParams &p, const void *d_actions, float *obs, float *d_rew, uint8_t *d_done, const PersistArgs &pa) {
-    dim3 grid(((h->n + kGroupEnvs - 1) / kGroupEnvs + 7) / 8 * 8), block(kGroupBlock);
+    dim3 grid(contiguous_grid((h->n + kGroupEnvs - 1) / kGroupEnvs)), block(kGroupBlock);
     const double *no_noise = nullptr;
     void *no_act = nullptr;
     const bool ph = h->cfg.rng_mode == SRLHIP_RNG_PHILOX;

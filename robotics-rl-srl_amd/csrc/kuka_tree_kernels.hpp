@@ -96,17 +96,16 @@ __device__ __forceinline__ void tstore_body(const KukaState &s, int64_t n, int e
 // (solver_detail = 0) as compile-time constants — the run-time
 // configuration tests of the env logic and of the step's branches fold away (the host selects it only for a handle with exactly
 // this configuration, kuka_tree.hip: spec_config_of).
-// PERSIST = 1 (srlhip_set_persistent; GIVEN actions): the loop does not count to T — before every step the wavefront waits for the host's
-// next sequence number (PersistArgs: workgroup 0 polls the mapped word, the others its relay in device memory), reads its actions from
-// the SAME mapped row every step, writes its outputs straight to the host's mapped planes (they stay in its XCD's L2; the last wavefront
-// of its eighth of the grid — one XCD, verified behind a start barrier — writes that L2 back and reports; on any other placement the
-// outputs go through a staging copy that this wavefront copies out), publishes Monitor's record of an episode that ended right away;
-// it leaves the loop (and writes the state back like any rollout) when workgroup 0 relays the park token.  While it waits it already
-// runs the action-independent half of the next step (tree::tphysics_pre).
+// PERSIST = 1 (srlhip_set_persistent; GIVEN actions; the protocol is step_signal.hpp's): the loop does not count to T — before every step
+// the wavefront waits for the host's next sequence number, reads its actions from the SAME mapped row every step, writes its outputs
+// straight to the host's mapped planes (on a placement where that is not valid: to a staging copy that the last wavefront of its eighth
+// of the grid copies out), publishes Monitor's record of an episode that ended right away; it leaves the loop (and writes the state back
+// like any rollout) when workgroup 0 relays the park token.  While it waits it already runs the action-independent half of the next
+// step (tree::tphysics_pre).
 // (timeline build of persistent stepping, profiles/probes/persist_timeline.py: -DSRL_PERSIST_PROF; 100 MHz device-wide clock, the stamps of
 //  a workgroup's LAST step, 8 per workgroup, behind the relay / counter words)
 #if defined(SRL_PERSIST_PROF) && defined(__HIP_DEVICE_COMPILE__)
-#define SRL_PSTAMP(k) do { if (threadIdx.x == 0) reinterpret_cast<uint64_t *>(pa.relay + 28 * kPersistWordStride)[bid * 8 + (k)] = wall_clock64(); } while (0)
+#define SRL_PSTAMP(k) do { if (threadIdx.x == 0) reinterpret_cast<uint64_t *>(pa.relay + kWordStamps)[bid * kStampsPerBlock + (k)] = wall_clock64(); } while (0)
 #else
 #define SRL_PSTAMP(k) do { } while (0)
 #endif
@@ -168,11 +167,8 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
     const int bid = ((int)blockIdx.x & 7) * ((int)gridDim.x >> 3) + ((int)blockIdx.x >> 3);
     if constexpr (PERSIST) {
 #if defined(__HIP_DEVICE_COMPILE__)
-        // Every workgroup (the padding ones too) registers with the XCD it runs on: the direct output path below is valid only if the
-        // eighth of the grid that shares an arrival counter (blockIdx % 8) shares an L2, i.e. IS one XCD.  One word: count | mismatches << 16.
-        uint32_t xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        if (threadIdx.x == 0) __hip_atomic_fetch_add(pa.ctrl, 1u + (((xcc & 15u) != (blockIdx.x & 7u)) ? 0x10000u : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t xcc = xcd_id();
+        if (threadIdx.x == 0) persist_register(pa, xcc);          // every workgroup, the padding ones too
 #endif
     }
     if (bid * kGroupEnvs >= p.n) return;             // a padding block of the rounded-up grid (whole wavefront): it must not shadow env n - 1
@@ -238,13 +234,10 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
     (void)direct; (void)park_now;
     if constexpr (PERSIST) {
 #if defined(__HIP_DEVICE_COMPILE__)
-        // Start barrier (the grid is co-resident): workgroup 0 waits until every workgroup has registered and publishes the verdict —
-        // 1: every eighth of the grid sits on one XCD -> the wavefronts write their outputs STRAIGHT to the host's mapped planes (plain
-        // stores: they stay in that XCD's L2) and the eighth's last arriver writes the L2 back once; 2: not so -> the staging copy and
-        // the copier below (valid on any placement); 3: told to stop while waiting (a workgroup never started) -> everybody parks.
+        // start barrier -> 1: outputs straight to the host's mapped planes, 2: the staging copy and the copier below, 3: park
         uint32_t verdict = 0;
         if (threadIdx.x == 0) {
-            uint32_t *vw = pa.ctrl + kPersistWordStride;
+            uint32_t *vw = pa.ctrl + (kWordVerdict - kWordCtrl);
             if (blockIdx.x == 0) {
                 for (;;) {
                     const uint32_t reg = __hip_atomic_load(pa.ctrl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -295,10 +288,8 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
             uint32_t token = 0;
             if (threadIdx.x == 0) {
                 if (blockIdx.x == 0) {
-                    // the one poller on the bus: a new sequence number -> relay it; told to stop, or nothing for spin_limit polls -> park
                     uint32_t sq = my_seq, stop = 0, spins = 0;
                     for (;;) {
-                        // (seq, stop) are one aligned 8-byte word of the control block: ONE PCIe read per poll
                         const uint64_t w = __hip_atomic_load(reinterpret_cast<const uint64_t *>(pa.seq), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                         sq = (uint32_t)w; stop = (uint32_t)(w >> 32);
                         if (sq != my_seq || stop || ++spins >= pa.spin_limit) break;
@@ -306,14 +297,13 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
                     }
                     token = sq != my_seq ? sq : kPersistPark;
                     if (token == kPersistPark) __hip_atomic_store(pa.parked, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    // eight relay words, 256 bytes apart (eight memory channels): a poller reads the word of its blockIdx % 8
                     for (int x = 0; x < 8; x++) __hip_atomic_store(pa.relay + x * kPersistWordStride, token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 } else {
                     const uint32_t *rw = pa.relay + (blockIdx.x & 7) * kPersistWordStride;
                     for (;;) {
                         token = __hip_atomic_load(rw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         if (token != my_seq) break;
-                        __builtin_amdgcn_s_sleep(8);              // ~128 pollers per word, ~0.25 us between two polls of a wavefront
+                        __builtin_amdgcn_s_sleep(8);
                     }
                 }
             }
@@ -382,12 +372,9 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
         }
         if constexpr (PERSIST) {
 #if defined(__HIP_DEVICE_COMPILE__)
-            // The outputs go to a STAGING copy of the host's planes in device memory, by agent-scope (write-through) stores.  Neither
-            // way of writing them to the mapped planes directly works from 1024 wavefronts: a plain store stays in the XCD's L2 until a
-            // write-back (measured: the host saw the previous step's observations; a release fence per wavefront writes back the whole
-            // L2 — generator states, spills — 1024 times per step: 121 us), a system-scope store of 1-12 bytes crosses PCIe as its own
-            // serialised transaction (~40 ns each, 20 k per step: 835 us).  Monitor's record of an episode that ended in this step goes
-            // to its mapped plane directly (rare: system-scope stores).
+            // direct: plain stores to the mapped planes; otherwise agent-scope (write-through) stores to the staging copy (step_signal.hpp
+            // has the reasons).  Monitor's record of an episode that ended in this step goes to its mapped plane directly (rare:
+            // system-scope stores).
             SRL_PSTAMP(2);
             if (lead) {
                 float ob[17];
@@ -409,16 +396,12 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
             __builtin_amdgcn_s_waitcnt(0x0F70);         // "written through" = the store counter reaching 0
             asm volatile("" ::: "memory");
             SRL_PSTAMP(3);
-            // Every eighth of the workgroups (a contiguous env range) has an arrival counter; the LAST wavefront to arrive — staged
-            // form: copies that range of the three planes from the staging copy to the host's, dwords, coalesced, whole lines —
-            // makes them visible with ONE system-scope release (a write-back of its L2: in the direct form that IS the transfer) and
-            // then writes the eighth's `done` word: the host polls 8 words.  The counter is never reset: after k steps it stands at
-            // k * (real workgroups of the eighth).
+            // the LAST wavefront of its eighth of the workgroups (a contiguous env range) to arrive — staged form: copies that range of
+            // the three planes from the staging copy to the host's, dwords, coalesced, whole lines — reports
             const int per = (int)gridDim.x >> 3, grp8 = bid / per;
-            int real = (p.n + kGroupEnvs - 1) / kGroupEnvs - grp8 * per;
-            real = real > per ? per : real;
+            const int real = contiguous_real(grp8, (p.n + kGroupEnvs - 1) / kGroupEnvs, per);
             uint32_t last = 0;
-            if (threadIdx.x == 0) last = __hip_atomic_fetch_add(pa.count + grp8 * kPersistWordStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == (uint32_t)real * persist_k;
+            if (threadIdx.x == 0) last = signal_arrive(eighth_counter(pa.count, grp8), real, persist_k);
             SRL_PSTAMP(4);
             if (__builtin_amdgcn_readfirstlane(last)) {
                 const int lo = grp8 * per * kGroupEnvs, hi = min(lo + per * kGroupEnvs, p.n);
@@ -427,9 +410,9 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
                                            {pa.stage + pa.done_dw + lo / 4, pa.host_out + pa.done_dw + lo / 4, (hi - lo + 3) / 4}};
                 if (!direct) persist_copy(seg);
                 SRL_PSTAMP(5);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+                signal_writeback();
                 SRL_PSTAMP(6);
-                if (threadIdx.x == 0) __hip_atomic_store(pa.done + grp8, my_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                if (threadIdx.x == 0) persist_post(pa, grp8, my_seq);
             }
 #endif
         } else {
@@ -443,37 +426,24 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
             if (done_p) done_p += n;
             if constexpr (GIVEN) {
 #if defined(__HIP_DEVICE_COMPILE__)
-                // EARLY COMPLETION SIGNAL of a single-step launch on a host-pointer handle (api.hip host_step_begin arms it: pa.done set):
-                // the host does not wait for the kernel to END (exit stores of ~40 state planes, the completion signal, the stream
-                // synchronisation's wake-up) — the step's outputs are plain stores to its mapped planes in this XCD's L2, and the last
-                // wavefront of each eighth of the grid (one XCD — checked per launch, below; otherwise the host is told to wait for the
-                // kernel's end) writes that L2 back and reports, as in persistent stepping.
+                // early completion signal of a single-step launch (step_signal.hpp; armed: pa.done set): the last wavefront of each eighth reports
                 if (pa.done && t == T - 1) {
                     if (done && lead) {          // Monitor's record: the host reads it right after the step, before the exit stores below
                         __hip_atomic_store(st.last_return + e, last_ret, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                         __hip_atomic_store(st.last_length + e, last_len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     }
-                    // (which XCD is immaterial — a second kernel running beside this one shifts the round-robin — as long as the eighth's
-                    //  workgroups all sit on the SAME one: each ORs its XCD's bit into the eighth's tag before it arrives)
                     const int per = (int)gridDim.x >> 3, grp8 = bid / per;
-                    uint32_t xcc;
-                    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-                    uint32_t *tag = pa.count + grp8 * kPersistWordStride + 1;
-                    if (threadIdx.x == 0) __hip_atomic_fetch_or(tag, 1u << (xcc & 15u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const uint32_t xcc = xcd_id();
+                    uint32_t *cnt = eighth_counter(pa.count, grp8);
+                    if (threadIdx.x == 0) step_signal_tag(cnt, xcc);
                     __builtin_amdgcn_s_waitcnt(0x0F70);
                     asm volatile("" ::: "memory");
-                    int real = (p.n + kGroupEnvs - 1) / kGroupEnvs - grp8 * per;
-                    real = real > per ? per : real;
+                    const int real = contiguous_real(grp8, (p.n + kGroupEnvs - 1) / kGroupEnvs, per);
                     uint32_t last = 0;
-                    if (threadIdx.x == 0) last = __hip_atomic_fetch_add(pa.count + grp8 * kPersistWordStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == (uint32_t)real * pa.start_seq;
+                    if (threadIdx.x == 0) last = signal_arrive(cnt, real, pa.start_seq);
                     if (__builtin_amdgcn_readfirstlane(last)) {
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-                        if (threadIdx.x == 0) {
-                            const uint32_t seen = __hip_atomic_exchange(tag, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (reset for the next launch)
-                            // one XCD: the write-back above carried the whole eighth -> the sequence number; several: its complement
-                            // (the host then waits for the kernel's end, where every L2 is written back)
-                            __hip_atomic_store(pa.done + grp8, (seen & (seen - 1u)) ? ~pa.start_seq : pa.start_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        }
+                        signal_writeback();
+                        if (threadIdx.x == 0) step_signal_post(pa, cnt, grp8);
                     }
                 }
 #endif

@@ -365,32 +365,24 @@ mobile_rollout_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, in
         }
     }
     if (sig.done) {
-        // EARLY COMPLETION SIGNAL of a single-step launch on a host-pointer handle (api.hip host_step_begin; the Kuka kernels'
-        // kuka_tree_kernels.hpp has the long version): the step's outputs are in this XCD's L2; per eighth of the grid (workgroups
-        // b = g mod 8: one XCD, checked through the eighth's XCD tag) the last WAVEFRONT to arrive writes that L2 back and posts the
-        // step's sequence number — the host does not wait for the exit stores below, the kernel's end and the stream synchronisation.
+        // early completion signal of a single-step launch (step_signal.hpp): per eighth of the grid the last WAVEFRONT to arrive reports
         if (n_fin != n_fin0) {           // Monitor's record: the host reads it right after the step
             __hip_atomic_store(st.last_return + e, last_ret, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             __hip_atomic_store(st.last_length + e, last_len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
-        const int g8 = (int)blockIdx.x & 7, waves = (p.n + 63) / 64;
-        int real = 0;                    // wavefronts with a live lane in the workgroups of this eighth
-        for (int b = g8; b * (kBlock / 64) < waves; b += 8) real += min(kBlock / 64, waves - b * (kBlock / 64));
-        uint32_t xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        uint32_t *cnt = sig.count + g8 * kPersistWordStride, *tag = cnt + 1;
+        const int g8 = (int)blockIdx.x & 7;
+        const int real = strided_real(g8, (p.n + 63) / 64, kBlock / 64);      // wavefronts with a live lane in the workgroups of this eighth
+        const uint32_t xcc = xcd_id();
+        uint32_t *cnt = eighth_counter(sig.count, g8);
         const bool first = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0;       // the wavefront's first ACTIVE lane
-        if (first) __hip_atomic_fetch_or(tag, 1u << (xcc & 15u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (first) step_signal_tag(cnt, xcc);
         __builtin_amdgcn_s_waitcnt(0x0F70);
         asm volatile("" ::: "memory");
         uint32_t last = 0;
-        if (first) last = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == (uint32_t)real * sig.start_seq;
+        if (first) last = signal_arrive(cnt, real, sig.start_seq);
         if (__builtin_amdgcn_readfirstlane(last)) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-            if (first) {
-                const uint32_t seen = __hip_atomic_exchange(tag, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(sig.done + g8, (seen & (seen - 1u)) ? ~sig.start_seq : sig.start_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
+            signal_writeback();
+            if (first) step_signal_post(sig, cnt, g8);
         }
     }
     store_env(s, e, m);
@@ -401,12 +393,10 @@ mobile_rollout_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, in
     st.n_finished[e] = n_fin; st.last_reward[e] = last_reward;
 }
 
-// Persistent stepping (srlhip_set_persistent; the protocol of the Kuka kernels, kuka_tree_kernels.hpp): ONE launch stays resident with every
-// env's state in registers and takes its steps from the host through mapped memory — workgroup 0 polls the host's sequence number and
-// relays it, the others poll the relay; every lane reads its action from the mapped plane, steps, stores its outputs straight to the
-// host's mapped planes (plain stores: they stay in the XCD's L2), and the last wavefront of each eighth of the grid (workgroups b = g mod
-// 8: one XCD, verified behind a start barrier) writes that L2 back and posts the eighth's `done` word.  Where an eighth does not sit on
-// one XCD the outputs are written through instead (system-scope stores: slow, correct).  Same step code as mobile_rollout_k: bit-identical.
+// Persistent stepping (srlhip_set_persistent; the protocol is step_signal.hpp's): ONE launch stays resident with every env's state in
+// registers; every lane reads its action from the mapped plane, steps and stores its outputs straight to the host's mapped planes, the
+// last wavefront of each eighth of the grid (workgroups b = g mod 8) reports.  Where an eighth does not sit on one XCD the outputs are
+// written through instead (system-scope stores: slow, correct).  Same step code as mobile_rollout_k: bit-identical.
 template <int MODE, int KIND, int DISC>
 __global__ void __launch_bounds__(kBlock)
 mobile_persist_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, const void *actions, float *obs, float *rew, uint8_t *done_out, PersistArgs pa) {
@@ -415,9 +405,8 @@ mobile_persist_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, co
     const bool valid = e < p.n;
     const int ee = valid ? e : p.n - 1;
     p.kind = KIND; p.is_discrete = DISC;
-    uint32_t xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(pa.ctrl, 1u + (((xcc & 15u) != (blockIdx.x & 7u)) ? 0x10000u : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t xcc = xcd_id();
+    if (threadIdx.x == 0) persist_register(pa, xcc);
     typename RngSel<MODE>::type rng;
     rng_load<MODE>(rng, rs, ee, p.n, nullptr, 0, nullptr);
     MobileEnv m;
@@ -427,7 +416,7 @@ mobile_persist_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, co
     // start barrier: every workgroup has registered -> 1: direct outputs, 2: written-through outputs, 3: told to stop while waiting
     if (threadIdx.x == 0) {
         uint32_t verdict = 0;
-        uint32_t *vw = pa.ctrl + kPersistWordStride;
+        uint32_t *vw = pa.ctrl + (kWordVerdict - kWordCtrl);
         if (blockIdx.x == 0) {
             for (;;) {
                 const uint32_t reg = __hip_atomic_load(pa.ctrl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -444,9 +433,8 @@ mobile_persist_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, co
     __syncthreads();
     const uint32_t verdict = verdict_s;
     const bool direct = verdict == 1u;
-    const int g8 = (int)blockIdx.x & 7, waves = (p.n + 63) / 64;
-    int real = 0;                    // wavefronts with a live lane in the workgroups of this eighth
-    for (int b = g8; b * (kBlock / 64) < waves; b += 8) real += min(kBlock / 64, waves - b * (kBlock / 64));
+    const int g8 = (int)blockIdx.x & 7;
+    const int real = strided_real(g8, (p.n + 63) / 64, kBlock / 64);          // wavefronts with a live lane in the workgroups of this eighth
     const bool first = valid && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0;     // (lanes of a wavefront are valid from lane 0 up)
     uint32_t my_seq = pa.start_seq, k = 0;
     const int od = p.kind == SRLHIP_ENV_MOBILE_1D ? 1 : 2;
@@ -507,10 +495,10 @@ mobile_persist_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, co
         __builtin_amdgcn_s_waitcnt(0x0F70);
         asm volatile("" ::: "memory");
         uint32_t last = 0;
-        if (first) last = __hip_atomic_fetch_add(pa.count + g8 * kPersistWordStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == (uint32_t)real * k;
+        if (first) last = signal_arrive(eighth_counter(pa.count, g8), real, k);
         if (__builtin_amdgcn_readfirstlane(last)) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-            if (first) __hip_atomic_store(pa.done + g8, my_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            signal_writeback();
+            if (first) persist_post(pa, g8, my_seq);
         }
     }
     if (!valid) return;
@@ -786,9 +774,9 @@ void launch_rollout(Handle *h, const MobileParams &p, int T, const void *d_actio
                     float *d_rew, uint8_t *d_done, int advance_actr) {
     dim3 grid((h->n + kBlock - 1) / kBlock), block(kBlock);
     PersistArgs sig{};                          // the early completion signal of a single-step launch with the caller's actions (api.hip)
-    if (h->step_signal && T == 1 && d_actions && !advance_actr) {
-        sig = *h->step_signal; h->step_signal_armed = true;
-        h->signal_eighths = grid.x >= 8 ? 0xffu : (1u << grid.x) - 1u;      // eighth g = the workgroups b = g mod 8
+    if (h->step_signal.done && T == 1 && d_actions && !advance_actr) {
+        sig = h->step_signal; h->step_signal_armed = true;
+        h->signal_eighths = strided_eighths((int)grid.x);
     }
 #define SRL_GO(KIND, DISC)                                                                                              \
     hipLaunchKernelGGL((mobile_rollout_k<MODE, KIND, DISC>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T, \
@@ -954,7 +942,7 @@ template <int MODE> static const void *mobile_persist_fn(const MobileParams &p) 
 #undef SRL_FN
 }
 // workgroups of the resident kernel (0: no persistent form for this handle); capacity: how many the device holds at once;
-// eighths: which of the 8 `done` words it writes (eighth g = the workgroups b = g mod 8)
+// eighths: which of the 8 `done` words it writes
 int mobile_persist_blocks(Handle *h, int *capacity, uint32_t *eighths) {
     if (capacity) *capacity = 0;
     const srlhip_config &c = h->cfg;
@@ -967,7 +955,7 @@ int mobile_persist_blocks(Handle *h, int *capacity, uint32_t *eighths) {
     const void *fn = c.rng_mode == SRLHIP_RNG_PHILOX ? mobile_persist_fn<SRLHIP_RNG_PHILOX>(p) : mobile_persist_fn<SRLHIP_RNG_MT19937>(p);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, 0) != hipSuccess) return 0;
     if (capacity) *capacity = per_cu * prop.multiProcessorCount;
-    if (eighths) *eighths = grid >= 8 ? 0xffu : (1u << grid) - 1u;
+    if (eighths) *eighths = strided_eighths(grid);
     return (long long)per_cu * prop.multiProcessorCount >= grid ? grid : 0;
 }
 int mobile_persist_start(Handle *h, const void *d_actions, float *d_obs, float *d_rew, uint8_t *d_done, const PersistArgs &pa) {
