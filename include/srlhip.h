@@ -217,6 +217,30 @@ int srlhip_set_persistent(srlhip_handle h, int32_t on, int32_t park_us);
 int srlhip_rollout(srlhip_handle h, int32_t T, const void *actions_TN,
                    void *obs_TN, float *reward_TN, uint8_t *done_TN, void *act_out_TN);
 
+/* Fused rollout of a per-env LINEAR POLICY (the ARS policy, rl_baselines/evolution_strategies/ars.py): like srlhip_rollout, but
+ * the action of every step is chosen inside the kernel from the env's current float32 observation o (at the first step the
+ * observation of the state the call found, afterwards the one the previous step produced — after an auto-reset the new episode's
+ * first one):  score_a = sum_d (double)x_d * W[d][a] in float64, d ascending, x = o or its frozen VecNormalize image;
+ * discrete actions: a = argmax, lowest index wins a tie; continuous actions: the row (float)score_a, not clipped.
+ * Everything behind the action is srlhip_rollout's step.  act_out_TN receives the actions taken (the `None` rows of frozen envs
+ * included); any output may be NULL.
+ * Needs cfg.auto_reset, a device RNG mode, ground-truth observations and a MobileRobot env, KukaButtonGymEnv, KukaMovingButtonGymEnv
+ * or Kuka2ButtonGymEnv on the full model (any action mode the env has); everything else — the joints / joints_position observation
+ * modes, raw pixels, KukaRandButtonGymEnv, the lumped model, RNG_HOST — returns SRLHIP_ENOTSUP with a message naming it.  Host-pointer handles: EINVAL for non-finite weights / mean
+ * and for std entries that are not finite and > 0.  EINVAL while a srlhip_step_async is pending.  A resident kernel parks.
+ * Capturable under srlhip_graph_begin on device-pointer handles. */
+typedef struct srlhip_linear_policy {
+    int32_t struct_size;        /* sizeof(srlhip_linear_policy): ABI check */
+    int32_t per_env;            /* 1: weights [num_envs][obs_dim][A]; 0: one [obs_dim][A] for every env (A = num_actions or action_dim) */
+    int32_t freeze_after_done;  /* 1: from the step AFTER an env's first done in this call it takes the `None` action
+                                   (-1; Kuka continuous: a row of NaNs; MobileRobot continuous: a zero row) for the rest of the call */
+    int32_t normalize;          /* 1: x_d = (float) clamp(((double)o_d - mean[d]) / std[d], -clip_obs, clip_obs) first */
+    const double *weights, *obs_mean, *obs_std;   /* follow cfg.io_device like every other pointer; mean / std: [obs_dim] */
+    double clip_obs;
+} srlhip_linear_policy;
+int srlhip_rollout_policy(srlhip_handle h, int32_t T, const srlhip_linear_policy *pol,
+                          void *obs_TN, float *reward_TN, uint8_t *done_TN, void *act_out_TN);
+
 /* Raw state access (checkpoint / parity): field ids below; arrays are
  * [num_envs] (or [k][num_envs] for vector fields) of the field's own type.
  * Always HOST pointers. */

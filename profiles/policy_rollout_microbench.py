@@ -1,0 +1,98 @@
+"""Fused policy rollout against its two neighbours, KukaButtonGymEnv-v0 and MobileRobotGymEnv-v0, 4096 envs, one device, HIP events on
+the handle's stream.  The script sets SRLHIP_KUKA_SPEC=0 itself (the library reads it once per process) so that the Kuka GIVEN rollout
+is the generic instantiation, like the policy one:
+
+    given     srlhip_rollout with a caller-supplied [T][N] action plane (the baseline: never the policy kernel itself)
+    policy    srlhip_rollout_policy over the same T, per-env N(0, 1) weights
+    per_step  the ARS inner loop: ARSModel.batched_actions + DeviceVecEnv.step, T times
+
+Each figure is the median of --reps repetitions after --warmup; every repetition starts from reset() so all three run the same
+episodes' lengths.  Prints one JSON line per env.  Elapsed time on the stream, not device busy time: the per-step leg includes
+its launch and host gaps.
+
+    python profiles/policy_rollout_microbench.py [--envs 4096] [--steps 252] [--reps 15] [--warmup 3]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(REPO, "robotics-rl-srl_amd"), REPO):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+os.environ["SRLHIP_KUKA_SPEC"] = "0"      # before the library's first Kuka launch reads it: the GIVEN baseline must be the generic kernel
+
+import torch  # noqa: E402
+
+from rl_baselines.evolution_strategies.ars import ARSModel  # noqa: E402
+from srlhip.device_env import DeviceVecEnv  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=252)
+    ap.add_argument("--kuka-steps", type=int, default=64)
+    ap.add_argument("--reps", type=int, default=15)
+    ap.add_argument("--warmup", type=int, default=3)
+    a = ap.parse_args()
+    assert a.envs % 2 == 0
+    leg(a, "KukaButtonGymEnv-v0", a.kuka_steps, 3, 6, "philox")
+    leg(a, "MobileRobotGymEnv-v0", a.steps, 2, 4, "philox")
+    # MT19937: the GIVEN rollout is then the sequential mobile_rollout_k too (Philox takes the episode-parallel kernel) — like for like
+    leg(a, "MobileRobotGymEnv-v0", a.steps, 2, 4, "mt19937")
+
+
+def leg(a, env_id, T, D, A, rng):
+    n = a.envs
+    env = DeviceVecEnv(env_id, n, seed=0, rng_mode=rng)
+    dev, h = env.device, env.h
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(0)
+    P = n // 2
+    delta = torch.randn((P, D, A), dtype=torch.float64, device=dev, generator=gen)
+    M = torch.zeros((D, A), dtype=torch.float64, device=dev)
+    sign = torch.tensor([1.0, -1.0], dtype=torch.float64, device=dev).view(1, 2, 1, 1)
+    W = (M + sign * delta.unsqueeze(1)).reshape(n, D, A).contiguous()
+    given = torch.randint(0, A, (T, n), dtype=torch.int32, device=dev, generator=gen)
+    planes = (torch.empty((T, n, D), dtype=torch.float32, device=dev), torch.empty((T, n), dtype=torch.float32, device=dev),
+              torch.empty((T, n), dtype=torch.uint8, device=dev), torch.empty((T, n), dtype=torch.int32, device=dev))
+    ptrs = tuple(t.data_ptr() for t in planes)
+    active = torch.ones(n, dtype=torch.bool, device=dev)
+
+    def run_given():
+        h.rollout(T, given.data_ptr(), out=ptrs[:3] + (None,))
+
+    def run_policy():
+        h.rollout_policy(T, W.data_ptr(), True, False, out=ptrs)
+
+    def run_per_step():
+        obs = env.obs
+        for _ in range(T):
+            act = ARSModel.batched_actions(obs, M, delta, 1.0, active, False, True)
+            obs, _, _ = env.step(act)
+
+    out = {"env": env_id, "rng": rng, "envs": n, "steps": T, "reps": a.reps}
+    with torch.cuda.stream(env.torch_stream):
+        for name, fn in (("given", run_given), ("policy", run_policy), ("per_step", run_per_step)):
+            ms = []
+            for i in range(a.warmup + a.reps):
+                env.reset()
+                h.timing_begin()
+                fn()
+                t = h.timing_end()
+                if i >= a.warmup:
+                    ms.append(t)
+            out[name + "_ms"] = statistics.median(ms)
+            out[name + "_us_per_step"] = 1e3 * statistics.median(ms) / T
+            out[name + "_min_max_ms"] = [min(ms), max(ms)]
+    out["policy_over_given"] = out["policy_ms"] / out["given_ms"]
+    out["per_step_over_policy"] = out["per_step_ms"] / out["policy_ms"]
+    env.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -55,6 +55,15 @@ int mobile_step(Handle *h, const void *d_actions, const double *d_noise, float *
                 uint8_t *d_done);
 int mobile_rollout(Handle *h, int T, const void *d_actions, float *d_obs, float *d_rew, uint8_t *d_done,
                    void *d_act_out);
+// srlhip_rollout_policy: the linear policy as the kernels take it (device pointers; mean / std null without normalisation)
+struct PolicyArgs {
+    const double *w, *mean, *std;
+    double clip;
+    int32_t per_env, freeze, normalize;
+};
+int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
+// kuka_tree_policy.hip (full model); d_hdr: the handle's 16-double policy header
+int kuka_rollout_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
 int mobile_field(Handle *h, int field, void **dptr, size_t *elem, int *count);
 int mobile_reset_rand_count(const srlhip_config &c);
 int mobile_persist_blocks(Handle *h, int *capacity, uint32_t *eighths);      // persistent stepping (mobile.hip)
@@ -153,6 +162,7 @@ struct Handle {
     uint32_t signal_eighths = 0;     // which of the 8 `done` words the armed launch will write (set by the launcher)
     uint32_t persist_eighths = 0;    // which of the 8 `done` words the resident kernel writes
     int persist_reserved = 0;        // workgroups this handle holds in the per-device residency tally (api.hip)
+    double *policy_hdr = nullptr;    // srlhip_rollout_policy on a Kuka handle: the scalars its kernel reads (allocated with the handle: the call may be captured)
 
     int fail(int code, const std::string &msg) { err = msg; return code; }
     template <class T>

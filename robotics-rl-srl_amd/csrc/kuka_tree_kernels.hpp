@@ -152,11 +152,19 @@ __device__ __forceinline__ void persist_copy(const PersistSeg (&seg)[3]) {
 #endif
 }
 
-template <int MODE, bool JOINTS, bool GIVEN, int NB, int RB = 0, int SPEC = 0, int PERSIST = 0>
+// POLICY = 1 (srlhip_rollout_policy; kuka_tree_policy.hip): the third action source — a linear policy of the env's own current
+// ground-truth observation.  `actions` is then the float64 weight plane ([n][3][A] or [3][A]) and `noise` the 10-double header
+// kuka_policy_header_k wrote (per_env, freeze, normalize, clip, mean[3], std[3]).  Lane a < A of the env's row keeps column a of the
+// env's weights in VGPRs (LDS is full: 40 712 B per wavefront = four wavefronts per CU), mean / std sit in every lane; all of it is
+// loaded before the prologue's vmcnt wait, nothing inside the loop.  At the loop top every lane forms the observation from the row's
+// replicated env scalars and its own score; the row's scores are broadcast (DPP row_newbcast) and every lane takes the same strict
+// argmax (lowest lane wins a tie), or lane j's score becomes ca[j].
+template <int MODE, bool JOINTS, bool GIVEN, int NB, int RB = 0, int SPEC = 0, int PERSIST = 0, int POLICY = 0>
 __global__ void __launch_bounds__(kGroupBlock)
 kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int T, const void *actions, const double *noise,
                     float *obs, float *rew, uint8_t *done_out, void *act_out, PersistArgs pa) {
     static_assert(!PERSIST || GIVEN, "persistent stepping takes the caller's actions");
+    static_assert(!POLICY || (!GIVEN && !PERSIST && !SPEC && !RB), "the policy source has generic, launching instantiations only");
     using namespace grp;
     __shared__ double scratch_all[kGroupEnvs][kTS];
     const int64_t n = p.n;
@@ -213,6 +221,18 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
     Philox &act = gact.p;
     const int od = cfg.obs_mode == 1 ? 14 : cfg.obs_mode == 2 ? 17 : 3;
     const int adim = cfg.is_discrete ? 1 : cfg.action_joints ? 7 : 3;
+    double pol_w[3] = {0.0, 0.0, 0.0}, pol_mean[3] = {0.0, 0.0, 0.0}, pol_std[3] = {1.0, 1.0, 1.0}, pol_clip = 0.0;
+    bool pol_freeze = false, pol_norm = false, pol_frozen = false;
+    (void)pol_w; (void)pol_mean; (void)pol_std; (void)pol_clip; (void)pol_freeze; (void)pol_norm; (void)pol_frozen;
+    if constexpr (POLICY) {
+        const double *hdr = noise;
+        const int A = cfg.is_discrete ? 6 : adim;
+        const double *w = static_cast<const double *>(actions) + (hdr[0] != 0.0 ? (int64_t)e * 3 * A : 0);
+        const int col = L.l < A ? L.l : 0;
+#pragma unroll
+        for (int d = 0; d < 3; d++) { pol_w[d] = L.l < A ? w[d * A + col] : 0.0; pol_mean[d] = hdr[4 + d]; pol_std[d] = hdr[7 + d]; }
+        pol_freeze = hdr[1] != 0.0; pol_norm = hdr[2] != 0.0; pol_clip = hdr[3];
+    }
     // Every load of the prologue retires HERE.  Otherwise the compiler's wait for them sits at their first use INSIDE the loop, as
     // `s_waitcnt vmcnt(0)` — and gfx9 counts stores on the same counter, so from the second step on that wait drains the previous
     // step's output stores: a full store round trip (~1.5 k cycles) in every step of the rollout.
@@ -315,7 +335,36 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
             asm volatile("" ::: "memory");                       // the action reads below stay behind the token (they are system-scope loads)
 #endif
         }
-        if constexpr (GIVEN) {
+        if constexpr (POLICY) {
+            // observe() for ground truth (the host refuses the other modes), from the row's replicated scalars
+            const float ob[3] = {(float)(v.grip[0] - v.bpos[0]), (float)(v.grip[1] - v.bpos[1]), (float)(v.grip[2] - v.bpos[2])};
+            double score = 0.0;
+#pragma unroll
+            for (int d = 0; d < 3; d++) {
+                float x = ob[d];
+                if (pol_norm) x = (float)fmin(fmax(((double)ob[d] - pol_mean[d]) / pol_std[d], -pol_clip), pol_clip);
+                score = d == 0 ? (double)x * pol_w[0] : score + (double)x * pol_w[d];
+            }
+            const double sc[7] = {bcast<0>(score), bcast<1>(score), bcast<2>(score), bcast<3>(score), bcast<4>(score), bcast<5>(score), bcast<6>(score)};
+            if (cfg.is_discrete) {
+                double best = sc[0];
+#pragma unroll
+                for (int k = 1; k < 6; k++) if (sc[k] > best) { best = sc[k]; a = k; }      // strict: the lowest lane wins a tie
+            } else {
+#pragma unroll
+                for (int j = 0; j < 7; j++) ca[j] = j < adim ? (float)sc[j] : 0.f;
+            }
+            if (pol_frozen) {                          // the reference's `None`: -1, or the all-NaN row (written as bits: this file is built with -fno-honor-nans)
+                a = -1;
+#pragma unroll
+                for (int j = 0; j < 7; j++) ca[j] = 0.f;
+            }
+            if (act_p && lead) {
+                if (cfg.is_discrete) *reinterpret_cast<int32_t *>(act_p) = a;
+                else for (int j = 0; j < adim; j++) reinterpret_cast<uint32_t *>(act_p)[j] = pol_frozen ? 0x7fc00000u : __builtin_bit_cast(uint32_t, ca[j]);
+            }
+            if (act_p) act_p += act_stride;
+        } else if constexpr (GIVEN) {
             if constexpr (kLaunchSplit) {
             } else if constexpr (PERSIST) {           // the same mapped row every step: re-read, never cached in a register
                 if (cfg.is_discrete) a = __hip_atomic_load(reinterpret_cast<const int32_t *>(given_p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -362,6 +411,7 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
         const int info = cfg.info_bits ? (v.ikx & 1) << 1 : 0;      // srlhip_config.info_bits: the IK conditioning flag this step ran under (before the auto-reset clears it)
         if (done) {
             last_ret = ep_ret; last_len = ep_len; n_fin += 1; ep_ret = 0.0; ep_len = 0;
+            if constexpr (POLICY) pol_frozen = pol_frozen || pol_freeze;      // from the NEXT step on
             if (cfg.auto_reset) {
                 double *objs = valid ? s.objs + e : nullptr;
                 tree::tenv_reset<JOINTS ? 1 : 0, NB, RB>(v, g, tab, cfg, scratch, rng0, s.tstarts, s.tsettled, objs, n, &body);
@@ -467,7 +517,7 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
         if constexpr (MODE == SRLHIP_RNG_PHILOX) rs.ctr[e_out] = rng0.p.ctr;
         else if constexpr (MODE == SRLHIP_RNG_MT19937) rng0.store(rs.mt, e_out);
         else krng_store<MODE>(rng0, rs, e_out);
-        if constexpr (!GIVEN) rs.act_ctr[e_out] = act.ctr;
+        if constexpr (!GIVEN && !POLICY) rs.act_ctr[e_out] = act.ctr;
         st.ep_return[e_out] = ep_ret; st.ep_length[e_out] = ep_len;
         if (n_fin != n_fin0) { st.last_return[e_out] = last_ret; st.last_length[e_out] = last_len; }
         st.n_finished[e_out] = n_fin; st.last_reward[e_out] = last_reward;

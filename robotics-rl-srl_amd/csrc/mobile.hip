@@ -393,6 +393,84 @@ mobile_rollout_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, in
     st.n_finished[e] = n_fin; st.last_reward[e] = last_reward;
 }
 
+// srlhip_rollout_policy: the third action source.  The action of every step is a linear map of the env's own current observation
+// (the ARS policy: one env per perturbed policy), so the recurrence cannot be cut into segments: the sequential form, one lane per
+// env.  Weights, mean and std sit in registers before the loop and nothing is loaded inside it — the streamed stores are never
+// waited for (mobile_rollout_k's chunked vmcnt wait exists for its action plane only).  step_env / reset_env / observe are the
+// ones every other kernel uses: with the recorded actions as a GIVEN plane mobile_rollout_k reproduces this kernel bit for bit.
+template <int MODE, int KIND, int DISC>
+__global__ void __launch_bounds__(kBlock)
+mobile_rollout_policy_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, int T, PolicyArgs pol,
+                        float *__restrict__ obs, float *__restrict__ rew, uint8_t *__restrict__ done_out, void *__restrict__ act_out) {
+    constexpr int D = KIND == SRLHIP_ENV_MOBILE_1D ? 1 : 2;
+    constexpr int A = DISC ? (KIND == SRLHIP_ENV_MOBILE_1D ? 2 : 4) : 2;
+    int e = blockIdx.x * kBlock + threadIdx.x;
+    if (e >= p.n) return;
+    p.kind = KIND; p.is_discrete = DISC;
+    typename RngSel<MODE>::type rng;
+    rng_load<MODE>(rng, rs, e, p.n, nullptr, 0, nullptr);
+    MobileEnv m;
+    load_env(s, e, m);
+    double W[D][A], mean[D], sd[D];
+    const double *w = pol.w + (pol.per_env ? (int64_t)e * (D * A) : 0);
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+#pragma unroll
+        for (int a = 0; a < A; a++) W[d][a] = w[d * A + a];
+        mean[d] = pol.normalize ? pol.mean[d] : 0.0;
+        sd[d] = pol.normalize ? pol.std[d] : 1.0;
+    }
+    double ep_ret = st.ep_return[e], last_ret = 0.0, last_reward = 0.0;
+    int32_t ep_len = st.ep_length[e], last_len = 0, n_fin = st.n_finished[e];
+    const int32_t n_fin0 = n_fin;
+    float o[2];
+    observe(p, m, o[0], o[1]);
+    bool frozen = false;
+    for (int t = 0; t < T; t++) {
+        const int64_t row = (int64_t)t * p.n + e;
+        double score[A];
+#pragma unroll
+        for (int d = 0; d < D; d++) {
+            float x = o[d];
+            if (pol.normalize) x = (float)fmin(fmax(((double)o[d] - mean[d]) / sd[d], -pol.clip), pol.clip);
+#pragma unroll
+            for (int a = 0; a < A; a++) score[a] = d == 0 ? (double)x * W[0][a] : score[a] + (double)x * W[d][a];
+        }
+        int a = 0; float a0 = 0.f, a1 = 0.f;
+        if (DISC) {
+            double best = score[0];
+#pragma unroll
+            for (int k = 1; k < A; k++) if (score[k] > best) { best = score[k]; a = k; }       // strict: the lowest index wins a tie
+            if (frozen) a = -1;                                                              // the reference's `None`
+            if (act_out) __builtin_nontemporal_store(a, static_cast<int32_t *>(act_out) + row);
+        } else {
+            a0 = frozen ? 0.f : (float)score[0]; a1 = frozen ? 0.f : (float)score[1];         // (MobileRobot's step has no continuous `None`)
+            if (act_out) __builtin_nontemporal_store(f32x2{a0, a1}, reinterpret_cast<f32x2 *>(act_out) + row);
+        }
+        double dv = 0.1 + rng.normal(0.0, 0.0);       // DELTA_POS + N(0, NOISE_STD = 0): drawn, value 0
+        double reward; bool done;
+        step_env<KIND, DISC>(p, m, a, a0, a1, dv, reward, done);
+        ep_ret += reward; ep_len += 1; last_reward = reward;
+        if (done) {
+            last_ret = ep_ret; last_len = ep_len; n_fin += 1; ep_ret = 0.0; ep_len = 0;
+            reset_env(p, rng, m);                     // (the entry point requires auto_reset)
+            if (pol.freeze) frozen = true;            // from the NEXT step on
+        }
+        observe(p, m, o[0], o[1]);
+        if (obs) {
+            if (KIND == SRLHIP_ENV_MOBILE_1D) __builtin_nontemporal_store(o[0], obs + row);
+            else __builtin_nontemporal_store(f32x2{o[0], o[1]}, reinterpret_cast<f32x2 *>(obs + 2 * row));
+        }
+        if (rew) __builtin_nontemporal_store((float)reward, rew + row);
+        if (done_out) __builtin_nontemporal_store((uint8_t)done, done_out + row);
+    }
+    store_env(s, e, m);
+    rng_store<MODE>(rng, rs, e);
+    st.ep_return[e] = ep_ret; st.ep_length[e] = ep_len;
+    if (n_fin != n_fin0) { st.last_return[e] = last_ret; st.last_length[e] = last_len; }
+    st.n_finished[e] = n_fin; st.last_reward[e] = last_reward;
+}
+
 // Persistent stepping (srlhip_set_persistent; the protocol is step_signal.hpp's): ONE launch stays resident with every env's state in
 // registers; every lane reads its action from the mapped plane, steps and stores its outputs straight to the host's mapped planes, the
 // last wavefront of each eighth of the grid (workgroups b = g mod 8) reports.  Where an eighth does not sit on one XCD the outputs are
@@ -912,6 +990,30 @@ int mobile_rollout(Handle *h, int T, const void *d_actions, float *d_obs, float 
     if (ep_path) {}
     else if (h->cfg.rng_mode == SRLHIP_RNG_PHILOX) launch_rollout<SRLHIP_RNG_PHILOX>(h, p, T, d_actions, nullptr, d_obs, d_rew, d_done, advance);
     else launch_rollout<SRLHIP_RNG_MT19937>(h, p, T, d_actions, nullptr, d_obs, d_rew, d_done, advance);
+    SRL_HIP_CHECK(h, hipGetLastError());
+    return 0;
+}
+
+int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
+    const MobileParams p = params_of(h);
+    if ((h->cfg.rng_mode != SRLHIP_RNG_PHILOX && h->cfg.rng_mode != SRLHIP_RNG_MT19937) || !p.auto_reset)
+        return h->fail(SRLHIP_ENOTSUP, "rollout_policy: needs auto_reset and a device RNG mode (PHILOX or MT19937)");
+    h->snap_valid = false;                      // the live state moves, the episode-parallel rollout's snapshot set does not
+    dim3 grid((h->n + kBlock - 1) / kBlock), block(kBlock);
+#define SRL_GO(MODE, KIND, DISC) hipLaunchKernelGGL((mobile_rollout_policy_k<MODE, KIND, DISC>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T, pol, d_obs, d_rew, d_done, d_act_out)
+#define SRL_KIND(MODE, KIND) { if (p.is_discrete) SRL_GO(MODE, KIND, 1); else SRL_GO(MODE, KIND, 0); }
+#define SRL_MODE(MODE)                                                                        \
+    switch (p.kind) {                                                                         \
+        case SRLHIP_ENV_MOBILE: SRL_KIND(MODE, SRLHIP_ENV_MOBILE) break;                       \
+        case SRLHIP_ENV_MOBILE_1D: SRL_GO(MODE, SRLHIP_ENV_MOBILE_1D, 1); break;               \
+        case SRLHIP_ENV_MOBILE_2TARGET: SRL_GO(MODE, SRLHIP_ENV_MOBILE_2TARGET, 1); break;     \
+        default: SRL_KIND(MODE, SRLHIP_ENV_MOBILE_LINE)                                        \
+    }
+    // (MobileRobot1D / 2Target take discrete actions only: srlhip_create refuses the other combination)
+    if (h->cfg.rng_mode == SRLHIP_RNG_PHILOX) SRL_MODE(SRLHIP_RNG_PHILOX) else SRL_MODE(SRLHIP_RNG_MT19937)
+#undef SRL_MODE
+#undef SRL_KIND
+#undef SRL_GO
     SRL_HIP_CHECK(h, hipGetLastError());
     return 0;
 }

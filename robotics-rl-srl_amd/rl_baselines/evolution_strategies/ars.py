@@ -8,7 +8,12 @@ M - noise * delta_k; one batched matmul + argmax (or softmax sampling) produces 
 stepper reads in place (DeviceVecEnv, io_device = 1), on the stepper's own HIP stream — no host round trip per step.
 Finished directions receive the `None` action exactly like the reference ("do nothing, as we are done"): -1 with discrete actions,
 a row of NaNs with continuous actions on the Kuka envs (include/srlhip.h), whose step then draws no noise.  MobileRobot envs with
-continuous actions get zero rows instead: the reference's MobileRobotGymEnv.step has no continuous `None` (action[0] raises)."""
+continuous actions get zero rows instead: the reference's MobileRobotGymEnv.step has no continuous `None` (action[0] raises).
+
+--fused-rollout (off by default; the MobileRobot envs, KukaButton / KukaMovingButton / Kuka2Button; ground-truth observations,
+--deterministic or --continuous-actions, no frame stacking): one evaluation is reset + ONE srlhip_rollout_policy launch — the kernel applies each env's own M +- noise * delta to the
+observation it has just produced — and the returns come from the reward / done planes.  Softmax sampling (no --deterministic)
+stays on the per-step path above; so does CMA-ES, whose policy is a 100-unit MLP."""
 import pickle
 import time
 
@@ -56,7 +61,52 @@ class ARSModel(object):
                             help='Set the maximum update vectors amplitude (mesured in factors of step_size)')
         parser.add_argument('--deterministic', action='store_true', default=False,
                             help='do a deterministic approach for the actions on the output of the policy')
+        parser.add_argument('--fused-rollout', action='store_true', default=False,
+                            help='evaluate each population with one fused policy rollout launch (ground-truth observations; needs '
+                                 '--deterministic or --continuous-actions and --num-stack 1; not KukaRandButton). The training '
+                                 'callback then fires once per evaluation, not once per env step')
         return parser
+
+    # steps after which every env has reported done (`done = counter > max_steps`): MobileRobot 250 (mobile_robot_env.py:336-343),
+    # KukaButton 1000, KukaMovingButton / Kuka2Button 1500
+    FUSED_EPISODE_LIMIT = {_lib.ENV_MOBILE: 251, _lib.ENV_MOBILE_1D: 251, _lib.ENV_MOBILE_2TARGET: 251, _lib.ENV_MOBILE_LINE: 251,
+                           _lib.ENV_KUKA_BUTTON: 1001, _lib.ENV_KUKA_MOVING: 1501, _lib.ENV_KUKA_2BUTTON: 1501}
+
+    @staticmethod
+    def check_fused_arguments(args):
+        """--fused-rollout against the rest of the arguments; raises ValueError before any env is built."""
+        if not getattr(args, "fused_rollout", False):
+            return
+        if not (getattr(args, "deterministic", False) or getattr(args, "continuous_actions", False)):
+            raise ValueError("--fused-rollout needs --deterministic or --continuous-actions: softmax sampling of the action is "
+                             "not fused (it stays on the per-step path)")
+        if int(getattr(args, "num_stack", 1)) != 1:
+            raise ValueError("--fused-rollout needs --num-stack 1: frame stacking is not fused")
+        if getattr(args, "srl_model", "ground_truth") != "ground_truth":
+            raise ValueError("--fused-rollout needs --srl-model ground_truth")
+        if ENV_CLASSES[args.env].ENV_KIND not in ARSModel.FUSED_EPISODE_LIMIT:
+            raise ValueError("--fused-rollout: {} has no fused policy rollout".format(args.env))
+
+    @staticmethod
+    def returns_from_planes(reward, done):
+        """The reference's return rule (ars.py:178-180) on [T][N] reward / done planes: a step's reward counts only while the env
+        has not reported done, the reporting step included -> (float64 returns [N], number of rows in which some env was still live
+        when it acted)."""
+        d = (done & 1) != 0                                                            # (bit 1: srlhip_config.info_bits)
+        seen = torch.cumsum(d.to(torch.int32), 0) > 0                                  # done at this row or an earlier one
+        ret = (reward.to(torch.float64) * (~seen).to(torch.float64)).sum(0)
+        before = torch.cat([torch.zeros_like(seen[:1]), seen[:-1]], 0)               # done at an EARLIER row: frozen when it acts
+        return ret, (~before).any(dim=1).sum()
+
+    def evaluate_fused(self, env, M, delta, T):
+        """One evaluation of the population in one launch (the env was just reset): env 2k runs M + noise * delta_k, env 2k + 1
+        runs M - noise * delta_k, frozen after its first done -> (returns [P][2] float64, rows in which some direction was live)."""
+        P, (D, A) = delta.shape[0], M.shape
+        sign = torch.tensor([1.0, -1.0], dtype=M.dtype, device=M.device).view(1, 2, 1, 1)
+        W = (M.unsqueeze(0).unsqueeze(0) + self.exploration_noise * sign * delta.unsqueeze(1)).reshape(2 * P, D, A).contiguous()
+        planes = env.rollout_policy(T, W, per_env=True, freeze_after_done=True)
+        ret, live_rows = self.returns_from_planes(planes["reward"], planes["done"])
+        return ret.view(P, 2), int(live_rows)
 
     @classmethod
     def getOptParam(cls):
@@ -125,8 +175,12 @@ class ARSModel(object):
         assert args.top_population <= args.num_population, \
             "Cannot select top %d, from population of %d." % (args.top_population, args.num_population)
         assert args.num_population > 1, "The population cannot be less than 2."
+        merged = dict(vars(args), **(train_kwargs or {}))
+        self.check_fused_arguments(type(args)(**merged))          # at argument time: before any env is built
         env = self.makeEnv(args, env_kwargs)
         args.__dict__.update(train_kwargs or {})
+        fused = bool(getattr(args, "fused_rollout", False))
+        fused_T = self.FUSED_EPISODE_LIMIT.get(ENV_CLASSES[args.env].ENV_KIND, 0) + 1
         continuous = bool(getattr(args, "continuous_actions", False))
         none_rows = continuous and ENV_CLASSES[args.env].ENV_KIND >= _lib.ENV_KUKA_BUTTON      # finished directions: `None` where the reference has it
         action_space = int(np.prod(env.action_space.shape)) if continuous else env.action_space.n
@@ -146,28 +200,34 @@ class ARSModel(object):
         log_dir = getattr(args, "log_dir", None)
         with torch.cuda.stream(env.torch_stream):          # policy math and stepper kernels on ONE stream: no host syncs
             while step < num_updates:
-                r = torch.zeros((P, 2), dtype=torch.float64, device=dev)
                 delta = torch.randn((P, obs_dim, action_space), dtype=torch.float64, device=dev, generator=gen)
-                done = torch.zeros(2 * P, dtype=torch.bool, device=dev)
-                live_steps = torch.zeros((), dtype=torch.int64, device=dev)      # env steps taken while some direction was still running
                 step0 = step
                 obs = env.reset()
-                while True:
-                    actions = self.batched_actions(obs, M, delta, self.exploration_noise, ~done, continuous,
-                                                   self.deterministic, gen, none_rows)
-                    live_steps += (~done).any().to(torch.int64)
-                    obs, reward, new_done = env.step(actions)
-                    step += P
-                    done = done | (new_done != 0)
-                    # cumulate the reward for every direction that is not finished (ars.py:178-180: after the update of `done`)
-                    r += (reward.to(torch.float64) * (~done).to(torch.float64)).view(P, 2)
+                if fused:
+                    r, live_rows = self.evaluate_fused(env, M, delta, fused_T)
+                    step = step0 + P * live_rows
                     if callback is not None:
-                        callback(locals(), globals())
-                    if (step // P) % 16 == 0 and bool(done.all()):      # the only device->host read: every 16 env steps
-                        step = step0 + P * int(live_steps)                # the <= 15 idle steps since the last direction ended do not count
-                        break
-                    if (step / P + 1) % 500 == 0:
-                        print("{} steps - {:.2f} FPS".format(step, step / (time.time() - start_time)))
+                        callback(locals(), globals())              # once per evaluation on this path
+                else:
+                    r = torch.zeros((P, 2), dtype=torch.float64, device=dev)
+                    done = torch.zeros(2 * P, dtype=torch.bool, device=dev)
+                    live_steps = torch.zeros((), dtype=torch.int64, device=dev)      # env steps taken while some direction was still running
+                    while True:
+                        actions = self.batched_actions(obs, M, delta, self.exploration_noise, ~done, continuous,
+                                                       self.deterministic, gen, none_rows)
+                        live_steps += (~done).any().to(torch.int64)
+                        obs, reward, new_done = env.step(actions)
+                        step += P
+                        done = done | (new_done != 0)
+                        # cumulate the reward for every direction that is not finished (ars.py:178-180: after the update of `done`)
+                        r += (reward.to(torch.float64) * (~done).to(torch.float64)).view(P, 2)
+                        if callback is not None:
+                            callback(locals(), globals())
+                        if (step // P) % 16 == 0 and bool(done.all()):      # the only device->host read: every 16 env steps
+                            step = step0 + P * int(live_steps)                # the <= 15 idle steps since the last direction ended do not count
+                            break
+                        if (step / P + 1) % 500 == 0:
+                            print("{} steps - {:.2f} FPS".format(step, step / (time.time() - start_time)))
                 idx = torch.argsort(r.max(dim=1).values, descending=True)[:self.top_population]
                 top = r[idx]
                 delta_sum = ((top[:, 0] - top[:, 1]).view(-1, 1, 1) * delta[idx]).sum(0)

@@ -37,7 +37,7 @@ _FIELD_SHAPES = {
 EXPORTS = [
     "srlhip_abi_version", "srlhip_default_config", "srlhip_create", "srlhip_destroy", "srlhip_obs_dim",
     "srlhip_obs_bytes", "srlhip_action_dim", "srlhip_num_actions", "srlhip_seed", "srlhip_reset",
-    "srlhip_reset_rand_count", "srlhip_step", "srlhip_step_async", "srlhip_step_wait", "srlhip_step_pending", "srlhip_set_persistent", "srlhip_rollout", "srlhip_get_state", "srlhip_set_state",
+    "srlhip_reset_rand_count", "srlhip_step", "srlhip_step_async", "srlhip_step_wait", "srlhip_step_pending", "srlhip_set_persistent", "srlhip_rollout", "srlhip_rollout_policy", "srlhip_get_state", "srlhip_set_state",
     "srlhip_device_ptr", "srlhip_render", "srlhip_episode_stats", "srlhip_episode_records", "srlhip_episode_stats_device", "srlhip_sync", "srlhip_copy_async", "srlhip_stream", "srlhip_timing_begin",
     "srlhip_timing_end", "srlhip_last_error", "srlhip_selftest_group_primitives", "srlhip_kuka_kernel", "srlhip_kuka_default_model", "srlhip_set_kuka_model", "srlhip_kuka_tree_default_model", "srlhip_set_kuka_tree_model",
     "srlhip_graph_begin", "srlhip_graph_end", "srlhip_graph_launch", "srlhip_graph_destroy",
@@ -83,6 +83,15 @@ class Config(ctypes.Structure):
     ]
 
 
+class LinearPolicy(ctypes.Structure):
+    """struct srlhip_linear_policy"""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("per_env", ctypes.c_int32), ("freeze_after_done", ctypes.c_int32),
+        ("normalize", ctypes.c_int32), ("weights", ctypes.c_void_p), ("obs_mean", ctypes.c_void_p),
+        ("obs_std", ctypes.c_void_p), ("clip_obs", ctypes.c_double),
+    ]
+
+
 class SrlHipError(RuntimeError):
     pass
 
@@ -124,6 +133,7 @@ def load():
     lib.srlhip_step_wait.argtypes = [vp, vp, vp, vp]
     lib.srlhip_set_persistent.argtypes = [vp, i32, i32]
     lib.srlhip_rollout.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    lib.srlhip_rollout_policy.argtypes = [vp, i32, ctypes.POINTER(LinearPolicy), vp, vp, vp, vp]
     lib.srlhip_get_state.argtypes = [vp, i32, vp]
     lib.srlhip_set_state.argtypes = [vp, i32, vp]
     lib.srlhip_device_ptr.argtypes = [vp, i32, ctypes.POINTER(vp)]
@@ -295,6 +305,50 @@ class Handle(object):
         self._check(self._lib.srlhip_rollout(self._h, T, _ptr(a), _ptr(obs), _ptr(rew), _ptr(done), _ptr(act)),
                     "srlhip_rollout")
         return {"obs": obs, "reward": rew, "done": done, "actions": a if a is not None else act}
+
+    def policy_shape(self, per_env=True):
+        """shape of rollout_policy's weights: ([num_envs],) obs_dim, A with A = num_actions (discrete) or action_dim"""
+        a = self.num_actions if self.cfg.is_discrete else self.action_dim
+        return ((self.num_envs,) if per_env else ()) + (self.obs_dim, a)
+
+    def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0,
+                       want=("obs", "reward", "done", "actions"), out=None):
+        """srlhip_rollout_policy: T fused steps whose actions a linear policy picks inside the kernel from the env's own current
+        observation (float64 scores; argmax with discrete actions, the float32 scores themselves with continuous ones).
+        `weights`: float64 [num_envs][obs_dim][A] (per_env) or [obs_dim][A]; obs_mean / obs_std (float64 [obs_dim], both or
+        neither): the observation is normalised and clipped to +-clip_obs first, with these statistics frozen for the call.
+        Host-pointer handles take numpy arrays and return a dict of [T][N] planes (`want` selects them); device-pointer handles take
+        raw device pointers for weights / mean / std and `out` = (obs, reward, done, actions) pointers (0 / None = skip)."""
+        n = self.num_envs
+        pol = LinearPolicy()
+        pol.struct_size, pol.per_env, pol.freeze_after_done = ctypes.sizeof(LinearPolicy), int(bool(per_env)), int(bool(freeze_after_done))
+        assert (obs_mean is None) == (obs_std is None), "obs_mean and obs_std come together"
+        pol.normalize, pol.clip_obs = int(obs_mean is not None), float(clip_obs)
+        if self.cfg.io_device:
+            pol.weights, pol.obs_mean, pol.obs_std = weights, obs_mean, obs_std
+            obs, rew, done, act = out
+            self._check(self._lib.srlhip_rollout_policy(self._h, T, ctypes.byref(pol), _ptr(obs or None), _ptr(rew or None),
+                                                        _ptr(done or None), _ptr(act or None)), "srlhip_rollout_policy")
+            return out
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        assert w.shape == self.policy_shape(per_env), (w.shape, self.policy_shape(per_env))
+        keep = [w]
+        pol.weights = w.ctypes.data
+        if obs_mean is not None:
+            mean, std = np.ascontiguousarray(obs_mean, dtype=np.float64), np.ascontiguousarray(obs_std, dtype=np.float64)
+            assert mean.shape == (self.obs_dim,) and std.shape == (self.obs_dim,), (mean.shape, std.shape)
+            keep += [mean, std]
+            pol.obs_mean, pol.obs_std = mean.ctypes.data, std.ctypes.data
+        obs = self.new_obs(T) if "obs" in want else None
+        rew = np.zeros((T, n), np.float32) if "reward" in want else None
+        done = np.zeros((T, n), np.uint8) if "done" in want else None
+        act = None
+        if "actions" in want:
+            act = np.zeros((T, n), np.int32) if self.cfg.is_discrete else np.zeros((T, n, self.action_dim), np.float32)
+        self._check(self._lib.srlhip_rollout_policy(self._h, T, ctypes.byref(pol), _ptr(obs), _ptr(rew), _ptr(done), _ptr(act)),
+                    "srlhip_rollout_policy")
+        del keep
+        return {"obs": obs, "reward": rew, "done": done, "actions": act}
 
     def get_state(self, field):
         dtype, k = _FIELD_SHAPES[field]

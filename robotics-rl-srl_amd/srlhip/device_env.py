@@ -75,6 +75,34 @@ class DeviceVecEnv(object):
             self.h.sync()
         return self.obs, self.rewards, self.dones
 
+    def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0):
+        """srlhip_rollout_policy on tensors: T fused steps whose actions the linear policy `weights` (float64 tensor
+        [N][obs_dim][A], or [obs_dim][A] with per_env=False) picks inside the kernel from each env's own current observation.
+        obs_mean / obs_std: float64 tensors [obs_dim], frozen for the call.  Enqueue-only on the env's stream (like step());
+        returns {"obs", "reward", "done", "actions"}: new [T][N]... tensors of the RAW observations, rewards, dones and the
+        actions taken.  The env's own obs / rewards / dones tensors are left as they were."""
+        n, dev = self.num_envs, self.device
+        assert weights.is_cuda and weights.dtype == torch.float64 and weights.is_contiguous(), (weights.dtype, weights.device)
+        assert tuple(weights.shape) == self.h.policy_shape(per_env), (tuple(weights.shape), self.h.policy_shape(per_env))
+        assert (obs_mean is None) == (obs_std is None), "obs_mean and obs_std come together"
+        for x in (obs_mean, obs_std):
+            assert x is None or (x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() and tuple(x.shape) == (self.h.obs_dim,))
+        ordered = self._on_env_stream()
+        if not ordered:
+            torch.cuda.current_stream(dev).synchronize()
+        with torch.cuda.stream(self.torch_stream):         # the planes are allocated (and later freed) on the stream that fills them
+            out = {"obs": torch.empty((T, n, self.h.obs_dim), dtype=torch.float32, device=dev),
+                   "reward": torch.empty((T, n), dtype=torch.float32, device=dev),
+                   "done": torch.empty((T, n), dtype=torch.uint8, device=dev),
+                   "actions": torch.empty((T, n), dtype=torch.int32, device=dev) if self.cfg.is_discrete
+                   else torch.empty((T, n, self.h.action_dim), dtype=torch.float32, device=dev)}
+        self.h.rollout_policy(T, weights.data_ptr(), per_env, freeze_after_done,
+                              None if obs_mean is None else obs_mean.data_ptr(), None if obs_std is None else obs_std.data_ptr(), clip_obs,
+                              out=tuple(out[k].data_ptr() for k in ("obs", "reward", "done", "actions")))
+        if not ordered:
+            self.h.sync()
+        return out
+
     def episode_stats(self):
         return self.h.episode_stats()
 
@@ -123,6 +151,12 @@ class DeviceVecFrameStack(DeviceVecEnvWrapper):
         obs, rew, done = self.venv.step(actions)
         return self._push(obs, done), rew, done
 
+    def rollout_policy(self, T, weights, **kw):
+        """The fused policy rollout sees single frames: only the trivial stack passes through."""
+        if self.n_stack > 1:
+            raise NotImplementedError("rollout_policy: frame stacking (n_stack > 1) is not fused; use the per-step path")
+        return self.venv.rollout_policy(T, weights, **kw)
+
 
 class RunningMeanStd(object):
     """stable_baselines.common.running_mean_std.RunningMeanStd (parallel-variance batch update) on tensors"""
@@ -135,6 +169,17 @@ class RunningMeanStd(object):
     def update(self, x):
         x = x.to(torch.float64)
         bmean, bvar, bcount = x.mean(0), x.var(0, unbiased=False), x.shape[0]
+        delta, tot = bmean - self.mean, self.count + bcount
+        m2 = self.var * self.count + bvar * bcount + delta * delta * (self.count * bcount / tot)
+        self.mean, self.var, self.count = self.mean + delta * (bcount / tot), m2 / tot, tot
+
+    def update_weighted(self, x, w):
+        """The same update for the rows of x [..., shape] whose weight w [...] is 1 (0: the row does not count), without
+        gathering them: no device-to-host read.  `count` becomes a 0-d tensor."""
+        x, w = x.to(torch.float64).reshape(-1, *self.mean.shape), w.to(torch.float64).reshape(-1, *([1] * self.mean.dim()))
+        bcount = torch.clamp(w.sum(), min=1.0)
+        bmean = (w * x).sum(0) / bcount
+        bvar = (w * (x - bmean) ** 2).sum(0) / bcount
         delta, tot = bmean - self.mean, self.count + bcount
         m2 = self.var * self.count + bvar * bcount + delta * delta * (self.count * bcount / tot)
         self.mean, self.var, self.count = self.mean + delta * (bcount / tot), m2 / tot, tot
@@ -161,7 +206,7 @@ class DeviceVecNormalize(DeviceVecEnvWrapper):
         from .vec_wrappers import _RunningMeanStd as HostRms
         for rms, name in ((self.obs_rms, "obs_rms"), (self.ret_rms, "ret_rms")):
             host = HostRms(tuple(rms.mean.shape))
-            host.mean, host.var, host.count = rms.mean.cpu().numpy(), rms.var.cpu().numpy(), float(rms.count)
+            host.mean, host.var, host.count = rms.mean.cpu().numpy(), rms.var.cpu().numpy(), float(rms.count)      # (count: float or 0-d tensor)
             with open("{}/{}.pkl".format(path, name), "wb") as f:
                 pickle.dump(host, f)
 
@@ -186,6 +231,28 @@ class DeviceVecNormalize(DeviceVecEnvWrapper):
 
     def get_original_obs(self):
         return self.old_obs
+
+    def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False):
+        """The wrapped env's fused policy rollout on NORMALISED observations: the current statistics (sqrt(var + eps) as std,
+        clip_obs) are handed to the kernel and stay frozen for the whole call.  With training = False this equals the per-step
+        path.  With training = True the statistics are then updated ONCE, from the returned raw observation planes — only rows up
+        to and including each env's first done when freeze_after_done is set (all rows otherwise): a different schedule than
+        step()'s update before every action.  Returns the raw planes; rewards are not normalised."""
+        if not self.norm_obs:
+            return self.venv.rollout_policy(T, weights, per_env=per_env, freeze_after_done=freeze_after_done)
+        mean = self.obs_rms.mean.reshape(-1).contiguous()
+        std = torch.sqrt(self.obs_rms.var + self.epsilon).reshape(-1).contiguous()
+        out = self.venv.rollout_policy(T, weights, per_env=per_env, freeze_after_done=freeze_after_done, obs_mean=mean, obs_std=std,
+                                       clip_obs=self.clip_obs)
+        if self.training:
+            obs = out["obs"]
+            if freeze_after_done:
+                done = ((out["done"] & 1) != 0).to(torch.int32)                       # (bit 1: srlhip_config.info_bits)
+                live = (torch.cumsum(done, 0) - done) == 0                            # no done BEFORE this row
+                self.obs_rms.update_weighted(obs, live)                               # (no gather: the call stays enqueue-only)
+            else:
+                self.obs_rms.update(obs.reshape(-1, obs.shape[-1]))
+        return out
 
     def reset(self):
         obs = self.venv.reset()

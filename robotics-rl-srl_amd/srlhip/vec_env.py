@@ -489,6 +489,25 @@ class HipVecEnv(object):
             parts = list(pool.map(run, self._shards))
         return {k: (None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=1)) for k in parts[0]}
 
+    def rollout_policy(self, n_steps, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0):
+        """Fused rollout under a linear policy chosen inside the kernel (_lib.Handle.rollout_policy): dict of [T][N] planes, global
+        env-id order.  Shards like rollout(): each shard gets its slice of per-env weights and runs on its own GPU at the same time."""
+        if self._enc is not None:
+            raise NotImplementedError("fused rollouts with a learned SRL encoder: use srlhip.pixel_env.PixelStateVecEnv")
+        if self._pending:
+            self.step_wait()
+        kw = dict(per_env=per_env, freeze_after_done=freeze_after_done, obs_mean=obs_mean, obs_std=obs_std, clip_obs=clip_obs)
+        if len(self._shards) == 1:
+            return self._h.rollout_policy(n_steps, weights, **kw)
+        w = np.asarray(weights, dtype=np.float64)
+
+        def run(sh):
+            return sh.h.rollout_policy(n_steps, np.ascontiguousarray(w[sh.lo:sh.hi]) if per_env else w, **kw)
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(len(self._shards)) as pool:
+            parts = list(pool.map(run, self._shards))
+        return {k: (None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=1)) for k in parts[0]}
+
     def get_images(self):
         if self._pending:
             self.step_wait()
