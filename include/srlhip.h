@@ -241,6 +241,37 @@ typedef struct srlhip_linear_policy {
 int srlhip_rollout_policy(srlhip_handle h, int32_t T, const srlhip_linear_policy *pol,
                           void *obs_TN, float *reward_TN, uint8_t *done_TN, void *act_out_TN);
 
+/* Fused rollout of a per-env ONE-HIDDEN-LAYER ReLU MLP POLICY (the CMA-ES policy, rl_baselines/evolution_strategies/cma_es.py:
+ * MLPPolicyPytorch(obs_dim, [H], A)): srlhip_rollout_policy with another score function.  params holds, per env (per_env) or once,
+ * P = H*D + H + A*H + A float32 values in nn.Module.parameters() order — fc_in.weight [H][D], fc_in.bias [H], fc_out.weight [A][H],
+ * fc_out.bias [A] (D = obs_dim, A = num_actions or action_dim) — the layout of a CMA-ES candidate vector, so a [num_envs][P]
+ * population is passed as it is.  With x the float32 observation or its frozen VecNormalize image, formed exactly as in
+ * srlhip_rollout_policy:
+ *     h_j = max(0, b1_j + sum_d W1[j][d] * x_d),   score_a = b2_a + sum_j W2[a][j] * h_j,
+ * every product and sum in float64 (the float32 parameters and x converted first; a product and the sum that takes it may be one
+ * fused multiply-add).  The ORDER of the sum over j is the kernel's: a group of 16 lanes works on one env, lane l sums its units
+ * l, l+16, ... in that order and the 16 partial sums are then reduced in a fixed pattern — so scores agree with any other summation
+ * order only to float64 rounding (|error| <= 2^-46 * (|b2_a| + sum_j |W2[a][j]| * (|b1_j| + sum_d |W1[j][d] * x_d|)) for H <= 128),
+ * but the order is FIXED: two calls on equal state and parameters give equal bits.
+ * Action selection (strict argmax, lowest index first / the row (float)score_a), freeze_after_done, auto-reset, NULL output planes,
+ * chunked calls, graph capture and the parked resident kernel are srlhip_rollout_policy's, and so is the set of refusals
+ * (SRLHIP_ENOTSUP naming the cause: joints / joints_position / raw_pixels observations, KukaRandButtonGymEnv, the lumped model,
+ * RNG_HOST, no auto_reset), plus Kuka2ButtonGymEnv with joint-space continuous actions (the env takes discrete actions in the
+ * reference; its kernels have six score rows, not seven).  EINVAL: hidden outside 1..128, reserved != 0, a wrong struct_size, a pending srlhip_step_async and, on
+ * host-pointer handles, non-finite params / mean or std entries that are not finite and > 0. */
+typedef struct srlhip_mlp_policy {
+    int32_t struct_size;        /* sizeof(srlhip_mlp_policy): ABI check */
+    int32_t per_env;            /* 1: params [num_envs][P]; 0: one [P] for every env */
+    int32_t freeze_after_done, normalize;   /* as in srlhip_linear_policy */
+    int32_t hidden;             /* H, 1..128 (the reference uses 100) */
+    int32_t reserved;           /* 0 */
+    const float *params;        /* follows cfg.io_device like every other pointer */
+    const double *obs_mean, *obs_std;       /* [obs_dim] */
+    double clip_obs;
+} srlhip_mlp_policy;
+int srlhip_rollout_mlp_policy(srlhip_handle h, int32_t T, const srlhip_mlp_policy *pol,
+                              void *obs_TN, float *reward_TN, uint8_t *done_TN, void *act_out_TN);
+
 /* Raw state access (checkpoint / parity): field ids below; arrays are
  * [num_envs] (or [k][num_envs] for vector fields) of the field's own type.
  * Always HOST pointers. */

@@ -10,7 +10,15 @@ Each figure is the median of --reps repetitions after --warmup; every repetition
 episodes' lengths.  Prints one JSON line per env.  Elapsed time on the stream, not device busy time: the per-step leg includes
 its launch and host gaps.
 
-    python profiles/policy_rollout_microbench.py [--envs 4096] [--steps 252] [--reps 15] [--warmup 3]"""
+    python profiles/policy_rollout_microbench.py [--envs 4096] [--steps 252] [--reps 15] [--warmup 3]
+
+--mlp times the MLP policy (srlhip_rollout_mlp_policy, H = 100, per-env N(0, 0.5) float32 parameters) instead, at --envs and at 20
+envs (the reference's default CMA-ES population):
+
+    mlp       srlhip_rollout_mlp_policy over T steps
+    given     srlhip_rollout with the action plane the MLP rollout recorded
+    per_step  the CMA-ES inner loop (cma_es.py, unchanged by the fused path): BatchedMLP.forward in float64 + argmax + where +
+              DeviceVecEnv.step, T times"""
 import argparse
 import json
 import os
@@ -37,8 +45,15 @@ def main():
     ap.add_argument("--kuka-steps", type=int, default=64)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--mlp", action="store_true")
     a = ap.parse_args()
     assert a.envs % 2 == 0
+    if a.mlp:
+        for n in (a.envs, 20):
+            mlp_leg(a, "KukaButtonGymEnv-v0", a.kuka_steps, 3, 6, "philox", n)
+            mlp_leg(a, "MobileRobotGymEnv-v0", a.steps, 2, 4, "philox", n)
+            mlp_leg(a, "MobileRobotGymEnv-v0", a.steps, 2, 4, "mt19937", n)
+        return
     leg(a, "KukaButtonGymEnv-v0", a.kuka_steps, 3, 6, "philox")
     leg(a, "MobileRobotGymEnv-v0", a.steps, 2, 4, "philox")
     # MT19937: the GIVEN rollout is then the sequential mobile_rollout_k too (Philox takes the episode-parallel kernel) — like for like
@@ -90,6 +105,58 @@ def leg(a, env_id, T, D, A, rng):
             out[name + "_min_max_ms"] = [min(ms), max(ms)]
     out["policy_over_given"] = out["policy_ms"] / out["given_ms"]
     out["per_step_over_policy"] = out["per_step_ms"] / out["policy_ms"]
+    env.close()
+    print(json.dumps(out))
+
+
+def mlp_leg(a, env_id, T, D, A, rng, n, H=100):
+    from rl_baselines.evolution_strategies.cma_es import BatchedMLP
+    env = DeviceVecEnv(env_id, n, seed=0, rng_mode=rng)
+    dev, h = env.device, env.h
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(0)
+    policy = BatchedMLP(D, A, H)
+    pop = 0.5 * torch.randn((n, policy.n_params), dtype=torch.float64, device=dev, generator=gen)
+    W = pop.to(torch.float32).contiguous()
+    planes = (torch.empty((T, n, D), dtype=torch.float32, device=dev), torch.empty((T, n), dtype=torch.float32, device=dev),
+              torch.empty((T, n), dtype=torch.uint8, device=dev), torch.empty((T, n), dtype=torch.int32, device=dev))
+    ptrs = tuple(t.data_ptr() for t in planes)
+    done = torch.zeros(n, dtype=torch.bool, device=dev)
+
+    def run_mlp():
+        h.rollout_mlp_policy(T, W.data_ptr(), H, True, False, out=ptrs)
+
+    with torch.cuda.stream(env.torch_stream):
+        env.reset()
+        run_mlp()
+        given = planes[3].clone()                       # the recorded action plane
+
+    def run_given():
+        h.rollout(T, given.data_ptr(), out=ptrs[:3] + (None,))
+
+    def run_per_step():
+        obs = env.obs
+        for _ in range(T):
+            act = torch.argmax(policy.forward(pop, obs), dim=1)
+            act = torch.where(done, torch.full_like(act, -1), act).to(torch.int32).contiguous()
+            obs, _, _ = env.step(act)
+
+    out = {"env": env_id, "rng": rng, "envs": n, "steps": T, "hidden": H, "reps": a.reps}
+    with torch.cuda.stream(env.torch_stream):
+        for name, fn in (("given", run_given), ("mlp", run_mlp), ("per_step", run_per_step)):
+            ms = []
+            for i in range(a.warmup + a.reps):
+                env.reset()
+                h.timing_begin()
+                fn()
+                t = h.timing_end()
+                if i >= a.warmup:
+                    ms.append(t)
+            out[name + "_ms"] = statistics.median(ms)
+            out[name + "_us_per_step"] = 1e3 * statistics.median(ms) / T
+            out[name + "_min_max_ms"] = [min(ms), max(ms)]
+    out["mlp_over_given"] = out["mlp_ms"] / out["given_ms"]
+    out["mlp_over_per_step"] = out["mlp_ms"] / out["per_step_ms"]
     env.close()
     print(json.dumps(out))
 

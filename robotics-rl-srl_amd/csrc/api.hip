@@ -808,6 +808,70 @@ int srlhip_rollout_policy(srlhip_handle hh, int32_t T, const srlhip_linear_polic
     return 0;
 }
 
+int srlhip_rollout_mlp_policy(srlhip_handle hh, int32_t T, const srlhip_mlp_policy *pol, void *obs_TN, float *reward_TN,
+                              uint8_t *done_TN, void *act_out_TN) {
+    if (!hh) return SRLHIP_EINVAL;
+    Handle *h = reinterpret_cast<Handle *>(hh);
+    if (!pol) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: null policy");
+    if (pol->struct_size != (int32_t)sizeof(srlhip_mlp_policy)) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: srlhip_mlp_policy.struct_size mismatch (ABI)");
+    if (T <= 0) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: T must be positive");
+    if (h->step_pending) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: a srlhip_step_async is pending (call srlhip_step_wait first)");
+    if (pol->hidden < 1 || pol->hidden > 128) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: hidden must be in 1..128");
+    if (pol->reserved != 0) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: reserved must be 0");
+    if (!pol->params) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: null params");
+    if (pol->normalize && (!pol->obs_mean || !pol->obs_std)) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: normalize needs obs_mean and obs_std");
+    const srlhip_config &c = h->cfg;
+    // the same refusals as srlhip_rollout_policy, by name; the handle stays as it was
+    if (c.rng_mode == SRLHIP_RNG_HOST) return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy: RNG_HOST is not supported (needs a device RNG mode)");
+    if (!c.auto_reset) return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy: needs auto_reset");
+    if (c.obs_mode == SRLHIP_OBS_RAW_PIXELS) return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy: raw_pixels observations are not supported (ground_truth only)");
+    if (c.obs_mode == SRLHIP_OBS_JOINTS) return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy: the joints observation mode is not supported (ground_truth only)");
+    if (c.obs_mode == SRLHIP_OBS_JOINTS_POSITION) return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy: the joints_position observation mode is not supported (ground_truth only)");
+    if (c.env_kind == SRLHIP_ENV_KUKA_RAND) return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy: KukaRandButtonGymEnv is not supported");
+    if (!is_mobile(c.env_kind) && c.kuka_model != SRLHIP_KUKA_MODEL_FULL) return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy: the lumped Kuka model is not supported");
+    int rc = set_device(h);                            // (parks a resident kernel)
+    if (rc) return rc;
+    const size_t n = (size_t)h->n, tn = n * (size_t)T;
+    const size_t D = (size_t)obs_dim_of(c), A = (size_t)(c.is_discrete ? num_actions_of(c) : action_dim_of(c)), H = (size_t)pol->hidden;
+    const size_t wcount = (H * D + H + A * H + A) * (pol->per_env ? n : 1);
+    MlpPolicyArgs pa{pol->params, pol->normalize ? pol->obs_mean : nullptr, pol->normalize ? pol->obs_std : nullptr, pol->clip_obs,
+                     pol->per_env ? 1 : 0, pol->freeze_after_done ? 1 : 0, pol->normalize ? 1 : 0, pol->hidden};
+    void *d_obs = obs_TN; float *d_rew = reward_TN; uint8_t *d_done = done_TN; void *d_act_out = act_out_TN;
+    const size_t ob = obs_bytes_per_env(h) * tn, ab = action_bytes(h) * (size_t)T;
+    std::vector<double> packed;                        // host-pointer handles: [mean D][std D] doubles, then the float32 params, one staged block
+    if (!c.io_device) {
+        for (size_t i = 0; i < wcount; i++)
+            if (!std::isfinite(pol->params[i])) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: non-finite params");
+        if (pol->normalize) {
+            if (!all_finite_f64(pol->obs_mean, D)) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: non-finite obs_mean");
+            for (size_t d = 0; d < D; d++)
+                if (!(std::isfinite(pol->obs_std[d]) && pol->obs_std[d] > 0.0)) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: obs_std entries must be finite and > 0");
+        }
+        packed.assign(2 * D + (wcount + 1) / 2, 1.0);
+        if (pol->normalize) { memcpy(packed.data(), pol->obs_mean, 8 * D); memcpy(packed.data() + D, pol->obs_std, 8 * D); }
+        memcpy(packed.data() + 2 * D, pol->params, 4 * wcount);
+        if ((rc = stage_in(h, &h->st_rand, &h->st_rand_sz, packed.data(), 8 * packed.size()))) return rc;
+        const double *blk = static_cast<const double *>(h->st_rand);
+        pa.w = reinterpret_cast<const float *>(blk + 2 * D);
+        if (pol->normalize) { pa.mean = blk; pa.std = blk + D; }
+        if (act_out_TN) { if ((rc = ensure(h, &h->st_actions, &h->st_actions_sz, ab))) return rc; d_act_out = h->st_actions; }
+        if (obs_TN) { if ((rc = ensure(h, &h->st_obs, &h->st_obs_sz, ob))) return rc; d_obs = h->st_obs; }
+        if (reward_TN) { if ((rc = ensure(h, &h->st_rew, &h->st_rew_sz, 4 * tn))) return rc; d_rew = static_cast<float *>(h->st_rew); }
+        if (done_TN) { if ((rc = ensure(h, &h->st_done, &h->st_done_sz, tn))) return rc; d_done = static_cast<uint8_t *>(h->st_done); }
+    }
+    rc = is_mobile(c.env_kind) ? mobile_rollout_mlp_policy(h, T, pa, static_cast<float *>(d_obs), d_rew, d_done, d_act_out)
+                               : kuka_rollout_mlp_policy(h, T, pa, h->policy_hdr, static_cast<float *>(d_obs), d_rew, d_done, d_act_out);
+    if (rc) return rc;
+    if (!c.io_device) {
+        if (obs_TN) SRL_HIP_CHECK(h, hipMemcpyAsync(obs_TN, d_obs, ob, hipMemcpyDeviceToHost, h->stream));
+        if (reward_TN) SRL_HIP_CHECK(h, hipMemcpyAsync(reward_TN, d_rew, 4 * tn, hipMemcpyDeviceToHost, h->stream));
+        if (done_TN) SRL_HIP_CHECK(h, hipMemcpyAsync(done_TN, d_done, tn, hipMemcpyDeviceToHost, h->stream));
+        if (act_out_TN) SRL_HIP_CHECK(h, hipMemcpyAsync(act_out_TN, d_act_out, ab, hipMemcpyDeviceToHost, h->stream));
+        SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));       // (`packed` must outlive its copy)
+    }
+    return 0;
+}
+
 int srlhip_get_state(srlhip_handle hh, int32_t field, void *out) {
     if (!hh || !out) return SRLHIP_EINVAL;
     Handle *h = reinterpret_cast<Handle *>(hh);

@@ -64,6 +64,16 @@ struct PolicyArgs {
 int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
 // kuka_tree_policy.hip (full model); d_hdr: the handle's 16-double policy header
 int kuka_rollout_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
+// srlhip_rollout_mlp_policy: the one-hidden-layer MLP as the kernels take it; w: float32 [n][P] or [P], P = H D + H + A H + A
+struct MlpPolicyArgs {
+    const float *w;
+    const double *mean, *std;
+    double clip;
+    int32_t per_env, freeze, normalize, hidden;
+};
+int mobile_rollout_mlp_policy(Handle *h, int T, const MlpPolicyArgs &pol, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
+// kuka_tree_mlp.hip (full model); d_hdr: the handle's 16-double policy header
+int kuka_rollout_mlp_policy(Handle *h, int T, const MlpPolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
 int mobile_field(Handle *h, int field, void **dptr, size_t *elem, int *count);
 int mobile_reset_rand_count(const srlhip_config &c);
 int mobile_persist_blocks(Handle *h, int *capacity, uint32_t *eighths);      // persistent stepping (mobile.hip)

@@ -152,6 +152,16 @@ __device__ __forceinline__ void persist_copy(const PersistSeg (&seg)[3]) {
 #endif
 }
 
+// sum of x over the env's 16-lane row, lane 0 first: the same bits in every lane
+__device__ __forceinline__ double mlp_row_sum(double x) {
+    using namespace grp;
+    double acc = bcast<0>(x);
+    fmac_bcast<1>(acc, x, 1.0); fmac_bcast<2>(acc, x, 1.0); fmac_bcast<3>(acc, x, 1.0); fmac_bcast<4>(acc, x, 1.0); fmac_bcast<5>(acc, x, 1.0);
+    fmac_bcast<6>(acc, x, 1.0); fmac_bcast<7>(acc, x, 1.0); fmac_bcast<8>(acc, x, 1.0); fmac_bcast<9>(acc, x, 1.0); fmac_bcast<10>(acc, x, 1.0);
+    fmac_bcast<11>(acc, x, 1.0); fmac_bcast<12>(acc, x, 1.0); fmac_bcast<13>(acc, x, 1.0); fmac_bcast<14>(acc, x, 1.0); fmac_bcast<15>(acc, x, 1.0);
+    return acc;
+}
+
 // POLICY = 1 (srlhip_rollout_policy; kuka_tree_policy.hip): the third action source — a linear policy of the env's own current
 // ground-truth observation.  `actions` is then the float64 weight plane ([n][3][A] or [3][A]) and `noise` the 10-double header
 // kuka_policy_header_k wrote (per_env, freeze, normalize, clip, mean[3], std[3]).  Lane a < A of the env's row keeps column a of the
@@ -159,6 +169,16 @@ __device__ __forceinline__ void persist_copy(const PersistSeg (&seg)[3]) {
 // loaded before the prologue's vmcnt wait, nothing inside the loop.  At the loop top every lane forms the observation from the row's
 // replicated env scalars and its own score; the row's scores are broadcast (DPP row_newbcast) and every lane takes the same strict
 // argmax (lowest lane wins a tie), or lane j's score becomes ca[j].
+// POLICY = 2 (srlhip_rollout_mlp_policy; kuka_tree_mlp.hip): a one-hidden-layer ReLU MLP of the same observation.  `actions` is the
+// float32 parameter plane ([n][P] or [P], P = 3 H + H + A H + A in nn.Module.parameters() order) and `noise` the 11-double header
+// kuka_mlp_header_k wrote (the ten above, then H).  Lane l of the env's row owns the hidden units l, l + 16, ... (at most 8: H <= 128)
+// and holds their fc_in rows, biases and fc_out columns as float32 locals (units >= H: zeros), lane 0 also fc_out's bias; the
+// parameter plane is read once, before the prologue's vmcnt wait, never inside the loop.  The locals do NOT all stay in registers:
+// 86 - 95 floats next to a kernel already at 403 - 503 of 512 registers put every instantiation at the budget, and the compiler
+// spills 166 - 259 VGPRs to 408 - 720 B of private scratch per lane and reloads them inside the step loop (figures and the measured
+// cost: profiles/NOTES.md AE).  At the loop top every lane computes its hidden units and its A
+// partial scores in float64 (unit order l, l + 16, ...), the partials are summed over the row lane 0 .. 15 in order (fmac_bcast with
+// weight 1: the same bits in every lane, the same order in every call), then the argmax / continuous row of POLICY = 1.
 template <int MODE, bool JOINTS, bool GIVEN, int NB, int RB = 0, int SPEC = 0, int PERSIST = 0, int POLICY = 0>
 __global__ void __launch_bounds__(kGroupBlock)
 kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int T, const void *actions, const double *noise,
@@ -224,7 +244,32 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
     double pol_w[3] = {0.0, 0.0, 0.0}, pol_mean[3] = {0.0, 0.0, 0.0}, pol_std[3] = {1.0, 1.0, 1.0}, pol_clip = 0.0;
     bool pol_freeze = false, pol_norm = false, pol_frozen = false;
     (void)pol_w; (void)pol_mean; (void)pol_std; (void)pol_clip; (void)pol_freeze; (void)pol_norm; (void)pol_frozen;
-    if constexpr (POLICY) {
+    constexpr int kMlpU = 8, kMlpA = JOINTS ? 7 : 6;          // hidden units per lane; score rows an instantiation can need
+    float mlp_w1[kMlpU][3], mlp_b1[kMlpU], mlp_w2[kMlpA][kMlpU], mlp_b2[kMlpA];
+    const int mlp_A = cfg.is_discrete ? 6 : adim;
+    (void)mlp_w1; (void)mlp_b1; (void)mlp_w2; (void)mlp_b2; (void)mlp_A;
+    if constexpr (POLICY == 2) {
+        const double *hdr = noise;
+        const int A = cfg.is_discrete ? 6 : adim, H = (int)hdr[10];
+        const float *w = static_cast<const float *>(actions) + (hdr[0] != 0.0 ? (int64_t)e * (3 * H + H + A * H + A) : 0);
+        const float *w2 = w + 4 * H, *b2 = w2 + A * H;
+#pragma unroll
+        for (int u = 0; u < kMlpU; u++) {
+            const int j = L.l + GL * u;
+            const bool on = j < H;
+            const int jc = on ? j : 0;                        // clamped: every lane loads (inside the env's parameter block) and selects
+#pragma unroll                                                // afterwards — a load under a branch would be waited for one by one
+            for (int d = 0; d < 3; d++) { const float x = w[jc * 3 + d]; mlp_w1[u][d] = on ? x : 0.f; }
+            { const float x = w[3 * H + jc]; mlp_b1[u] = on ? x : 0.f; }
+#pragma unroll
+            for (int k = 0; k < kMlpA; k++) { const float x = w2[(k < A ? k : 0) * H + jc]; mlp_w2[k][u] = on && k < A ? x : 0.f; }
+        }
+#pragma unroll
+        for (int k = 0; k < kMlpA; k++) { const float x = b2[k < A ? k : 0]; mlp_b2[k] = L.l == 0 && k < A ? x : 0.f; }
+#pragma unroll
+        for (int d = 0; d < 3; d++) { pol_mean[d] = hdr[4 + d]; pol_std[d] = hdr[7 + d]; }
+        pol_freeze = hdr[1] != 0.0; pol_norm = hdr[2] != 0.0; pol_clip = hdr[3];
+    } else if constexpr (POLICY) {
         const double *hdr = noise;
         const int A = cfg.is_discrete ? 6 : adim;
         const double *w = static_cast<const double *>(actions) + (hdr[0] != 0.0 ? (int64_t)e * 3 * A : 0);
@@ -335,7 +380,49 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
             asm volatile("" ::: "memory");                       // the action reads below stay behind the token (they are system-scope loads)
 #endif
         }
-        if constexpr (POLICY) {
+        if constexpr (POLICY == 2) {
+            const float ob[3] = {(float)(v.grip[0] - v.bpos[0]), (float)(v.grip[1] - v.bpos[1]), (float)(v.grip[2] - v.bpos[2])};
+            double x[3];
+#pragma unroll
+            for (int d = 0; d < 3; d++) {
+                float xf = ob[d];
+                if (pol_norm) xf = (float)fmin(fmax(((double)ob[d] - pol_mean[d]) / pol_std[d], -pol_clip), pol_clip);
+                x[d] = (double)xf;
+            }
+            double part[kMlpA];
+#pragma unroll
+            for (int k = 0; k < kMlpA; k++) part[k] = (double)mlp_b2[k];
+#pragma unroll
+            for (int u = 0; u < kMlpU; u++) {
+                double hu = (double)mlp_b1[u];
+#pragma unroll
+                for (int d = 0; d < 3; d++) hu += (double)mlp_w1[u][d] * x[d];
+                hu = hu > 0.0 ? hu : 0.0;
+#pragma unroll
+                for (int k = 0; k < kMlpA; k++) part[k] += (double)mlp_w2[k][u] * hu;
+            }
+            double sc[kMlpA];
+#pragma unroll
+            for (int k = 0; k < kMlpA; k++) sc[k] = k < mlp_A ? mlp_row_sum(part[k]) : 0.0;      // (uniform over the grid: rows the action form has)
+            if (cfg.is_discrete) {
+                double best = sc[0];
+#pragma unroll
+                for (int k = 1; k < 6; k++) if (sc[k] > best) { best = sc[k]; a = k; }      // strict: the lowest index wins a tie
+            } else {
+#pragma unroll
+                for (int j = 0; j < kMlpA; j++) ca[j] = j < adim ? (float)sc[j] : 0.f;
+            }
+            if (pol_frozen) {                          // as POLICY = 1
+                a = -1;
+#pragma unroll
+                for (int j = 0; j < 7; j++) ca[j] = 0.f;
+            }
+            if (act_p && lead) {
+                if (cfg.is_discrete) *reinterpret_cast<int32_t *>(act_p) = a;
+                else for (int j = 0; j < adim; j++) reinterpret_cast<uint32_t *>(act_p)[j] = pol_frozen ? 0x7fc00000u : __builtin_bit_cast(uint32_t, ca[j]);
+            }
+            if (act_p) act_p += act_stride;
+        } else if constexpr (POLICY) {
             // observe() for ground truth (the host refuses the other modes), from the row's replicated scalars
             const float ob[3] = {(float)(v.grip[0] - v.bpos[0]), (float)(v.grip[1] - v.bpos[1]), (float)(v.grip[2] - v.bpos[2])};
             double score = 0.0;

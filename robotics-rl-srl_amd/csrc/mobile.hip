@@ -471,6 +471,140 @@ mobile_rollout_policy_k(MobileParams p, MobileState s, RngState rs, EpisodeStats
     st.n_finished[e] = n_fin; st.last_reward[e] = last_reward;
 }
 
+// srlhip_rollout_mlp_policy: the action of every step is a one-hidden-layer ReLU MLP of the env's own current observation (the CMA-ES
+// policy: one env per candidate).  P = H D + H + A H + A <= 704 float32 values per env do not fit one lane, so a GROUP of 16 lanes (a
+// DPP row) works on one env: lane l keeps the hidden units l, l + 16, ... (at most 8: H <= 128; units >= H are zeros) with their fc_in
+// rows, biases and fc_out columns in VGPRs — at most 8 (D + 1 + A) = 56 floats — and lane 0 fc_out's bias.  Nothing is loaded inside
+// the step loop (see mobile_rollout_policy_k: the streamed stores are never waited for).  The env itself lives in the group's lead
+// lane only (the MT19937 state is regenerated in place in memory: redundant copies of an env would race on it): each step the lead
+// lane's observation is broadcast over the row, every lane forms its hidden units and A partial scores in float64, the partials are
+// summed over the row by a four-stage DPP butterfly (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror: each
+// stage adds two values that both lanes of a pair hold, so every lane ends with the same bits, in an order that never changes),
+// and the lead lane takes the action and steps.  Lanes of envs >= n shadow env n - 1 without stepping or storing: every lane of a
+// running wavefront stays active for the row operations.  step_env / reset_env / observe are the shared ones.
+constexpr int kMlpLanes = 16, kMlpUnits = 8;
+
+template <int CTRL> __device__ __forceinline__ double dpp_f64(double x) {
+    const long long v = __double_as_longlong(x);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(v >> 32), CTRL, 0xf, 0xf, false);
+    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+}
+__device__ __forceinline__ double row_sum16(double x) {
+    x += dpp_f64<0xB1>(x);        // quad_perm [1,0,3,2]
+    x += dpp_f64<0x4E>(x);        // quad_perm [2,3,0,1]
+    x += dpp_f64<0x141>(x);       // row_half_mirror
+    x += dpp_f64<0x140>(x);       // row_mirror
+    return x;
+}
+__device__ __forceinline__ float row_lead_f32(float x) {      // lane 0 of the row (row_newbcast:0)
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x150, 0xf, 0xf, false));
+}
+
+template <int MODE, int KIND, int DISC>
+__global__ void __launch_bounds__(kBlock)
+mobile_rollout_mlp_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, int T, MlpPolicyArgs pol,
+                     float *__restrict__ obs, float *__restrict__ rew, uint8_t *__restrict__ done_out, void *__restrict__ act_out) {
+    constexpr int D = KIND == SRLHIP_ENV_MOBILE_1D ? 1 : 2;
+    constexpr int A = DISC ? (KIND == SRLHIP_ENV_MOBILE_1D ? 2 : 4) : 2;
+    const int tid = blockIdx.x * kBlock + threadIdx.x, l = tid & (kMlpLanes - 1);
+    if ((tid & ~63) / kMlpLanes >= p.n) return;        // a whole wavefront past the last env
+    const bool valid = tid / kMlpLanes < p.n, lead = valid && l == 0;
+    const int e = valid ? tid / kMlpLanes : p.n - 1;
+    p.kind = KIND; p.is_discrete = DISC;
+    const int H = pol.hidden;
+    float W1[kMlpUnits][D], B1[kMlpUnits], W2[A][kMlpUnits], B2[A];
+    const float *w = pol.w + (pol.per_env ? (int64_t)e * (H * D + H + A * H + A) : 0);
+#pragma unroll
+    for (int u = 0; u < kMlpUnits; u++) {
+        const int j = l + kMlpLanes * u;
+        const bool on = j < H;
+        const int jc = on ? j : 0;                     // clamped: every lane loads (inside the env's parameter block) and selects
+#pragma unroll                                         // afterwards — a load under a branch would be waited for one by one
+        for (int d = 0; d < D; d++) { const float x = w[jc * D + d]; W1[u][d] = on ? x : 0.f; }
+        { const float x = w[H * D + jc]; B1[u] = on ? x : 0.f; }
+#pragma unroll
+        for (int a = 0; a < A; a++) { const float x = w[H * D + H + a * H + jc]; W2[a][u] = on ? x : 0.f; }
+    }
+#pragma unroll
+    for (int a = 0; a < A; a++) { const float x = w[H * D + H + A * H + a]; B2[a] = l == 0 ? x : 0.f; }
+    double mean[D], sd[D];
+#pragma unroll
+    for (int d = 0; d < D; d++) { mean[d] = pol.normalize ? pol.mean[d] : 0.0; sd[d] = pol.normalize ? pol.std[d] : 1.0; }
+    typename RngSel<MODE>::type rng = {};
+    MobileEnv m = {};
+    double ep_ret = 0.0, last_ret = 0.0, last_reward = 0.0;
+    int32_t ep_len = 0, last_len = 0, n_fin = 0, n_fin0 = 0;
+    float o[2] = {0.f, 0.f};
+    if (lead) {
+        rng_load<MODE>(rng, rs, e, p.n, nullptr, 0, nullptr);
+        load_env(s, e, m);
+        ep_ret = st.ep_return[e]; ep_len = st.ep_length[e]; n_fin = n_fin0 = st.n_finished[e];
+        observe(p, m, o[0], o[1]);
+    }
+    bool frozen = false;
+    for (int t = 0; t < T; t++) {
+        double score[A];
+#pragma unroll
+        for (int a = 0; a < A; a++) score[a] = (double)B2[a];
+        double x[D];
+#pragma unroll
+        for (int d = 0; d < D; d++) {
+            const float od = row_lead_f32(o[d]);
+            float xf = od;
+            if (pol.normalize) xf = (float)fmin(fmax(((double)od - mean[d]) / sd[d], -pol.clip), pol.clip);
+            x[d] = (double)xf;
+        }
+#pragma unroll
+        for (int u = 0; u < kMlpUnits; u++) {
+            double hu = (double)B1[u];
+#pragma unroll
+            for (int d = 0; d < D; d++) hu += (double)W1[u][d] * x[d];
+            hu = hu > 0.0 ? hu : 0.0;
+#pragma unroll
+            for (int a = 0; a < A; a++) score[a] += (double)W2[a][u] * hu;
+        }
+#pragma unroll
+        for (int a = 0; a < A; a++) score[a] = row_sum16(score[a]);
+        if (lead) {
+            const int64_t row = (int64_t)t * p.n + e;
+            int a = 0; float a0 = 0.f, a1 = 0.f;
+            if (DISC) {
+                double best = score[0];
+#pragma unroll
+                for (int k = 1; k < A; k++) if (score[k] > best) { best = score[k]; a = k; }       // strict: the lowest index wins a tie
+                if (frozen) a = -1;                                                              // the reference's `None`
+                if (act_out) __builtin_nontemporal_store(a, static_cast<int32_t *>(act_out) + row);
+            } else {
+                a0 = frozen ? 0.f : (float)score[0]; a1 = frozen ? 0.f : (float)score[1];         // (MobileRobot's step has no continuous `None`)
+                if (act_out) __builtin_nontemporal_store(f32x2{a0, a1}, reinterpret_cast<f32x2 *>(act_out) + row);
+            }
+            double dv = 0.1 + rng.normal(0.0, 0.0);       // DELTA_POS + N(0, NOISE_STD = 0): drawn, value 0
+            double reward; bool done;
+            step_env<KIND, DISC>(p, m, a, a0, a1, dv, reward, done);
+            ep_ret += reward; ep_len += 1; last_reward = reward;
+            if (done) {
+                last_ret = ep_ret; last_len = ep_len; n_fin += 1; ep_ret = 0.0; ep_len = 0;
+                reset_env(p, rng, m);                     // (the entry point requires auto_reset)
+                if (pol.freeze) frozen = true;            // from the NEXT step on
+            }
+            observe(p, m, o[0], o[1]);
+            if (obs) {
+                if (KIND == SRLHIP_ENV_MOBILE_1D) __builtin_nontemporal_store(o[0], obs + row);
+                else __builtin_nontemporal_store(f32x2{o[0], o[1]}, reinterpret_cast<f32x2 *>(obs + 2 * row));
+            }
+            if (rew) __builtin_nontemporal_store((float)reward, rew + row);
+            if (done_out) __builtin_nontemporal_store((uint8_t)done, done_out + row);
+        }
+    }
+    if (!lead) return;
+    store_env(s, e, m);
+    rng_store<MODE>(rng, rs, e);
+    st.ep_return[e] = ep_ret; st.ep_length[e] = ep_len;
+    if (n_fin != n_fin0) { st.last_return[e] = last_ret; st.last_length[e] = last_len; }
+    st.n_finished[e] = n_fin; st.last_reward[e] = last_reward;
+}
+
 // Persistent stepping (srlhip_set_persistent; the protocol is step_signal.hpp's): ONE launch stays resident with every env's state in
 // registers; every lane reads its action from the mapped plane, steps and stores its outputs straight to the host's mapped planes, the
 // last wavefront of each eighth of the grid (workgroups b = g mod 8) reports.  Where an eighth does not sit on one XCD the outputs are
@@ -1010,6 +1144,29 @@ int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, float *d_obs,
         default: SRL_KIND(MODE, SRLHIP_ENV_MOBILE_LINE)                                        \
     }
     // (MobileRobot1D / 2Target take discrete actions only: srlhip_create refuses the other combination)
+    if (h->cfg.rng_mode == SRLHIP_RNG_PHILOX) SRL_MODE(SRLHIP_RNG_PHILOX) else SRL_MODE(SRLHIP_RNG_MT19937)
+#undef SRL_MODE
+#undef SRL_KIND
+#undef SRL_GO
+    SRL_HIP_CHECK(h, hipGetLastError());
+    return 0;
+}
+
+int mobile_rollout_mlp_policy(Handle *h, int T, const MlpPolicyArgs &pol, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
+    const MobileParams p = params_of(h);
+    if ((h->cfg.rng_mode != SRLHIP_RNG_PHILOX && h->cfg.rng_mode != SRLHIP_RNG_MT19937) || !p.auto_reset)
+        return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy: needs auto_reset and a device RNG mode (PHILOX or MT19937)");
+    h->snap_valid = false;                      // the live state moves, the episode-parallel rollout's snapshot set does not
+    dim3 grid(((int64_t)h->n * kMlpLanes + kBlock - 1) / kBlock), block(kBlock);      // 16 lanes per env
+#define SRL_GO(MODE, KIND, DISC) hipLaunchKernelGGL((mobile_rollout_mlp_k<MODE, KIND, DISC>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T, pol, d_obs, d_rew, d_done, d_act_out)
+#define SRL_KIND(MODE, KIND) { if (p.is_discrete) SRL_GO(MODE, KIND, 1); else SRL_GO(MODE, KIND, 0); }
+#define SRL_MODE(MODE)                                                                        \
+    switch (p.kind) {                                                                         \
+        case SRLHIP_ENV_MOBILE: SRL_KIND(MODE, SRLHIP_ENV_MOBILE) break;                       \
+        case SRLHIP_ENV_MOBILE_1D: SRL_GO(MODE, SRLHIP_ENV_MOBILE_1D, 1); break;               \
+        case SRLHIP_ENV_MOBILE_2TARGET: SRL_GO(MODE, SRLHIP_ENV_MOBILE_2TARGET, 1); break;     \
+        default: SRL_KIND(MODE, SRLHIP_ENV_MOBILE_LINE)                                        \
+    }
     if (h->cfg.rng_mode == SRLHIP_RNG_PHILOX) SRL_MODE(SRLHIP_RNG_PHILOX) else SRL_MODE(SRLHIP_RNG_MT19937)
 #undef SRL_MODE
 #undef SRL_KIND

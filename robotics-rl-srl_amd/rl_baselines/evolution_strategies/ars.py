@@ -13,7 +13,7 @@ continuous actions get zero rows instead: the reference's MobileRobotGymEnv.step
 --fused-rollout (off by default; the MobileRobot envs, KukaButton / KukaMovingButton / Kuka2Button; ground-truth observations,
 --deterministic or --continuous-actions, no frame stacking): one evaluation is reset + ONE srlhip_rollout_policy launch — the kernel applies each env's own M +- noise * delta to the
 observation it has just produced — and the returns come from the reward / done planes.  Softmax sampling (no --deterministic)
-stays on the per-step path above; so does CMA-ES, whose policy is a 100-unit MLP."""
+stays on the per-step path above.  (CMA-ES, whose policy is a 100-unit MLP, has its own fused form: cma_es.py.)"""
 import pickle
 import time
 

@@ -12,7 +12,12 @@ the int32 action tensor is read by the stepper in place, and the only host read 
 The `cma` package is not available in this environment; the strategy itself — (mu/mu_w, lambda)-CMA-ES with cumulative
 step-size adaptation and rank-one + rank-mu covariance updates, Hansen's tutorial parameter settings, i.e. what
 `cma.CMAEvolutionStrategy(x0, sigma0, {'popsize': n})` runs — is restated in `CMAES` below as torch tensor code on the same
-device.  Learned-from-pixels policies (the reference's CNNPolicyPytorch) are not part of the device loop."""
+device.  Learned-from-pixels policies (the reference's CNNPolicyPytorch) are not part of the device loop.
+
+--fused-rollout (off by default; the envs ARS fuses; ground-truth observations, --deterministic or --continuous-actions, no frame
+stacking): one generation is reset + ONE srlhip_rollout_mlp_policy launch — the population, cast to float32 as the reference's torch
+parameters are, is the kernel's parameter plane as it is, member k's MLP picks env k's actions inside the kernel — and the returns
+come from the reward / done planes.  Softmax sampling (no --deterministic) stays on the per-step path."""
 import math
 import pickle
 import time
@@ -23,6 +28,7 @@ import torch
 from srlhip import _lib
 from srlhip.device_env import DeviceVecEnv, DeviceVecFrameStack, DeviceVecNormalize
 from srlhip.envs import ENV_CLASSES
+from rl_baselines.evolution_strategies.ars import ARSModel
 
 
 class CMAES(object):
@@ -139,7 +145,45 @@ class CMAESModel(object):
         parser.add_argument('--cuda', action='store_true', default=False, help='use gpu for the neural network')
         parser.add_argument('--deterministic', action='store_true', default=False,
                             help='do a deterministic approach for the actions on the output of the policy')
+        parser.add_argument('--fused-rollout', action='store_true', default=False,
+                            help='evaluate each generation with one fused MLP-policy rollout launch (ground-truth observations; needs '
+                                 '--deterministic or --continuous-actions and --num-stack 1; not KukaRandButton). The training '
+                                 'callback then fires once per generation, not once per env step')
         return parser
+
+    HIDDEN = 100                        # MLPPolicyPytorch(obs_dim, [100], n_actions)
+
+    @staticmethod
+    def check_fused_arguments(args):
+        """--fused-rollout against the rest of the arguments; raises ValueError before any env is built."""
+        if not getattr(args, "fused_rollout", False):
+            return
+        if not (getattr(args, "deterministic", False) or getattr(args, "continuous_actions", False)):
+            raise ValueError("--fused-rollout needs --deterministic with discrete actions (or --continuous-actions): softmax sampling "
+                             "of the action is not fused (it stays on the per-step path)")
+        if int(getattr(args, "num_stack", 1)) != 1:
+            raise ValueError("--fused-rollout needs --num-stack 1: frame stacking is not fused")
+        if getattr(args, "srl_model", "ground_truth") != "ground_truth":
+            raise ValueError("--fused-rollout needs --srl-model ground_truth")
+        if ENV_CLASSES[args.env].ENV_KIND not in ARSModel.FUSED_EPISODE_LIMIT:
+            raise ValueError("--fused-rollout: {} has no fused policy rollout".format(args.env))
+
+    @staticmethod
+    def returns_from_planes(reward, done):
+        """The reference's accounting (cma_es.py:127-133) on [T][N] reward / done planes -> (float64 returns [N], int64 live steps
+        [N]).  `r[~done] += reward` runs AFTER `done` is updated, so the reward of a member's finishing step is not added; `step +=
+        sum(~done)` runs before the step, so a member's live steps are the rows up to and including its first done."""
+        d = (done & 1) != 0                                                            # (bit 1: srlhip_config.info_bits)
+        seen = torch.cumsum(d.to(torch.int32), 0) > 0                                  # done at this row or an earlier one
+        ret = (reward.to(torch.float64) * (~seen).to(torch.float64)).sum(0)
+        before = torch.cat([torch.zeros_like(seen[:1]), seen[:-1]], 0)               # done at an EARLIER row: frozen when it acts
+        return ret, (~before).to(torch.int64).sum(0)
+
+    def evaluate_fused(self, env, population, T):
+        """One generation in one launch (the env was just reset): member k's MLP drives env k, frozen after its first done ->
+        (r [P] float64, live_steps [P] int64)."""
+        planes = env.rollout_mlp_policy(T, population.to(torch.float32).contiguous(), self.policy.H, per_env=True, freeze_after_done=True)
+        return self.returns_from_planes(planes["reward"], planes["done"])
 
     @classmethod
     def getOptParam(cls):
@@ -185,12 +229,16 @@ class CMAESModel(object):
 
     def train(self, args, callback=None, env_kwargs=None, train_kwargs=None):
         args.num_cpu = args.num_population
+        merged = dict(vars(args), **(train_kwargs or {}))
+        self.check_fused_arguments(type(args)(**merged))          # at argument time: before any env is built
         env = self.makeEnv(args, env_kwargs=env_kwargs)
         args.__dict__.update(train_kwargs or {})
+        fused = bool(getattr(args, "fused_rollout", False))
+        fused_T = ARSModel.FUSED_EPISODE_LIMIT.get(ENV_CLASSES[args.env].ENV_KIND, 0) + 1
         continuous = bool(getattr(args, "continuous_actions", False))
         none_rows = continuous and ENV_CLASSES[args.env].ENV_KIND >= _lib.ENV_KUKA_BUTTON      # finished members: `None` (Kuka)
         action_space = int(np.prod(env.action_space.shape)) if continuous else env.action_space.n
-        self.policy = BatchedMLP(int(np.prod(env.observation_space.shape)), action_space)
+        self.policy = BatchedMLP(int(np.prod(env.observation_space.shape)), action_space, self.HIDDEN)
         self.n_population, self.mu, self.sigma = args.num_population, args.mu, args.sigma
         self.continuous_actions, self.deterministic = continuous, bool(getattr(args, "deterministic", False))
         P, dev = self.n_population, env.device
@@ -205,30 +253,36 @@ class CMAESModel(object):
         with torch.cuda.stream(env.torch_stream):          # policy math and stepper kernels on ONE stream: no host syncs
             while step < num_updates:
                 obs = env.reset()
-                r = torch.zeros(P, dtype=torch.float64, device=dev)
                 population = self.es.ask()                  # [P, n_params]
-                done = torch.zeros(P, dtype=torch.bool, device=dev)
                 live = torch.zeros((), dtype=torch.int64, device=dev)
-                k = 0
-                while True:
-                    scores = self.policy.forward(population, obs)
-                    if none_rows:
-                        actions = torch.where(done.unsqueeze(-1), torch.full_like(scores, float("nan")), scores).to(torch.float32).contiguous()
-                    elif continuous:
-                        actions = (scores * (~done).unsqueeze(-1).to(scores.dtype)).to(torch.float32).contiguous()
-                    else:
-                        a = torch.argmax(scores, dim=1) if self.deterministic else \
-                            torch.multinomial(torch.softmax(scores, dim=1), 1, generator=gen).squeeze(1)
-                        actions = torch.where(done, torch.full_like(a, -1), a).to(torch.int32).contiguous()      # None: "do nothing, as we are done"
-                    live += (~done).sum()                   # step += np.sum(~done) (cma_es.py:127)
-                    obs, reward, new_done = env.step(actions)
-                    done = done | (new_done != 0)
-                    r += reward.to(torch.float64) * (~done).to(torch.float64)      # cumulate the reward of every member that is not finished
-                    k += 1
+                if fused:                                   # one launch
+                    r, live_steps = self.evaluate_fused(env, population, fused_T)
+                    live += live_steps.sum()
                     if callback is not None:
-                        callback(locals(), globals())
-                    if k % 16 == 0 and bool(done.all()):    # the only device->host read
-                        break
+                        callback(locals(), globals())       # once per generation on this path
+                else:                                       # the per-step path
+                    r = torch.zeros(P, dtype=torch.float64, device=dev)
+                    done = torch.zeros(P, dtype=torch.bool, device=dev)
+                    k = 0
+                    while True:
+                        scores = self.policy.forward(population, obs)
+                        if none_rows:
+                            actions = torch.where(done.unsqueeze(-1), torch.full_like(scores, float("nan")), scores).to(torch.float32).contiguous()
+                        elif continuous:
+                            actions = (scores * (~done).unsqueeze(-1).to(scores.dtype)).to(torch.float32).contiguous()
+                        else:
+                            a = torch.argmax(scores, dim=1) if self.deterministic else \
+                                torch.multinomial(torch.softmax(scores, dim=1), 1, generator=gen).squeeze(1)
+                            actions = torch.where(done, torch.full_like(a, -1), a).to(torch.int32).contiguous()      # None: "do nothing, as we are done"
+                        live += (~done).sum()                   # step += np.sum(~done) (cma_es.py:127)
+                        obs, reward, new_done = env.step(actions)
+                        done = done | (new_done != 0)
+                        r += reward.to(torch.float64) * (~done).to(torch.float64)      # cumulate the reward of every member that is not finished
+                        k += 1
+                        if callback is not None:
+                            callback(locals(), globals())
+                        if k % 16 == 0 and bool(done.all()):    # the only device->host read
+                            break
                 step += int(live)
                 print("{} steps - {:.2f} FPS".format(step, step / (time.time() - start_time)))
                 self.es.tell(population, -r)

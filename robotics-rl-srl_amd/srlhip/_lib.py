@@ -37,7 +37,7 @@ _FIELD_SHAPES = {
 EXPORTS = [
     "srlhip_abi_version", "srlhip_default_config", "srlhip_create", "srlhip_destroy", "srlhip_obs_dim",
     "srlhip_obs_bytes", "srlhip_action_dim", "srlhip_num_actions", "srlhip_seed", "srlhip_reset",
-    "srlhip_reset_rand_count", "srlhip_step", "srlhip_step_async", "srlhip_step_wait", "srlhip_step_pending", "srlhip_set_persistent", "srlhip_rollout", "srlhip_rollout_policy", "srlhip_get_state", "srlhip_set_state",
+    "srlhip_reset_rand_count", "srlhip_step", "srlhip_step_async", "srlhip_step_wait", "srlhip_step_pending", "srlhip_set_persistent", "srlhip_rollout", "srlhip_rollout_policy", "srlhip_rollout_mlp_policy", "srlhip_get_state", "srlhip_set_state",
     "srlhip_device_ptr", "srlhip_render", "srlhip_episode_stats", "srlhip_episode_records", "srlhip_episode_stats_device", "srlhip_sync", "srlhip_copy_async", "srlhip_stream", "srlhip_timing_begin",
     "srlhip_timing_end", "srlhip_last_error", "srlhip_selftest_group_primitives", "srlhip_kuka_kernel", "srlhip_kuka_default_model", "srlhip_set_kuka_model", "srlhip_kuka_tree_default_model", "srlhip_set_kuka_tree_model",
     "srlhip_graph_begin", "srlhip_graph_end", "srlhip_graph_launch", "srlhip_graph_destroy",
@@ -92,6 +92,15 @@ class LinearPolicy(ctypes.Structure):
     ]
 
 
+class MlpPolicy(ctypes.Structure):
+    """struct srlhip_mlp_policy"""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("per_env", ctypes.c_int32), ("freeze_after_done", ctypes.c_int32),
+        ("normalize", ctypes.c_int32), ("hidden", ctypes.c_int32), ("reserved", ctypes.c_int32), ("params", ctypes.c_void_p),
+        ("obs_mean", ctypes.c_void_p), ("obs_std", ctypes.c_void_p), ("clip_obs", ctypes.c_double),
+    ]
+
+
 class SrlHipError(RuntimeError):
     pass
 
@@ -134,6 +143,7 @@ def load():
     lib.srlhip_set_persistent.argtypes = [vp, i32, i32]
     lib.srlhip_rollout.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     lib.srlhip_rollout_policy.argtypes = [vp, i32, ctypes.POINTER(LinearPolicy), vp, vp, vp, vp]
+    lib.srlhip_rollout_mlp_policy.argtypes = [vp, i32, ctypes.POINTER(MlpPolicy), vp, vp, vp, vp]
     lib.srlhip_get_state.argtypes = [vp, i32, vp]
     lib.srlhip_set_state.argtypes = [vp, i32, vp]
     lib.srlhip_device_ptr.argtypes = [vp, i32, ctypes.POINTER(vp)]
@@ -347,6 +357,50 @@ class Handle(object):
             act = np.zeros((T, n), np.int32) if self.cfg.is_discrete else np.zeros((T, n, self.action_dim), np.float32)
         self._check(self._lib.srlhip_rollout_policy(self._h, T, ctypes.byref(pol), _ptr(obs), _ptr(rew), _ptr(done), _ptr(act)),
                     "srlhip_rollout_policy")
+        del keep
+        return {"obs": obs, "reward": rew, "done": done, "actions": act}
+
+    def mlp_param_count(self, hidden):
+        """P of rollout_mlp_policy: H D + H + A H + A with D = obs_dim, A = num_actions (discrete) or action_dim"""
+        a = self.num_actions if self.cfg.is_discrete else self.action_dim
+        return hidden * self.obs_dim + hidden + a * hidden + a
+
+    def rollout_mlp_policy(self, T, params, hidden, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0,
+                           want=("obs", "reward", "done", "actions"), out=None):
+        """srlhip_rollout_mlp_policy: rollout_policy with a one-hidden-layer ReLU MLP as the score function.  `params`: float32
+        [num_envs][P] (per_env) or [P], P = mlp_param_count(hidden), in nn.Module.parameters() order (fc_in.weight [H][D],
+        fc_in.bias [H], fc_out.weight [A][H], fc_out.bias [A]) — a CMA-ES population as it is.  Everything else as rollout_policy
+        (device-pointer handles: raw device pointers and `out`)."""
+        n = self.num_envs
+        pol = MlpPolicy()
+        pol.struct_size, pol.per_env, pol.freeze_after_done = ctypes.sizeof(MlpPolicy), int(bool(per_env)), int(bool(freeze_after_done))
+        assert (obs_mean is None) == (obs_std is None), "obs_mean and obs_std come together"
+        pol.normalize, pol.clip_obs, pol.hidden, pol.reserved = int(obs_mean is not None), float(clip_obs), int(hidden), 0
+        if self.cfg.io_device:
+            pol.params, pol.obs_mean, pol.obs_std = params, obs_mean, obs_std
+            obs, rew, done, act = out
+            self._check(self._lib.srlhip_rollout_mlp_policy(self._h, T, ctypes.byref(pol), _ptr(obs or None), _ptr(rew or None),
+                                                            _ptr(done or None), _ptr(act or None)), "srlhip_rollout_mlp_policy")
+            return out
+        w = np.ascontiguousarray(params, dtype=np.float32)
+        if 1 <= int(hidden) <= 128:                    # (outside: the library refuses by name)
+            shape = ((n,) if per_env else ()) + (self.mlp_param_count(int(hidden)),)
+            assert w.shape == shape, (w.shape, shape)
+        keep = [w]
+        pol.params = w.ctypes.data
+        if obs_mean is not None:
+            mean, std = np.ascontiguousarray(obs_mean, dtype=np.float64), np.ascontiguousarray(obs_std, dtype=np.float64)
+            assert mean.shape == (self.obs_dim,) and std.shape == (self.obs_dim,), (mean.shape, std.shape)
+            keep += [mean, std]
+            pol.obs_mean, pol.obs_std = mean.ctypes.data, std.ctypes.data
+        obs = self.new_obs(T) if "obs" in want else None
+        rew = np.zeros((T, n), np.float32) if "reward" in want else None
+        done = np.zeros((T, n), np.uint8) if "done" in want else None
+        act = None
+        if "actions" in want:
+            act = np.zeros((T, n), np.int32) if self.cfg.is_discrete else np.zeros((T, n, self.action_dim), np.float32)
+        self._check(self._lib.srlhip_rollout_mlp_policy(self._h, T, ctypes.byref(pol), _ptr(obs), _ptr(rew), _ptr(done), _ptr(act)),
+                    "srlhip_rollout_mlp_policy")
         del keep
         return {"obs": obs, "reward": rew, "done": done, "actions": act}
 

@@ -103,6 +103,33 @@ class DeviceVecEnv(object):
             self.h.sync()
         return out
 
+    def rollout_mlp_policy(self, T, params, hidden, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0):
+        """srlhip_rollout_mlp_policy on tensors: rollout_policy with a one-hidden-layer ReLU MLP.  `params`: float32 CUDA tensor
+        [N][P] (or [P] with per_env=False), P = h.mlp_param_count(hidden), nn.Module.parameters() order.  Enqueue-only; returns
+        the same dict of new [T][N]... tensors."""
+        n, dev = self.num_envs, self.device
+        assert params.is_cuda and params.dtype == torch.float32 and params.is_contiguous(), (params.dtype, params.device)
+        shape = ((n,) if per_env else ()) + (self.h.mlp_param_count(int(hidden)),)
+        assert tuple(params.shape) == shape, (tuple(params.shape), shape)
+        assert (obs_mean is None) == (obs_std is None), "obs_mean and obs_std come together"
+        for x in (obs_mean, obs_std):
+            assert x is None or (x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() and tuple(x.shape) == (self.h.obs_dim,))
+        ordered = self._on_env_stream()
+        if not ordered:
+            torch.cuda.current_stream(dev).synchronize()
+        with torch.cuda.stream(self.torch_stream):         # the planes are allocated (and later freed) on the stream that fills them
+            out = {"obs": torch.empty((T, n, self.h.obs_dim), dtype=torch.float32, device=dev),
+                   "reward": torch.empty((T, n), dtype=torch.float32, device=dev),
+                   "done": torch.empty((T, n), dtype=torch.uint8, device=dev),
+                   "actions": torch.empty((T, n), dtype=torch.int32, device=dev) if self.cfg.is_discrete
+                   else torch.empty((T, n, self.h.action_dim), dtype=torch.float32, device=dev)}
+        self.h.rollout_mlp_policy(T, params.data_ptr(), hidden, per_env, freeze_after_done,
+                                  None if obs_mean is None else obs_mean.data_ptr(), None if obs_std is None else obs_std.data_ptr(), clip_obs,
+                                  out=tuple(out[k].data_ptr() for k in ("obs", "reward", "done", "actions")))
+        if not ordered:
+            self.h.sync()
+        return out
+
     def episode_stats(self):
         return self.h.episode_stats()
 
@@ -156,6 +183,12 @@ class DeviceVecFrameStack(DeviceVecEnvWrapper):
         if self.n_stack > 1:
             raise NotImplementedError("rollout_policy: frame stacking (n_stack > 1) is not fused; use the per-step path")
         return self.venv.rollout_policy(T, weights, **kw)
+
+    def rollout_mlp_policy(self, T, params, hidden, **kw):
+        """As rollout_policy: only the trivial stack passes through."""
+        if self.n_stack > 1:
+            raise NotImplementedError("rollout_mlp_policy: frame stacking (n_stack > 1) is not fused; use the per-step path")
+        return self.venv.rollout_mlp_policy(T, params, hidden, **kw)
 
 
 class RunningMeanStd(object):
@@ -250,6 +283,25 @@ class DeviceVecNormalize(DeviceVecEnvWrapper):
                 done = ((out["done"] & 1) != 0).to(torch.int32)                       # (bit 1: srlhip_config.info_bits)
                 live = (torch.cumsum(done, 0) - done) == 0                            # no done BEFORE this row
                 self.obs_rms.update_weighted(obs, live)                               # (no gather: the call stays enqueue-only)
+            else:
+                self.obs_rms.update(obs.reshape(-1, obs.shape[-1]))
+        return out
+
+    def rollout_mlp_policy(self, T, params, hidden, per_env=True, freeze_after_done=False):
+        """rollout_policy's schedule for the MLP policy: the current statistics are frozen for the call and, with training = True,
+        updated once afterwards from the live rows of the returned raw observation planes."""
+        if not self.norm_obs:
+            return self.venv.rollout_mlp_policy(T, params, hidden, per_env=per_env, freeze_after_done=freeze_after_done)
+        mean = self.obs_rms.mean.reshape(-1).contiguous()
+        std = torch.sqrt(self.obs_rms.var + self.epsilon).reshape(-1).contiguous()
+        out = self.venv.rollout_mlp_policy(T, params, hidden, per_env=per_env, freeze_after_done=freeze_after_done, obs_mean=mean,
+                                           obs_std=std, clip_obs=self.clip_obs)
+        if self.training:
+            obs = out["obs"]
+            if freeze_after_done:
+                done = ((out["done"] & 1) != 0).to(torch.int32)                       # (bit 1: srlhip_config.info_bits)
+                live = (torch.cumsum(done, 0) - done) == 0                            # no done BEFORE this row
+                self.obs_rms.update_weighted(obs, live)
             else:
                 self.obs_rms.update(obs.reshape(-1, obs.shape[-1]))
         return out

@@ -508,6 +508,25 @@ class HipVecEnv(object):
             parts = list(pool.map(run, self._shards))
         return {k: (None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=1)) for k in parts[0]}
 
+    def rollout_mlp_policy(self, n_steps, params, hidden, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0):
+        """rollout_policy with a one-hidden-layer ReLU MLP (_lib.Handle.rollout_mlp_policy): each shard gets its rows of per-env
+        `params` (float32 [N][P])."""
+        if self._enc is not None:
+            raise NotImplementedError("fused rollouts with a learned SRL encoder: use srlhip.pixel_env.PixelStateVecEnv")
+        if self._pending:
+            self.step_wait()
+        kw = dict(per_env=per_env, freeze_after_done=freeze_after_done, obs_mean=obs_mean, obs_std=obs_std, clip_obs=clip_obs)
+        if len(self._shards) == 1:
+            return self._h.rollout_mlp_policy(n_steps, params, hidden, **kw)
+        w = np.asarray(params, dtype=np.float32)
+
+        def run(sh):
+            return sh.h.rollout_mlp_policy(n_steps, np.ascontiguousarray(w[sh.lo:sh.hi]) if per_env else w, hidden, **kw)
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(len(self._shards)) as pool:
+            parts = list(pool.map(run, self._shards))
+        return {k: (None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=1)) for k in parts[0]}
+
     def get_images(self):
         if self._pending:
             self.step_wait()
