@@ -599,6 +599,92 @@ int host_step_finish(Handle *h, void *obs_out, float *reward_out, uint8_t *done_
     if (done_out) memcpy(done_out, po + L.out_done, h->n);
     return 0;
 }
+
+// ---- rollouts on host-pointer handles: the output planes' device twins --------------------------------------------------------------------
+struct RolloutPlanes { void *obs; float *rew; uint8_t *done; void *act; };      // [T][n] each; null: not wanted
+// every wanted plane of `d` (host pointers on entry) becomes its staging buffer
+int stage_rollout_planes(Handle *h, int32_t T, RolloutPlanes &d) {
+    const size_t tn = (size_t)h->n * (size_t)T;
+    int rc;
+    if (d.act) { if ((rc = ensure(h, &h->st_actions, &h->st_actions_sz, action_bytes(h) * (size_t)T))) return rc; d.act = h->st_actions; }
+    if (d.obs) { if ((rc = ensure(h, &h->st_obs, &h->st_obs_sz, obs_bytes_per_env(h) * tn))) return rc; d.obs = h->st_obs; }
+    if (d.rew) { if ((rc = ensure(h, &h->st_rew, &h->st_rew_sz, 4 * tn))) return rc; d.rew = static_cast<float *>(h->st_rew); }
+    if (d.done) { if ((rc = ensure(h, &h->st_done, &h->st_done_sz, tn))) return rc; d.done = static_cast<uint8_t *>(h->st_done); }
+    return 0;
+}
+// ... and back: the planes staged in `dev` (a null dev.act: none was recorded) to the host's, then the call's one synchronisation
+int fetch_rollout_planes(Handle *h, int32_t T, const RolloutPlanes &host, const RolloutPlanes &dev) {
+    const size_t tn = (size_t)h->n * (size_t)T;
+    if (host.obs) SRL_HIP_CHECK(h, hipMemcpyAsync(host.obs, dev.obs, obs_bytes_per_env(h) * tn, hipMemcpyDeviceToHost, h->stream));
+    if (host.rew) SRL_HIP_CHECK(h, hipMemcpyAsync(host.rew, dev.rew, 4 * tn, hipMemcpyDeviceToHost, h->stream));
+    if (host.done) SRL_HIP_CHECK(h, hipMemcpyAsync(host.done, dev.done, tn, hipMemcpyDeviceToHost, h->stream));
+    if (host.act && dev.act) SRL_HIP_CHECK(h, hipMemcpyAsync(host.act, dev.act, action_bytes(h) * (size_t)T, hipMemcpyDeviceToHost, h->stream));
+    SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// ---- srlhip_rollout_policy / srlhip_rollout_mlp_policy: one host path ---------------------------------------------------------------------
+// Order of the checks, as before the two entry points shared them: the entry point's null policy and struct_size, policy_call_begin
+// (T, a pending step), the entry point's other struct checks (the MLP's hidden and reserved), then everything in rollout_policy.
+// what differs between the two entry points
+struct PolicyCall {
+    const char *name;              // the entry point, as every message begins
+    const char *what;              // what the struct calls its parameter block: "weights" / "params"
+    size_t elem, count;            // bytes per parameter, parameters per policy
+    int (*kuka)(Handle *, int, const PolicyArgs &, double *, float *, float *, uint8_t *, void *);
+};
+size_t policy_outputs(const srlhip_config &c) { return (size_t)(c.is_discrete ? num_actions_of(c) : action_dim_of(c)); }
+template <class P> PolicyArgs policy_args(const P &pol, const void *w, int32_t hidden) {
+    return PolicyArgs{w, pol.normalize ? pol.obs_mean : nullptr, pol.normalize ? pol.obs_std : nullptr, pol.clip_obs,
+                      pol.per_env ? 1 : 0, pol.freeze_after_done ? 1 : 0, pol.normalize ? 1 : 0, hidden};
+}
+
+int policy_call_begin(Handle *h, const char *name, int32_t T) {
+    if (T <= 0) return h->fail(SRLHIP_EINVAL, std::string(name) + ": T must be positive");
+    if (h->step_pending) return h->fail(SRLHIP_EINVAL, std::string(name) + ": a srlhip_step_async is pending (call srlhip_step_wait first)");
+    return 0;
+}
+
+int rollout_policy(Handle *h, int32_t T, const PolicyCall &pc, PolicyArgs pa, const RolloutPlanes &host) {
+    const auto fail = [&](int code, const std::string &tail) { return h->fail(code, std::string(pc.name) + ": " + tail); };      // (built on a failing call only)
+    if (!pa.w) return fail(SRLHIP_EINVAL, std::string("null ") + pc.what);
+    if (pa.normalize && (!pa.mean || !pa.std)) return fail(SRLHIP_EINVAL, "normalize needs obs_mean and obs_std");
+    const srlhip_config &c = h->cfg;
+    // what has no policy kernel: refused by name, the handle stays as it was
+    if (c.rng_mode == SRLHIP_RNG_HOST) return fail(SRLHIP_ENOTSUP, "RNG_HOST is not supported (needs a device RNG mode)");
+    if (!c.auto_reset) return fail(SRLHIP_ENOTSUP, "needs auto_reset");
+    if (c.obs_mode == SRLHIP_OBS_RAW_PIXELS) return fail(SRLHIP_ENOTSUP, "raw_pixels observations are not supported (ground_truth only)");
+    if (c.obs_mode == SRLHIP_OBS_JOINTS) return fail(SRLHIP_ENOTSUP, "the joints observation mode is not supported (ground_truth only)");
+    if (c.obs_mode == SRLHIP_OBS_JOINTS_POSITION) return fail(SRLHIP_ENOTSUP, "the joints_position observation mode is not supported (ground_truth only)");
+    if (c.env_kind == SRLHIP_ENV_KUKA_RAND) return fail(SRLHIP_ENOTSUP, "KukaRandButtonGymEnv is not supported");
+    if (!is_mobile(c.env_kind) && c.kuka_model != SRLHIP_KUKA_MODEL_FULL) return fail(SRLHIP_ENOTSUP, "the lumped Kuka model is not supported");
+    int rc = set_device(h);                            // (parks a resident kernel)
+    if (rc) return rc;
+    const size_t D = (size_t)obs_dim_of(c), wcount = pc.count * (pa.per_env ? (size_t)h->n : 1);
+    RolloutPlanes dev = host;
+    std::vector<double> packed;                        // host-pointer handles: [mean D][std D] doubles, then the parameters, one staged block
+    if (!c.io_device) {
+        if (!(pc.elem == 8 ? all_finite_f64(static_cast<const double *>(pa.w), wcount) : all_finite_f32(static_cast<const float *>(pa.w), wcount)))
+            return fail(SRLHIP_EINVAL, std::string("non-finite ") + pc.what);
+        if (pa.normalize) {
+            if (!all_finite_f64(pa.mean, D)) return fail(SRLHIP_EINVAL, "non-finite obs_mean");
+            for (size_t d = 0; d < D; d++)
+                if (!(std::isfinite(pa.std[d]) && pa.std[d] > 0.0)) return fail(SRLHIP_EINVAL, "obs_std entries must be finite and > 0");
+        }
+        packed.assign(2 * D + (pc.elem * wcount + 7) / 8, 1.0);
+        if (pa.normalize) { memcpy(packed.data(), pa.mean, 8 * D); memcpy(packed.data() + D, pa.std, 8 * D); }
+        memcpy(packed.data() + 2 * D, pa.w, pc.elem * wcount);
+        if ((rc = stage_in(h, &h->st_rand, &h->st_rand_sz, packed.data(), 8 * packed.size()))) return rc;
+        const double *blk = static_cast<const double *>(h->st_rand);
+        pa.w = blk + 2 * D;
+        if (pa.normalize) { pa.mean = blk; pa.std = blk + D; }
+        if ((rc = stage_rollout_planes(h, T, dev))) return rc;
+    }
+    rc = is_mobile(c.env_kind) ? mobile_rollout_policy(h, T, pa, static_cast<float *>(dev.obs), dev.rew, dev.done, dev.act)
+                               : pc.kuka(h, T, pa, h->policy_hdr, static_cast<float *>(dev.obs), dev.rew, dev.done, dev.act);
+    if (rc) return rc;
+    return c.io_device ? 0 : fetch_rollout_planes(h, T, host, dev);      // (`packed` must outlive its copy: the synchronisation is in there)
+}
 }  // namespace
 
 extern "C" {
@@ -706,45 +792,38 @@ int srlhip_rollout(srlhip_handle hh, int32_t T, const void *actions_TN, void *ob
     if (!h->cfg.auto_reset || h->cfg.rng_mode == SRLHIP_RNG_HOST)
         return h->fail(SRLHIP_EINVAL, "rollout: needs auto_reset and a device RNG mode");
     const size_t n = (size_t)h->n, tn = n * (size_t)T;
-    const void *d_act = actions_TN; void *d_obs = obs_TN; float *d_rew = reward_TN; uint8_t *d_done = done_TN;
-    void *d_act_out = act_out_TN;
-    const size_t ob = obs_bytes_per_env(h) * tn, ab = action_bytes(h) * (size_t)T;
+    const void *d_act = actions_TN;
+    const RolloutPlanes host{obs_TN, reward_TN, done_TN, act_out_TN};
+    RolloutPlanes dev = host;
     if (!h->cfg.io_device) {
         if (actions_TN && !h->cfg.is_discrete && !continuous_actions_ok(h, static_cast<const float *>(actions_TN), tn))
             return h->fail(SRLHIP_EINVAL, "rollout: non-finite continuous action (a Kuka env's `None` is a row of NaNs)");
-        if (actions_TN) { if ((rc = stage_in(h, &h->st_actions, &h->st_actions_sz, actions_TN, ab))) return rc; d_act = h->st_actions; }
-        else if (act_out_TN) { if ((rc = ensure(h, &h->st_actions, &h->st_actions_sz, ab))) return rc; d_act_out = h->st_actions; }
-        if (obs_TN) { if ((rc = ensure(h, &h->st_obs, &h->st_obs_sz, ob))) return rc; d_obs = h->st_obs; }
-        if (reward_TN) { if ((rc = ensure(h, &h->st_rew, &h->st_rew_sz, 4 * tn))) return rc; d_rew = static_cast<float *>(h->st_rew); }
-        if (done_TN) { if ((rc = ensure(h, &h->st_done, &h->st_done_sz, tn))) return rc; d_done = static_cast<uint8_t *>(h->st_done); }
+        if (actions_TN) {                              // st_actions holds the given plane: none is recorded (below), none comes back
+            if ((rc = stage_in(h, &h->st_actions, &h->st_actions_sz, actions_TN, action_bytes(h) * (size_t)T))) return rc;
+            d_act = h->st_actions; dev.act = nullptr;
+        }
+        if ((rc = stage_rollout_planes(h, T, dev))) return rc;
     }
     if (h->cfg.obs_mode != SRLHIP_OBS_RAW_PIXELS) {
         rc = is_mobile(h->cfg.env_kind)
-                 ? mobile_rollout(h, T, d_act, static_cast<float *>(d_obs), d_rew, d_done, actions_TN ? nullptr : d_act_out)
-                 : kuka_rollout(h, T, d_act, d_obs, d_rew, d_done, actions_TN ? nullptr : d_act_out);
+                 ? mobile_rollout(h, T, d_act, static_cast<float *>(dev.obs), dev.rew, dev.done, actions_TN ? nullptr : dev.act)
+                 : kuka_rollout(h, T, d_act, dev.obs, dev.rew, dev.done, actions_TN ? nullptr : dev.act);
         if (rc) return rc;
     } else {
         // images are drawn between steps: one stepper launch + one rasteriser launch per step, same stream
         const size_t a_step = action_bytes(h), o_step = obs_bytes_per_env(h) * n;
         for (int32_t t = 0; t < T; t++) {
             const void *a_t = d_act ? static_cast<const uint8_t *>(d_act) + (size_t)t * a_step : nullptr;
-            void *ao_t = (!actions_TN && d_act_out) ? static_cast<uint8_t *>(d_act_out) + (size_t)t * a_step : nullptr;
-            float *r_t = d_rew ? d_rew + (size_t)t * n : nullptr;
-            uint8_t *dn_t = d_done ? d_done + (size_t)t * n : nullptr;
+            void *ao_t = (!actions_TN && dev.act) ? static_cast<uint8_t *>(dev.act) + (size_t)t * a_step : nullptr;
+            float *r_t = dev.rew ? dev.rew + (size_t)t * n : nullptr;
+            uint8_t *dn_t = dev.done ? dev.done + (size_t)t * n : nullptr;
             rc = is_mobile(h->cfg.env_kind) ? mobile_rollout(h, 1, a_t, nullptr, r_t, dn_t, ao_t)
                                             : kuka_rollout(h, 1, a_t, nullptr, r_t, dn_t, ao_t);
             if (rc) return rc;
-            if (d_obs && (rc = raster_render(h, static_cast<uint8_t *>(d_obs) + (size_t)t * o_step))) return rc;
+            if (dev.obs && (rc = raster_render(h, static_cast<uint8_t *>(dev.obs) + (size_t)t * o_step))) return rc;
         }
     }
-    if (!h->cfg.io_device) {
-        if (obs_TN) SRL_HIP_CHECK(h, hipMemcpyAsync(obs_TN, d_obs, ob, hipMemcpyDeviceToHost, h->stream));
-        if (reward_TN) SRL_HIP_CHECK(h, hipMemcpyAsync(reward_TN, d_rew, 4 * tn, hipMemcpyDeviceToHost, h->stream));
-        if (done_TN) SRL_HIP_CHECK(h, hipMemcpyAsync(done_TN, d_done, tn, hipMemcpyDeviceToHost, h->stream));
-        if (act_out_TN && !actions_TN) SRL_HIP_CHECK(h, hipMemcpyAsync(act_out_TN, d_act_out, ab, hipMemcpyDeviceToHost, h->stream));
-        SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));
-    }
-    return 0;
+    return h->cfg.io_device ? 0 : fetch_rollout_planes(h, T, host, dev);
 }
 
 int srlhip_rollout_policy(srlhip_handle hh, int32_t T, const srlhip_linear_policy *pol, void *obs_TN, float *reward_TN,
@@ -753,59 +832,10 @@ int srlhip_rollout_policy(srlhip_handle hh, int32_t T, const srlhip_linear_polic
     Handle *h = reinterpret_cast<Handle *>(hh);
     if (!pol) return h->fail(SRLHIP_EINVAL, "rollout_policy: null policy");
     if (pol->struct_size != (int32_t)sizeof(srlhip_linear_policy)) return h->fail(SRLHIP_EINVAL, "rollout_policy: srlhip_linear_policy.struct_size mismatch (ABI)");
-    if (T <= 0) return h->fail(SRLHIP_EINVAL, "rollout_policy: T must be positive");
-    if (h->step_pending) return h->fail(SRLHIP_EINVAL, "rollout_policy: a srlhip_step_async is pending (call srlhip_step_wait first)");
-    if (!pol->weights) return h->fail(SRLHIP_EINVAL, "rollout_policy: null weights");
-    if (pol->normalize && (!pol->obs_mean || !pol->obs_std)) return h->fail(SRLHIP_EINVAL, "rollout_policy: normalize needs obs_mean and obs_std");
-    const srlhip_config &c = h->cfg;
-    // what has no policy kernel: refused by name, the handle stays as it was
-    if (c.rng_mode == SRLHIP_RNG_HOST) return h->fail(SRLHIP_ENOTSUP, "rollout_policy: RNG_HOST is not supported (needs a device RNG mode)");
-    if (!c.auto_reset) return h->fail(SRLHIP_ENOTSUP, "rollout_policy: needs auto_reset");
-    if (c.obs_mode == SRLHIP_OBS_RAW_PIXELS) return h->fail(SRLHIP_ENOTSUP, "rollout_policy: raw_pixels observations are not supported (ground_truth only)");
-    if (c.obs_mode == SRLHIP_OBS_JOINTS) return h->fail(SRLHIP_ENOTSUP, "rollout_policy: the joints observation mode is not supported (ground_truth only)");
-    if (c.obs_mode == SRLHIP_OBS_JOINTS_POSITION) return h->fail(SRLHIP_ENOTSUP, "rollout_policy: the joints_position observation mode is not supported (ground_truth only)");
-    if (c.env_kind == SRLHIP_ENV_KUKA_RAND) return h->fail(SRLHIP_ENOTSUP, "rollout_policy: KukaRandButtonGymEnv is not supported");
-    if (!is_mobile(c.env_kind) && c.kuka_model != SRLHIP_KUKA_MODEL_FULL) return h->fail(SRLHIP_ENOTSUP, "rollout_policy: the lumped Kuka model is not supported");
-    int rc = set_device(h);                            // (parks a resident kernel)
+    int rc = policy_call_begin(h, "rollout_policy", T);
     if (rc) return rc;
-    const size_t n = (size_t)h->n, tn = n * (size_t)T;
-    const size_t D = (size_t)obs_dim_of(c), A = (size_t)(c.is_discrete ? num_actions_of(c) : action_dim_of(c));
-    const size_t wcount = D * A * (pol->per_env ? n : 1);
-    PolicyArgs pa{pol->weights, pol->normalize ? pol->obs_mean : nullptr, pol->normalize ? pol->obs_std : nullptr, pol->clip_obs,
-                  pol->per_env ? 1 : 0, pol->freeze_after_done ? 1 : 0, pol->normalize ? 1 : 0};
-    void *d_obs = obs_TN; float *d_rew = reward_TN; uint8_t *d_done = done_TN; void *d_act_out = act_out_TN;
-    const size_t ob = obs_bytes_per_env(h) * tn, ab = action_bytes(h) * (size_t)T;
-    std::vector<double> packed;                        // host-pointer handles: [mean D][std D][weights], one staged block
-    if (!c.io_device) {
-        if (!all_finite_f64(pol->weights, wcount)) return h->fail(SRLHIP_EINVAL, "rollout_policy: non-finite weights");
-        if (pol->normalize) {
-            if (!all_finite_f64(pol->obs_mean, D)) return h->fail(SRLHIP_EINVAL, "rollout_policy: non-finite obs_mean");
-            for (size_t d = 0; d < D; d++)
-                if (!(std::isfinite(pol->obs_std[d]) && pol->obs_std[d] > 0.0)) return h->fail(SRLHIP_EINVAL, "rollout_policy: obs_std entries must be finite and > 0");
-        }
-        packed.assign(2 * D + wcount, 1.0);
-        if (pol->normalize) { memcpy(packed.data(), pol->obs_mean, 8 * D); memcpy(packed.data() + D, pol->obs_std, 8 * D); }
-        memcpy(packed.data() + 2 * D, pol->weights, 8 * wcount);
-        if ((rc = stage_in(h, &h->st_rand, &h->st_rand_sz, packed.data(), 8 * packed.size()))) return rc;
-        const double *blk = static_cast<const double *>(h->st_rand);
-        pa.w = blk + 2 * D;
-        if (pol->normalize) { pa.mean = blk; pa.std = blk + D; }
-        if (act_out_TN) { if ((rc = ensure(h, &h->st_actions, &h->st_actions_sz, ab))) return rc; d_act_out = h->st_actions; }
-        if (obs_TN) { if ((rc = ensure(h, &h->st_obs, &h->st_obs_sz, ob))) return rc; d_obs = h->st_obs; }
-        if (reward_TN) { if ((rc = ensure(h, &h->st_rew, &h->st_rew_sz, 4 * tn))) return rc; d_rew = static_cast<float *>(h->st_rew); }
-        if (done_TN) { if ((rc = ensure(h, &h->st_done, &h->st_done_sz, tn))) return rc; d_done = static_cast<uint8_t *>(h->st_done); }
-    }
-    rc = is_mobile(c.env_kind) ? mobile_rollout_policy(h, T, pa, static_cast<float *>(d_obs), d_rew, d_done, d_act_out)
-                               : kuka_rollout_policy(h, T, pa, h->policy_hdr, static_cast<float *>(d_obs), d_rew, d_done, d_act_out);
-    if (rc) return rc;
-    if (!c.io_device) {
-        if (obs_TN) SRL_HIP_CHECK(h, hipMemcpyAsync(obs_TN, d_obs, ob, hipMemcpyDeviceToHost, h->stream));
-        if (reward_TN) SRL_HIP_CHECK(h, hipMemcpyAsync(reward_TN, d_rew, 4 * tn, hipMemcpyDeviceToHost, h->stream));
-        if (done_TN) SRL_HIP_CHECK(h, hipMemcpyAsync(done_TN, d_done, tn, hipMemcpyDeviceToHost, h->stream));
-        if (act_out_TN) SRL_HIP_CHECK(h, hipMemcpyAsync(act_out_TN, d_act_out, ab, hipMemcpyDeviceToHost, h->stream));
-        SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));       // (`packed` must outlive its copy)
-    }
-    return 0;
+    const PolicyCall pc{"rollout_policy", "weights", 8, (size_t)obs_dim_of(h->cfg) * policy_outputs(h->cfg), kuka_rollout_policy};
+    return rollout_policy(h, T, pc, policy_args(*pol, pol->weights, 0), {obs_TN, reward_TN, done_TN, act_out_TN});
 }
 
 int srlhip_rollout_mlp_policy(srlhip_handle hh, int32_t T, const srlhip_mlp_policy *pol, void *obs_TN, float *reward_TN,
@@ -814,62 +844,13 @@ int srlhip_rollout_mlp_policy(srlhip_handle hh, int32_t T, const srlhip_mlp_poli
     Handle *h = reinterpret_cast<Handle *>(hh);
     if (!pol) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: null policy");
     if (pol->struct_size != (int32_t)sizeof(srlhip_mlp_policy)) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: srlhip_mlp_policy.struct_size mismatch (ABI)");
-    if (T <= 0) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: T must be positive");
-    if (h->step_pending) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: a srlhip_step_async is pending (call srlhip_step_wait first)");
+    int rc = policy_call_begin(h, "rollout_mlp_policy", T);
+    if (rc) return rc;
     if (pol->hidden < 1 || pol->hidden > 128) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: hidden must be in 1..128");
     if (pol->reserved != 0) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: reserved must be 0");
-    if (!pol->params) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: null params");
-    if (pol->normalize && (!pol->obs_mean || !pol->obs_std)) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: normalize needs obs_mean and obs_std");
-    const srlhip_config &c = h->cfg;
-    // the same refusals as srlhip_rollout_policy, by name; the handle stays as it was
-    if (c.rng_mode == SRLHIP_RNG_HOST) return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy: RNG_HOST is not supported (needs a device RNG mode)");
-    if (!c.auto_reset) return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy: needs auto_reset");
-    if (c.obs_mode == SRLHIP_OBS_RAW_PIXELS) return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy: raw_pixels observations are not supported (ground_truth only)");
-    if (c.obs_mode == SRLHIP_OBS_JOINTS) return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy: the joints observation mode is not supported (ground_truth only)");
-    if (c.obs_mode == SRLHIP_OBS_JOINTS_POSITION) return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy: the joints_position observation mode is not supported (ground_truth only)");
-    if (c.env_kind == SRLHIP_ENV_KUKA_RAND) return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy: KukaRandButtonGymEnv is not supported");
-    if (!is_mobile(c.env_kind) && c.kuka_model != SRLHIP_KUKA_MODEL_FULL) return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy: the lumped Kuka model is not supported");
-    int rc = set_device(h);                            // (parks a resident kernel)
-    if (rc) return rc;
-    const size_t n = (size_t)h->n, tn = n * (size_t)T;
-    const size_t D = (size_t)obs_dim_of(c), A = (size_t)(c.is_discrete ? num_actions_of(c) : action_dim_of(c)), H = (size_t)pol->hidden;
-    const size_t wcount = (H * D + H + A * H + A) * (pol->per_env ? n : 1);
-    MlpPolicyArgs pa{pol->params, pol->normalize ? pol->obs_mean : nullptr, pol->normalize ? pol->obs_std : nullptr, pol->clip_obs,
-                     pol->per_env ? 1 : 0, pol->freeze_after_done ? 1 : 0, pol->normalize ? 1 : 0, pol->hidden};
-    void *d_obs = obs_TN; float *d_rew = reward_TN; uint8_t *d_done = done_TN; void *d_act_out = act_out_TN;
-    const size_t ob = obs_bytes_per_env(h) * tn, ab = action_bytes(h) * (size_t)T;
-    std::vector<double> packed;                        // host-pointer handles: [mean D][std D] doubles, then the float32 params, one staged block
-    if (!c.io_device) {
-        for (size_t i = 0; i < wcount; i++)
-            if (!std::isfinite(pol->params[i])) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: non-finite params");
-        if (pol->normalize) {
-            if (!all_finite_f64(pol->obs_mean, D)) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: non-finite obs_mean");
-            for (size_t d = 0; d < D; d++)
-                if (!(std::isfinite(pol->obs_std[d]) && pol->obs_std[d] > 0.0)) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: obs_std entries must be finite and > 0");
-        }
-        packed.assign(2 * D + (wcount + 1) / 2, 1.0);
-        if (pol->normalize) { memcpy(packed.data(), pol->obs_mean, 8 * D); memcpy(packed.data() + D, pol->obs_std, 8 * D); }
-        memcpy(packed.data() + 2 * D, pol->params, 4 * wcount);
-        if ((rc = stage_in(h, &h->st_rand, &h->st_rand_sz, packed.data(), 8 * packed.size()))) return rc;
-        const double *blk = static_cast<const double *>(h->st_rand);
-        pa.w = reinterpret_cast<const float *>(blk + 2 * D);
-        if (pol->normalize) { pa.mean = blk; pa.std = blk + D; }
-        if (act_out_TN) { if ((rc = ensure(h, &h->st_actions, &h->st_actions_sz, ab))) return rc; d_act_out = h->st_actions; }
-        if (obs_TN) { if ((rc = ensure(h, &h->st_obs, &h->st_obs_sz, ob))) return rc; d_obs = h->st_obs; }
-        if (reward_TN) { if ((rc = ensure(h, &h->st_rew, &h->st_rew_sz, 4 * tn))) return rc; d_rew = static_cast<float *>(h->st_rew); }
-        if (done_TN) { if ((rc = ensure(h, &h->st_done, &h->st_done_sz, tn))) return rc; d_done = static_cast<uint8_t *>(h->st_done); }
-    }
-    rc = is_mobile(c.env_kind) ? mobile_rollout_mlp_policy(h, T, pa, static_cast<float *>(d_obs), d_rew, d_done, d_act_out)
-                               : kuka_rollout_mlp_policy(h, T, pa, h->policy_hdr, static_cast<float *>(d_obs), d_rew, d_done, d_act_out);
-    if (rc) return rc;
-    if (!c.io_device) {
-        if (obs_TN) SRL_HIP_CHECK(h, hipMemcpyAsync(obs_TN, d_obs, ob, hipMemcpyDeviceToHost, h->stream));
-        if (reward_TN) SRL_HIP_CHECK(h, hipMemcpyAsync(reward_TN, d_rew, 4 * tn, hipMemcpyDeviceToHost, h->stream));
-        if (done_TN) SRL_HIP_CHECK(h, hipMemcpyAsync(done_TN, d_done, tn, hipMemcpyDeviceToHost, h->stream));
-        if (act_out_TN) SRL_HIP_CHECK(h, hipMemcpyAsync(act_out_TN, d_act_out, ab, hipMemcpyDeviceToHost, h->stream));
-        SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));       // (`packed` must outlive its copy)
-    }
-    return 0;
+    const size_t D = (size_t)obs_dim_of(h->cfg), A = policy_outputs(h->cfg), H = (size_t)pol->hidden;
+    const PolicyCall pc{"rollout_mlp_policy", "params", 4, H * D + H + A * H + A, kuka_rollout_mlp_policy};
+    return rollout_policy(h, T, pc, policy_args(*pol, pol->params, pol->hidden), {obs_TN, reward_TN, done_TN, act_out_TN});
 }
 
 int srlhip_get_state(srlhip_handle hh, int32_t field, void *out) {

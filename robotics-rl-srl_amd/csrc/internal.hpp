@@ -2,6 +2,7 @@
 // kernel translation units (mobile.hip, kuka.hip).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <string>
@@ -55,25 +56,25 @@ int mobile_step(Handle *h, const void *d_actions, const double *d_noise, float *
                 uint8_t *d_done);
 int mobile_rollout(Handle *h, int T, const void *d_actions, float *d_obs, float *d_rew, uint8_t *d_done,
                    void *d_act_out);
-// srlhip_rollout_policy: the linear policy as the kernels take it (device pointers; mean / std null without normalisation)
+// srlhip_rollout_policy / srlhip_rollout_mlp_policy: the policy as the kernels take it (device pointers; mean / std null without
+// normalisation).  hidden == 0: the linear policy, w = float64 [n][D][A] or [D][A]; hidden = H >= 1: the one-hidden-layer MLP,
+// w = float32 [n][P] or [P], P = H D + H + A H + A.  Passed to kernels BY VALUE: the layout is part of their argument block.
 struct PolicyArgs {
-    const double *w, *mean, *std;
-    double clip;
-    int32_t per_env, freeze, normalize;
-};
-int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
-// kuka_tree_policy.hip (full model); d_hdr: the handle's 16-double policy header
-int kuka_rollout_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
-// srlhip_rollout_mlp_policy: the one-hidden-layer MLP as the kernels take it; w: float32 [n][P] or [P], P = H D + H + A H + A
-struct MlpPolicyArgs {
-    const float *w;
+    const void *w;
     const double *mean, *std;
     double clip;
     int32_t per_env, freeze, normalize, hidden;
 };
-int mobile_rollout_mlp_policy(Handle *h, int T, const MlpPolicyArgs &pol, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
-// kuka_tree_mlp.hip (full model); d_hdr: the handle's 16-double policy header
-int kuka_rollout_mlp_policy(Handle *h, int T, const MlpPolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
+static_assert(sizeof(PolicyArgs) == 48 && offsetof(PolicyArgs, w) == 0 && offsetof(PolicyArgs, mean) == 8 && offsetof(PolicyArgs, std) == 16 &&
+                  offsetof(PolicyArgs, clip) == 24 && offsetof(PolicyArgs, per_env) == 32 && offsetof(PolicyArgs, freeze) == 36 &&
+                  offsetof(PolicyArgs, normalize) == 40 && offsetof(PolicyArgs, hidden) == 44,
+              "PolicyArgs is a kernel argument: its layout is what the policy kernels were compiled against");
+// mobile.hip: the linear or the MLP kernel family by pol.hidden
+int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
+// kuka_tree_policy.hip / kuka_tree_mlp.hip (full model); d_hdr: the handle's 16-double policy header
+int kuka_rollout_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
+int kuka_rollout_mlp_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
+int kuka_policy_header(Handle *h, double *d_hdr, const PolicyArgs &pol);      // kuka_tree_policy.hip: the one header kernel's launch
 int mobile_field(Handle *h, int field, void **dptr, size_t *elem, int *count);
 int mobile_reset_rand_count(const srlhip_config &c);
 int mobile_persist_blocks(Handle *h, int *capacity, uint32_t *eighths);      // persistent stepping (mobile.hip)

@@ -164,14 +164,14 @@ __device__ __forceinline__ double mlp_row_sum(double x) {
 
 // POLICY = 1 (srlhip_rollout_policy; kuka_tree_policy.hip): the third action source — a linear policy of the env's own current
 // ground-truth observation.  `actions` is then the float64 weight plane ([n][3][A] or [3][A]) and `noise` the 10-double header
-// kuka_policy_header_k wrote (per_env, freeze, normalize, clip, mean[3], std[3]).  Lane a < A of the env's row keeps column a of the
+// kuka_policy_hdr_k wrote (per_env, freeze, normalize, clip, mean[3], std[3]).  Lane a < A of the env's row keeps column a of the
 // env's weights in VGPRs (LDS is full: 40 712 B per wavefront = four wavefronts per CU), mean / std sit in every lane; all of it is
 // loaded before the prologue's vmcnt wait, nothing inside the loop.  At the loop top every lane forms the observation from the row's
 // replicated env scalars and its own score; the row's scores are broadcast (DPP row_newbcast) and every lane takes the same strict
 // argmax (lowest lane wins a tie), or lane j's score becomes ca[j].
 // POLICY = 2 (srlhip_rollout_mlp_policy; kuka_tree_mlp.hip): a one-hidden-layer ReLU MLP of the same observation.  `actions` is the
 // float32 parameter plane ([n][P] or [P], P = 3 H + H + A H + A in nn.Module.parameters() order) and `noise` the 11-double header
-// kuka_mlp_header_k wrote (the ten above, then H).  Lane l of the env's row owns the hidden units l, l + 16, ... (at most 8: H <= 128)
+// kuka_policy_hdr_k wrote (the ten above, then H).  Lane l of the env's row owns the hidden units l, l + 16, ... (at most 8: H <= 128)
 // and holds their fc_in rows, biases and fc_out columns as float32 locals (units >= H: zeros), lane 0 also fc_out's bias; the
 // parameter plane is read once, before the prologue's vmcnt wait, never inside the loop.  The locals do NOT all stay in registers:
 // 86 - 95 floats next to a kernel already at 403 - 503 of 512 registers put every instantiation at the budget, and the compiler
@@ -652,6 +652,37 @@ kuka_tree_reset_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, const
             observe(v, p.cfg, obs + (int64_t)e * od, 1);
         }
     }
+}
+
+// srlhip_rollout_policy (POLICY = 1, kuka_tree_policy.hip) / srlhip_rollout_mlp_policy (POLICY = 2, kuka_tree_mlp.hip): the launch both
+// share — {PHILOX, MT19937} x {Cartesian one button, joint-space actions one button, Cartesian two buttons}, generic configuration
+// (SPEC = 0), launching form.  Every batch size runs this one-wavefront-per-SIMD kernel (the two-wavefront variant of kuka_tree_occ.hip
+// has no policy form).  Instantiating it instantiates the six kernels: once per POLICY, each in its own translation unit.
+// The guard restates what srlhip_rollout_policy / srlhip_rollout_mlp_policy have refused by name before they come here (api.hip:
+// rollout_policy): through the ABI it never fires, so where a caller's own refusal stands relative to it cannot be observed.
+template <int POLICY>
+int kuka_tree_policy_launch(Handle *h, const char *name, int T, const PolicyArgs &pol, double *d_hdr, float *obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
+    const srlhip_config &c = h->cfg;
+    if (!h->kuka || !h->kuka->full || c.env_kind == SRLHIP_ENV_KUKA_RAND || c.obs_mode != SRLHIP_OBS_GROUND_TRUTH || !c.auto_reset ||
+        (c.rng_mode != SRLHIP_RNG_PHILOX && c.rng_mode != SRLHIP_RNG_MT19937))
+        return h->fail(SRLHIP_ENOTSUP, std::string(name) + ": no policy instantiation for this Kuka configuration");
+    const KukaParams p = params_of(h);
+    int rc = kuka_policy_header(h, d_hdr, pol);
+    if (rc) return rc;
+    dim3 grid(contiguous_grid((h->n + kGroupEnvs - 1) / kGroupEnvs)), block(kGroupBlock);      // as kuka_tree_launch: blocks map to envs XCD by XCD
+    const bool joints = !c.is_discrete && c.action_joints, two = c.env_kind == SRLHIP_ENV_KUKA_2BUTTON;
+    const void *d_w = pol.w;
+    const double *hdr = d_hdr;
+#define SRL_TREE_POL(MODE, J, NB) hipLaunchKernelGGL((kuka_tree_rollout_k<MODE, J, false, NB, 0, 0, 0, POLICY>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, T, d_w, hdr, obs, d_rew, d_done, d_act_out, PersistArgs{})
+#define SRL_TREE_POL_MODE(MODE)                       \
+    if (two) SRL_TREE_POL(MODE, false, 2);            \
+    else if (joints) SRL_TREE_POL(MODE, true, 1);     \
+    else SRL_TREE_POL(MODE, false, 1);
+    if (c.rng_mode == SRLHIP_RNG_PHILOX) { SRL_TREE_POL_MODE(SRLHIP_RNG_PHILOX) } else { SRL_TREE_POL_MODE(SRLHIP_RNG_MT19937) }
+#undef SRL_TREE_POL_MODE
+#undef SRL_TREE_POL
+    SRL_HIP_CHECK(h, hipGetLastError());
+    return 0;
 }
 
 }  // namespace

@@ -1,44 +1,30 @@
-// kuka_tree_policy.hip — srlhip_rollout_policy on the full Kuka model: the POLICY instantiations of kuka_tree_rollout_k
-// (kuka_tree_kernels.hpp) — {PHILOX, MT19937} x {Cartesian one button, joint-space actions one button, Cartesian two buttons}, generic
-// configuration (SPEC = 0), launching form — and the header kernel that hands the policy's scalars to them.  Every batch size runs
-// this one-wavefront-per-SIMD kernel (the two-wavefront variant of kuka_tree_occ.hip has no policy form).
+// kuka_tree_policy.hip — srlhip_rollout_policy on the full Kuka model: the POLICY = 1 instantiations of kuka_tree_rollout_k (through
+// kuka_tree_kernels.hpp's kuka_tree_policy_launch), and the header kernel that hands a policy's scalars to them and to kuka_tree_mlp.hip's.
 #include "kuka_tree_kernels.hpp"
 
 namespace srl {
 using namespace kuka;
 
 namespace {
-// the 10 doubles the rollout kernel reads behind its `noise` argument; mean / std null without normalisation.  A kernel, not a copy:
-// on device-pointer handles mean / std are device memory and the call may sit inside a stream capture.
-__global__ void kuka_policy_header_k(double *hdr, PolicyArgs pol) {
+// the 11 doubles the rollout kernels read behind their `noise` argument (slot 10, the hidden width, by POLICY = 2 only); mean / std null
+// without normalisation.  A kernel, not a copy: on device-pointer handles mean / std are device memory and the call may sit inside a
+// stream capture.
+__global__ void kuka_policy_hdr_k(double *hdr, PolicyArgs pol) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     hdr[0] = pol.per_env; hdr[1] = pol.freeze; hdr[2] = pol.normalize; hdr[3] = pol.clip;
     for (int d = 0; d < 3; d++) { hdr[4 + d] = pol.normalize ? pol.mean[d] : 0.0; hdr[7 + d] = pol.normalize ? pol.std[d] : 1.0; }
+    hdr[10] = pol.hidden;
 }
 }  // namespace
 
-int kuka_rollout_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
-    const srlhip_config &c = h->cfg;
-    if (!h->kuka || !h->kuka->full || c.env_kind == SRLHIP_ENV_KUKA_RAND || c.obs_mode != SRLHIP_OBS_GROUND_TRUTH || !c.auto_reset ||
-        (c.rng_mode != SRLHIP_RNG_PHILOX && c.rng_mode != SRLHIP_RNG_MT19937))
-        return h->fail(SRLHIP_ENOTSUP, "rollout_policy: no policy instantiation for this Kuka configuration");
-    const KukaParams p = params_of(h);
-    hipLaunchKernelGGL(kuka_policy_header_k, dim3(1), dim3(64), 0, h->stream, d_hdr, pol);
-    SRL_HIP_CHECK(h, hipGetLastError());
-    dim3 grid(contiguous_grid((h->n + kGroupEnvs - 1) / kGroupEnvs)), block(kGroupBlock);      // as kuka_tree_launch: blocks map to envs XCD by XCD
-    const bool joints = !c.is_discrete && c.action_joints, two = c.env_kind == SRLHIP_ENV_KUKA_2BUTTON;
-    const void *d_w = pol.w;
-    const double *hdr = d_hdr;
-#define SRL_TREE_POL(MODE, J, NB) hipLaunchKernelGGL((kuka_tree_rollout_k<MODE, J, false, NB, 0, 0, 0, 1>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, T, d_w, hdr, obs, d_rew, d_done, d_act_out, PersistArgs{})
-#define SRL_TREE_POL_MODE(MODE)                       \
-    if (two) SRL_TREE_POL(MODE, false, 2);            \
-    else if (joints) SRL_TREE_POL(MODE, true, 1);     \
-    else SRL_TREE_POL(MODE, false, 1);
-    if (c.rng_mode == SRLHIP_RNG_PHILOX) { SRL_TREE_POL_MODE(SRLHIP_RNG_PHILOX) } else { SRL_TREE_POL_MODE(SRLHIP_RNG_MT19937) }
-#undef SRL_TREE_POL_MODE
-#undef SRL_TREE_POL
+int kuka_policy_header(Handle *h, double *d_hdr, const PolicyArgs &pol) {
+    hipLaunchKernelGGL(kuka_policy_hdr_k, dim3(1), dim3(64), 0, h->stream, d_hdr, pol);
     SRL_HIP_CHECK(h, hipGetLastError());
     return 0;
+}
+
+int kuka_rollout_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
+    return kuka_tree_policy_launch<1>(h, "rollout_policy", T, pol, d_hdr, obs, d_rew, d_done, d_act_out);
 }
 
 }  // namespace srl

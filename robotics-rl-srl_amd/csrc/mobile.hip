@@ -412,7 +412,7 @@ mobile_rollout_policy_k(MobileParams p, MobileState s, RngState rs, EpisodeStats
     MobileEnv m;
     load_env(s, e, m);
     double W[D][A], mean[D], sd[D];
-    const double *w = pol.w + (pol.per_env ? (int64_t)e * (D * A) : 0);
+    const double *w = static_cast<const double *>(pol.w) + (pol.per_env ? (int64_t)e * (D * A) : 0);
 #pragma unroll
     for (int d = 0; d < D; d++) {
 #pragma unroll
@@ -503,7 +503,7 @@ __device__ __forceinline__ float row_lead_f32(float x) {      // lane 0 of the r
 
 template <int MODE, int KIND, int DISC>
 __global__ void __launch_bounds__(kBlock)
-mobile_rollout_mlp_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, int T, MlpPolicyArgs pol,
+mobile_rollout_mlp_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, int T, PolicyArgs pol,
                      float *__restrict__ obs, float *__restrict__ rew, uint8_t *__restrict__ done_out, void *__restrict__ act_out) {
     constexpr int D = KIND == SRLHIP_ENV_MOBILE_1D ? 1 : 2;
     constexpr int A = DISC ? (KIND == SRLHIP_ENV_MOBILE_1D ? 2 : 4) : 2;
@@ -514,7 +514,7 @@ mobile_rollout_mlp_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st
     p.kind = KIND; p.is_discrete = DISC;
     const int H = pol.hidden;
     float W1[kMlpUnits][D], B1[kMlpUnits], W2[A][kMlpUnits], B2[A];
-    const float *w = pol.w + (pol.per_env ? (int64_t)e * (H * D + H + A * H + A) : 0);
+    const float *w = static_cast<const float *>(pol.w) + (pol.per_env ? (int64_t)e * (H * D + H + A * H + A) : 0);
 #pragma unroll
     for (int u = 0; u < kMlpUnits; u++) {
         const int j = l + kMlpLanes * u;
@@ -1128,46 +1128,26 @@ int mobile_rollout(Handle *h, int T, const void *d_actions, float *d_obs, float 
     return 0;
 }
 
+// srlhip_rollout_policy (pol.hidden == 0: one lane per env) / srlhip_rollout_mlp_policy (16 lanes per env)
 int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
     const MobileParams p = params_of(h);
     if ((h->cfg.rng_mode != SRLHIP_RNG_PHILOX && h->cfg.rng_mode != SRLHIP_RNG_MT19937) || !p.auto_reset)
-        return h->fail(SRLHIP_ENOTSUP, "rollout_policy: needs auto_reset and a device RNG mode (PHILOX or MT19937)");
+        return h->fail(SRLHIP_ENOTSUP, std::string(pol.hidden ? "rollout_mlp_policy" : "rollout_policy") + ": needs auto_reset and a device RNG mode (PHILOX or MT19937)");
     h->snap_valid = false;                      // the live state moves, the episode-parallel rollout's snapshot set does not
-    dim3 grid((h->n + kBlock - 1) / kBlock), block(kBlock);
-#define SRL_GO(MODE, KIND, DISC) hipLaunchKernelGGL((mobile_rollout_policy_k<MODE, KIND, DISC>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T, pol, d_obs, d_rew, d_done, d_act_out)
-#define SRL_KIND(MODE, KIND) { if (p.is_discrete) SRL_GO(MODE, KIND, 1); else SRL_GO(MODE, KIND, 0); }
-#define SRL_MODE(MODE)                                                                        \
-    switch (p.kind) {                                                                         \
-        case SRLHIP_ENV_MOBILE: SRL_KIND(MODE, SRLHIP_ENV_MOBILE) break;                       \
-        case SRLHIP_ENV_MOBILE_1D: SRL_GO(MODE, SRLHIP_ENV_MOBILE_1D, 1); break;               \
-        case SRLHIP_ENV_MOBILE_2TARGET: SRL_GO(MODE, SRLHIP_ENV_MOBILE_2TARGET, 1); break;     \
-        default: SRL_KIND(MODE, SRLHIP_ENV_MOBILE_LINE)                                        \
+    dim3 grid(((int64_t)h->n * (pol.hidden ? kMlpLanes : 1) + kBlock - 1) / kBlock), block(kBlock);
+#define SRL_GO(K, MODE, KIND, DISC) hipLaunchKernelGGL((K<MODE, KIND, DISC>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T, pol, d_obs, d_rew, d_done, d_act_out)
+#define SRL_KIND(K, MODE, KIND) { if (p.is_discrete) SRL_GO(K, MODE, KIND, 1); else SRL_GO(K, MODE, KIND, 0); }
+#define SRL_MODE(K, MODE)                                                                        \
+    switch (p.kind) {                                                                            \
+        case SRLHIP_ENV_MOBILE: SRL_KIND(K, MODE, SRLHIP_ENV_MOBILE) break;                       \
+        case SRLHIP_ENV_MOBILE_1D: SRL_GO(K, MODE, SRLHIP_ENV_MOBILE_1D, 1); break;               \
+        case SRLHIP_ENV_MOBILE_2TARGET: SRL_GO(K, MODE, SRLHIP_ENV_MOBILE_2TARGET, 1); break;     \
+        default: SRL_KIND(K, MODE, SRLHIP_ENV_MOBILE_LINE)                                        \
     }
     // (MobileRobot1D / 2Target take discrete actions only: srlhip_create refuses the other combination)
-    if (h->cfg.rng_mode == SRLHIP_RNG_PHILOX) SRL_MODE(SRLHIP_RNG_PHILOX) else SRL_MODE(SRLHIP_RNG_MT19937)
-#undef SRL_MODE
-#undef SRL_KIND
-#undef SRL_GO
-    SRL_HIP_CHECK(h, hipGetLastError());
-    return 0;
-}
-
-int mobile_rollout_mlp_policy(Handle *h, int T, const MlpPolicyArgs &pol, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
-    const MobileParams p = params_of(h);
-    if ((h->cfg.rng_mode != SRLHIP_RNG_PHILOX && h->cfg.rng_mode != SRLHIP_RNG_MT19937) || !p.auto_reset)
-        return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy: needs auto_reset and a device RNG mode (PHILOX or MT19937)");
-    h->snap_valid = false;                      // the live state moves, the episode-parallel rollout's snapshot set does not
-    dim3 grid(((int64_t)h->n * kMlpLanes + kBlock - 1) / kBlock), block(kBlock);      // 16 lanes per env
-#define SRL_GO(MODE, KIND, DISC) hipLaunchKernelGGL((mobile_rollout_mlp_k<MODE, KIND, DISC>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T, pol, d_obs, d_rew, d_done, d_act_out)
-#define SRL_KIND(MODE, KIND) { if (p.is_discrete) SRL_GO(MODE, KIND, 1); else SRL_GO(MODE, KIND, 0); }
-#define SRL_MODE(MODE)                                                                        \
-    switch (p.kind) {                                                                         \
-        case SRLHIP_ENV_MOBILE: SRL_KIND(MODE, SRLHIP_ENV_MOBILE) break;                       \
-        case SRLHIP_ENV_MOBILE_1D: SRL_GO(MODE, SRLHIP_ENV_MOBILE_1D, 1); break;               \
-        case SRLHIP_ENV_MOBILE_2TARGET: SRL_GO(MODE, SRLHIP_ENV_MOBILE_2TARGET, 1); break;     \
-        default: SRL_KIND(MODE, SRLHIP_ENV_MOBILE_LINE)                                        \
-    }
-    if (h->cfg.rng_mode == SRLHIP_RNG_PHILOX) SRL_MODE(SRLHIP_RNG_PHILOX) else SRL_MODE(SRLHIP_RNG_MT19937)
+#define SRL_FAMILY(K) { if (h->cfg.rng_mode == SRLHIP_RNG_PHILOX) SRL_MODE(K, SRLHIP_RNG_PHILOX) else SRL_MODE(K, SRLHIP_RNG_MT19937) }
+    if (pol.hidden) SRL_FAMILY(mobile_rollout_mlp_k) else SRL_FAMILY(mobile_rollout_policy_k)
+#undef SRL_FAMILY
 #undef SRL_MODE
 #undef SRL_KIND
 #undef SRL_GO

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from srlhip import _lib
-from srlhip.device_env import DeviceVecEnv, DeviceVecFrameStack, DeviceVecNormalize
+from srlhip.device_env import DeviceVecEnv, DeviceVecFrameStack, DeviceVecNormalize, first_done_masks
 from srlhip.envs import ENV_CLASSES
 
 
@@ -74,7 +74,7 @@ class ARSModel(object):
 
     @staticmethod
     def check_fused_arguments(args):
-        """--fused-rollout against the rest of the arguments; raises ValueError before any env is built."""
+        """--fused-rollout against the rest of the arguments; raises ValueError before any env is built.  (CMAESModel's too.)"""
         if not getattr(args, "fused_rollout", False):
             return
         if not (getattr(args, "deterministic", False) or getattr(args, "continuous_actions", False)):
@@ -92,10 +92,8 @@ class ARSModel(object):
         """The reference's return rule (ars.py:178-180) on [T][N] reward / done planes: a step's reward counts only while the env
         has not reported done, the reporting step included -> (float64 returns [N], number of rows in which some env was still live
         when it acted)."""
-        d = (done & 1) != 0                                                            # (bit 1: srlhip_config.info_bits)
-        seen = torch.cumsum(d.to(torch.int32), 0) > 0                                  # done at this row or an earlier one
+        seen, before = first_done_masks(done)
         ret = (reward.to(torch.float64) * (~seen).to(torch.float64)).sum(0)
-        before = torch.cat([torch.zeros_like(seen[:1]), seen[:-1]], 0)               # done at an EARLIER row: frozen when it acts
         return ret, (~before).any(dim=1).sum()
 
     def evaluate_fused(self, env, M, delta, T):

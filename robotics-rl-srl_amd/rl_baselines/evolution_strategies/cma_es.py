@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from srlhip import _lib
-from srlhip.device_env import DeviceVecEnv, DeviceVecFrameStack, DeviceVecNormalize
+from srlhip.device_env import DeviceVecEnv, DeviceVecFrameStack, DeviceVecNormalize, first_done_masks
 from srlhip.envs import ENV_CLASSES
 from rl_baselines.evolution_strategies.ars import ARSModel
 
@@ -153,30 +153,17 @@ class CMAESModel(object):
 
     HIDDEN = 100                        # MLPPolicyPytorch(obs_dim, [100], n_actions)
 
-    @staticmethod
-    def check_fused_arguments(args):
-        """--fused-rollout against the rest of the arguments; raises ValueError before any env is built."""
-        if not getattr(args, "fused_rollout", False):
-            return
-        if not (getattr(args, "deterministic", False) or getattr(args, "continuous_actions", False)):
-            raise ValueError("--fused-rollout needs --deterministic with discrete actions (or --continuous-actions): softmax sampling "
-                             "of the action is not fused (it stays on the per-step path)")
-        if int(getattr(args, "num_stack", 1)) != 1:
-            raise ValueError("--fused-rollout needs --num-stack 1: frame stacking is not fused")
-        if getattr(args, "srl_model", "ground_truth") != "ground_truth":
-            raise ValueError("--fused-rollout needs --srl-model ground_truth")
-        if ENV_CLASSES[args.env].ENV_KIND not in ARSModel.FUSED_EPISODE_LIMIT:
-            raise ValueError("--fused-rollout: {} has no fused policy rollout".format(args.env))
+    # --fused-rollout: the argument rules and the episode limits are ARS's
+    FUSED_EPISODE_LIMIT = ARSModel.FUSED_EPISODE_LIMIT
+    check_fused_arguments = staticmethod(ARSModel.check_fused_arguments)
 
     @staticmethod
     def returns_from_planes(reward, done):
         """The reference's accounting (cma_es.py:127-133) on [T][N] reward / done planes -> (float64 returns [N], int64 live steps
         [N]).  `r[~done] += reward` runs AFTER `done` is updated, so the reward of a member's finishing step is not added; `step +=
         sum(~done)` runs before the step, so a member's live steps are the rows up to and including its first done."""
-        d = (done & 1) != 0                                                            # (bit 1: srlhip_config.info_bits)
-        seen = torch.cumsum(d.to(torch.int32), 0) > 0                                  # done at this row or an earlier one
+        seen, before = first_done_masks(done)
         ret = (reward.to(torch.float64) * (~seen).to(torch.float64)).sum(0)
-        before = torch.cat([torch.zeros_like(seen[:1]), seen[:-1]], 0)               # done at an EARLIER row: frozen when it acts
         return ret, (~before).to(torch.int64).sum(0)
 
     def evaluate_fused(self, env, population, T):
@@ -234,7 +221,7 @@ class CMAESModel(object):
         env = self.makeEnv(args, env_kwargs=env_kwargs)
         args.__dict__.update(train_kwargs or {})
         fused = bool(getattr(args, "fused_rollout", False))
-        fused_T = ARSModel.FUSED_EPISODE_LIMIT.get(ENV_CLASSES[args.env].ENV_KIND, 0) + 1
+        fused_T = self.FUSED_EPISODE_LIMIT.get(ENV_CLASSES[args.env].ENV_KIND, 0) + 1
         continuous = bool(getattr(args, "continuous_actions", False))
         none_rows = continuous and ENV_CLASSES[args.env].ENV_KIND >= _lib.ENV_KUKA_BUTTON      # finished members: `None` (Kuka)
         action_space = int(np.prod(env.action_space.shape)) if continuous else env.action_space.n

@@ -298,20 +298,25 @@ class Handle(object):
                     "srlhip_step")
         return out
 
-    def rollout(self, T, actions=None, want=("obs", "reward", "done", "actions"), out=None):
+    def _new_planes(self, T, want, actions=True):
+        """the host planes of a rollout call: (obs, reward, done, actions), a zeroed [T][N] array for every name in `want`, else None"""
         n = self.num_envs
+        obs = self.new_obs(T) if "obs" in want else None
+        rew = np.zeros((T, n), np.float32) if "reward" in want else None
+        done = np.zeros((T, n), np.uint8) if "done" in want else None
+        act = None
+        if actions and "actions" in want:
+            act = np.zeros((T, n), np.int32) if self.cfg.is_discrete else np.zeros((T, n, self.action_dim), np.float32)
+        return obs, rew, done, act
+
+    def rollout(self, T, actions=None, want=("obs", "reward", "done", "actions"), out=None):
         if self.cfg.io_device:
             obs, rew, done, act = out
             self._check(self._lib.srlhip_rollout(self._h, T, _ptr(actions), _ptr(obs), _ptr(rew), _ptr(done),
                                                  _ptr(act)), "srlhip_rollout")
             return out
         a = None if actions is None else self.action_array(actions, T)
-        obs = self.new_obs(T) if "obs" in want else None
-        rew = np.zeros((T, n), np.float32) if "reward" in want else None
-        done = np.zeros((T, n), np.uint8) if "done" in want else None
-        act = None
-        if a is None and "actions" in want:
-            act = np.zeros((T, n), np.int32) if self.cfg.is_discrete else np.zeros((T, n, self.action_dim), np.float32)
+        obs, rew, done, act = self._new_planes(T, want, actions=a is None)
         self._check(self._lib.srlhip_rollout(self._h, T, _ptr(a), _ptr(obs), _ptr(rew), _ptr(done), _ptr(act)),
                     "srlhip_rollout")
         return {"obs": obs, "reward": rew, "done": done, "actions": a if a is not None else act}
@@ -321,6 +326,39 @@ class Handle(object):
         a = self.num_actions if self.cfg.is_discrete else self.action_dim
         return ((self.num_envs,) if per_env else ()) + (self.obs_dim, a)
 
+    def _policy_struct(self, cls, per_env, freeze_after_done, obs_mean, obs_std, clip_obs):
+        """a LinearPolicy / MlpPolicy with the fields the two structs share filled in (pointers: _rollout_policy_call)"""
+        pol = cls()
+        pol.struct_size, pol.per_env, pol.freeze_after_done = ctypes.sizeof(cls), int(bool(per_env)), int(bool(freeze_after_done))
+        assert (obs_mean is None) == (obs_std is None), "obs_mean and obs_std come together"
+        pol.normalize, pol.clip_obs = int(obs_mean is not None), float(clip_obs)
+        return pol
+
+    def _rollout_policy_call(self, name, T, pol, field, params, dtype, shape, obs_mean, obs_std, want, out):
+        """the ABI call `name` with `pol`, whose parameter block is the struct field `field`: `params` as `dtype` of `shape` (None:
+        unchecked) on a host-pointer handle, a raw device pointer on a device-pointer one"""
+        fn = getattr(self._lib, name)
+        if self.cfg.io_device:
+            setattr(pol, field, params)
+            pol.obs_mean, pol.obs_std = obs_mean, obs_std
+            obs, rew, done, act = out
+            self._check(fn(self._h, T, ctypes.byref(pol), _ptr(obs or None), _ptr(rew or None), _ptr(done or None),
+                           _ptr(act or None)), name)
+            return out
+        w = np.ascontiguousarray(params, dtype=dtype)
+        assert shape is None or w.shape == shape, (w.shape, shape)
+        keep = [w]
+        setattr(pol, field, w.ctypes.data)
+        if obs_mean is not None:
+            mean, std = np.ascontiguousarray(obs_mean, dtype=np.float64), np.ascontiguousarray(obs_std, dtype=np.float64)
+            assert mean.shape == (self.obs_dim,) and std.shape == (self.obs_dim,), (mean.shape, std.shape)
+            keep += [mean, std]
+            pol.obs_mean, pol.obs_std = mean.ctypes.data, std.ctypes.data
+        obs, rew, done, act = self._new_planes(T, want)
+        self._check(fn(self._h, T, ctypes.byref(pol), _ptr(obs), _ptr(rew), _ptr(done), _ptr(act)), name)
+        del keep
+        return {"obs": obs, "reward": rew, "done": done, "actions": act}
+
     def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0,
                        want=("obs", "reward", "done", "actions"), out=None):
         """srlhip_rollout_policy: T fused steps whose actions a linear policy picks inside the kernel from the env's own current
@@ -329,36 +367,9 @@ class Handle(object):
         neither): the observation is normalised and clipped to +-clip_obs first, with these statistics frozen for the call.
         Host-pointer handles take numpy arrays and return a dict of [T][N] planes (`want` selects them); device-pointer handles take
         raw device pointers for weights / mean / std and `out` = (obs, reward, done, actions) pointers (0 / None = skip)."""
-        n = self.num_envs
-        pol = LinearPolicy()
-        pol.struct_size, pol.per_env, pol.freeze_after_done = ctypes.sizeof(LinearPolicy), int(bool(per_env)), int(bool(freeze_after_done))
-        assert (obs_mean is None) == (obs_std is None), "obs_mean and obs_std come together"
-        pol.normalize, pol.clip_obs = int(obs_mean is not None), float(clip_obs)
-        if self.cfg.io_device:
-            pol.weights, pol.obs_mean, pol.obs_std = weights, obs_mean, obs_std
-            obs, rew, done, act = out
-            self._check(self._lib.srlhip_rollout_policy(self._h, T, ctypes.byref(pol), _ptr(obs or None), _ptr(rew or None),
-                                                        _ptr(done or None), _ptr(act or None)), "srlhip_rollout_policy")
-            return out
-        w = np.ascontiguousarray(weights, dtype=np.float64)
-        assert w.shape == self.policy_shape(per_env), (w.shape, self.policy_shape(per_env))
-        keep = [w]
-        pol.weights = w.ctypes.data
-        if obs_mean is not None:
-            mean, std = np.ascontiguousarray(obs_mean, dtype=np.float64), np.ascontiguousarray(obs_std, dtype=np.float64)
-            assert mean.shape == (self.obs_dim,) and std.shape == (self.obs_dim,), (mean.shape, std.shape)
-            keep += [mean, std]
-            pol.obs_mean, pol.obs_std = mean.ctypes.data, std.ctypes.data
-        obs = self.new_obs(T) if "obs" in want else None
-        rew = np.zeros((T, n), np.float32) if "reward" in want else None
-        done = np.zeros((T, n), np.uint8) if "done" in want else None
-        act = None
-        if "actions" in want:
-            act = np.zeros((T, n), np.int32) if self.cfg.is_discrete else np.zeros((T, n, self.action_dim), np.float32)
-        self._check(self._lib.srlhip_rollout_policy(self._h, T, ctypes.byref(pol), _ptr(obs), _ptr(rew), _ptr(done), _ptr(act)),
-                    "srlhip_rollout_policy")
-        del keep
-        return {"obs": obs, "reward": rew, "done": done, "actions": act}
+        pol = self._policy_struct(LinearPolicy, per_env, freeze_after_done, obs_mean, obs_std, clip_obs)
+        return self._rollout_policy_call("srlhip_rollout_policy", T, pol, "weights", weights, np.float64, self.policy_shape(per_env),
+                                         obs_mean, obs_std, want, out)
 
     def mlp_param_count(self, hidden):
         """P of rollout_mlp_policy: H D + H + A H + A with D = obs_dim, A = num_actions (discrete) or action_dim"""
@@ -371,38 +382,13 @@ class Handle(object):
         [num_envs][P] (per_env) or [P], P = mlp_param_count(hidden), in nn.Module.parameters() order (fc_in.weight [H][D],
         fc_in.bias [H], fc_out.weight [A][H], fc_out.bias [A]) — a CMA-ES population as it is.  Everything else as rollout_policy
         (device-pointer handles: raw device pointers and `out`)."""
-        n = self.num_envs
-        pol = MlpPolicy()
-        pol.struct_size, pol.per_env, pol.freeze_after_done = ctypes.sizeof(MlpPolicy), int(bool(per_env)), int(bool(freeze_after_done))
-        assert (obs_mean is None) == (obs_std is None), "obs_mean and obs_std come together"
-        pol.normalize, pol.clip_obs, pol.hidden, pol.reserved = int(obs_mean is not None), float(clip_obs), int(hidden), 0
-        if self.cfg.io_device:
-            pol.params, pol.obs_mean, pol.obs_std = params, obs_mean, obs_std
-            obs, rew, done, act = out
-            self._check(self._lib.srlhip_rollout_mlp_policy(self._h, T, ctypes.byref(pol), _ptr(obs or None), _ptr(rew or None),
-                                                            _ptr(done or None), _ptr(act or None)), "srlhip_rollout_mlp_policy")
-            return out
-        w = np.ascontiguousarray(params, dtype=np.float32)
-        if 1 <= int(hidden) <= 128:                    # (outside: the library refuses by name)
-            shape = ((n,) if per_env else ()) + (self.mlp_param_count(int(hidden)),)
-            assert w.shape == shape, (w.shape, shape)
-        keep = [w]
-        pol.params = w.ctypes.data
-        if obs_mean is not None:
-            mean, std = np.ascontiguousarray(obs_mean, dtype=np.float64), np.ascontiguousarray(obs_std, dtype=np.float64)
-            assert mean.shape == (self.obs_dim,) and std.shape == (self.obs_dim,), (mean.shape, std.shape)
-            keep += [mean, std]
-            pol.obs_mean, pol.obs_std = mean.ctypes.data, std.ctypes.data
-        obs = self.new_obs(T) if "obs" in want else None
-        rew = np.zeros((T, n), np.float32) if "reward" in want else None
-        done = np.zeros((T, n), np.uint8) if "done" in want else None
-        act = None
-        if "actions" in want:
-            act = np.zeros((T, n), np.int32) if self.cfg.is_discrete else np.zeros((T, n, self.action_dim), np.float32)
-        self._check(self._lib.srlhip_rollout_mlp_policy(self._h, T, ctypes.byref(pol), _ptr(obs), _ptr(rew), _ptr(done), _ptr(act)),
-                    "srlhip_rollout_mlp_policy")
-        del keep
-        return {"obs": obs, "reward": rew, "done": done, "actions": act}
+        pol = self._policy_struct(MlpPolicy, per_env, freeze_after_done, obs_mean, obs_std, clip_obs)
+        pol.hidden, pol.reserved = int(hidden), 0
+        shape = None                                   # (hidden outside 1..128: the library refuses by name)
+        if 1 <= int(hidden) <= 128:
+            shape = ((self.num_envs,) if per_env else ()) + (self.mlp_param_count(int(hidden)),)
+        return self._rollout_policy_call("srlhip_rollout_mlp_policy", T, pol, "params", params, np.float32, shape,
+                                         obs_mean, obs_std, want, out)
 
     def get_state(self, field):
         dtype, k = _FIELD_SHAPES[field]

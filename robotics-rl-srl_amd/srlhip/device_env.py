@@ -9,6 +9,8 @@ Stream discipline: the handle owns a HIP stream (srlhip_stream).  `env.torch_str
 torch.cuda.ExternalStream; code that runs under `with torch.cuda.stream(env.torch_stream):` is ordered with the
 stepper's kernels and needs no host synchronisation at all.  When the caller is on another stream, step()/reset()
 fall back to two host-side stream synchronisations per call."""
+import functools
+
 import numpy as np
 import torch
 
@@ -17,6 +19,14 @@ from .envs import ENV_CLASSES, OBS_MODES
 from .gym_compat import Box, Discrete
 
 from .vec_env import RNG_MODES, default_rng_mode
+
+
+def first_done_masks(done):
+    """[T][N] done plane -> bool planes (seen, before): the env has reported done at this row or an earlier one / at an EARLIER row
+    (`~before`: the rows up to and including its first done — from the next one on a freeze_after_done env acts `None`)"""
+    d = (done & 1) != 0                                                            # (bit 1: srlhip_config.info_bits)
+    seen = torch.cumsum(d.to(torch.int32), 0) > 0
+    return seen, torch.cat([torch.zeros_like(seen[:1]), seen[:-1]], 0)
 
 
 class DeviceVecEnv(object):
@@ -75,41 +85,11 @@ class DeviceVecEnv(object):
             self.h.sync()
         return self.obs, self.rewards, self.dones
 
-    def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0):
-        """srlhip_rollout_policy on tensors: T fused steps whose actions the linear policy `weights` (float64 tensor
-        [N][obs_dim][A], or [obs_dim][A] with per_env=False) picks inside the kernel from each env's own current observation.
-        obs_mean / obs_std: float64 tensors [obs_dim], frozen for the call.  Enqueue-only on the env's stream (like step());
-        returns {"obs", "reward", "done", "actions"}: new [T][N]... tensors of the RAW observations, rewards, dones and the
-        actions taken.  The env's own obs / rewards / dones tensors are left as they were."""
+    def _rollout_policy(self, call, T, params, dtype, shape, per_env, freeze_after_done, obs_mean, obs_std, clip_obs):
+        """`call` (a bound Handle.rollout_policy / rollout_mlp_policy, less its leading T and parameter pointer) on tensors: `params`
+        of `dtype` and `shape`, new output planes allocated on the env's stream, enqueue-only when the caller is on that stream"""
         n, dev = self.num_envs, self.device
-        assert weights.is_cuda and weights.dtype == torch.float64 and weights.is_contiguous(), (weights.dtype, weights.device)
-        assert tuple(weights.shape) == self.h.policy_shape(per_env), (tuple(weights.shape), self.h.policy_shape(per_env))
-        assert (obs_mean is None) == (obs_std is None), "obs_mean and obs_std come together"
-        for x in (obs_mean, obs_std):
-            assert x is None or (x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() and tuple(x.shape) == (self.h.obs_dim,))
-        ordered = self._on_env_stream()
-        if not ordered:
-            torch.cuda.current_stream(dev).synchronize()
-        with torch.cuda.stream(self.torch_stream):         # the planes are allocated (and later freed) on the stream that fills them
-            out = {"obs": torch.empty((T, n, self.h.obs_dim), dtype=torch.float32, device=dev),
-                   "reward": torch.empty((T, n), dtype=torch.float32, device=dev),
-                   "done": torch.empty((T, n), dtype=torch.uint8, device=dev),
-                   "actions": torch.empty((T, n), dtype=torch.int32, device=dev) if self.cfg.is_discrete
-                   else torch.empty((T, n, self.h.action_dim), dtype=torch.float32, device=dev)}
-        self.h.rollout_policy(T, weights.data_ptr(), per_env, freeze_after_done,
-                              None if obs_mean is None else obs_mean.data_ptr(), None if obs_std is None else obs_std.data_ptr(), clip_obs,
-                              out=tuple(out[k].data_ptr() for k in ("obs", "reward", "done", "actions")))
-        if not ordered:
-            self.h.sync()
-        return out
-
-    def rollout_mlp_policy(self, T, params, hidden, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0):
-        """srlhip_rollout_mlp_policy on tensors: rollout_policy with a one-hidden-layer ReLU MLP.  `params`: float32 CUDA tensor
-        [N][P] (or [P] with per_env=False), P = h.mlp_param_count(hidden), nn.Module.parameters() order.  Enqueue-only; returns
-        the same dict of new [T][N]... tensors."""
-        n, dev = self.num_envs, self.device
-        assert params.is_cuda and params.dtype == torch.float32 and params.is_contiguous(), (params.dtype, params.device)
-        shape = ((n,) if per_env else ()) + (self.h.mlp_param_count(int(hidden)),)
+        assert params.is_cuda and params.dtype == dtype and params.is_contiguous(), (params.dtype, params.device)
         assert tuple(params.shape) == shape, (tuple(params.shape), shape)
         assert (obs_mean is None) == (obs_std is None), "obs_mean and obs_std come together"
         for x in (obs_mean, obs_std):
@@ -123,12 +103,29 @@ class DeviceVecEnv(object):
                    "done": torch.empty((T, n), dtype=torch.uint8, device=dev),
                    "actions": torch.empty((T, n), dtype=torch.int32, device=dev) if self.cfg.is_discrete
                    else torch.empty((T, n, self.h.action_dim), dtype=torch.float32, device=dev)}
-        self.h.rollout_mlp_policy(T, params.data_ptr(), hidden, per_env, freeze_after_done,
-                                  None if obs_mean is None else obs_mean.data_ptr(), None if obs_std is None else obs_std.data_ptr(), clip_obs,
-                                  out=tuple(out[k].data_ptr() for k in ("obs", "reward", "done", "actions")))
+        call(T, params.data_ptr(), per_env=per_env, freeze_after_done=freeze_after_done,
+             obs_mean=None if obs_mean is None else obs_mean.data_ptr(), obs_std=None if obs_std is None else obs_std.data_ptr(),
+             clip_obs=clip_obs, out=tuple(out[k].data_ptr() for k in ("obs", "reward", "done", "actions")))
         if not ordered:
             self.h.sync()
         return out
+
+    def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0):
+        """srlhip_rollout_policy on tensors: T fused steps whose actions the linear policy `weights` (float64 tensor
+        [N][obs_dim][A], or [obs_dim][A] with per_env=False) picks inside the kernel from each env's own current observation.
+        obs_mean / obs_std: float64 tensors [obs_dim], frozen for the call.  Enqueue-only on the env's stream (like step());
+        returns {"obs", "reward", "done", "actions"}: new [T][N]... tensors of the RAW observations, rewards, dones and the
+        actions taken.  The env's own obs / rewards / dones tensors are left as they were."""
+        return self._rollout_policy(self.h.rollout_policy, T, weights, torch.float64, self.h.policy_shape(per_env),
+                                    per_env, freeze_after_done, obs_mean, obs_std, clip_obs)
+
+    def rollout_mlp_policy(self, T, params, hidden, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0):
+        """srlhip_rollout_mlp_policy on tensors: rollout_policy with a one-hidden-layer ReLU MLP.  `params`: float32 CUDA tensor
+        [N][P] (or [P] with per_env=False), P = h.mlp_param_count(hidden), nn.Module.parameters() order.  Enqueue-only; returns
+        the same dict of new [T][N]... tensors."""
+        shape = ((self.num_envs,) if per_env else ()) + (self.h.mlp_param_count(int(hidden)),)
+        return self._rollout_policy(functools.partial(self.h.rollout_mlp_policy, hidden=hidden), T, params, torch.float32, shape,
+                                    per_env, freeze_after_done, obs_mean, obs_std, clip_obs)
 
     def episode_stats(self):
         return self.h.episode_stats()
@@ -178,17 +175,19 @@ class DeviceVecFrameStack(DeviceVecEnvWrapper):
         obs, rew, done = self.venv.step(actions)
         return self._push(obs, done), rew, done
 
+    def _pass_through(self, name, *args, **kw):
+        """The fused policy rollouts see single frames: only the trivial stack passes through."""
+        if self.n_stack > 1:
+            raise NotImplementedError("{}: frame stacking (n_stack > 1) is not fused; use the per-step path".format(name))
+        return getattr(self.venv, name)(*args, **kw)
+
     def rollout_policy(self, T, weights, **kw):
         """The fused policy rollout sees single frames: only the trivial stack passes through."""
-        if self.n_stack > 1:
-            raise NotImplementedError("rollout_policy: frame stacking (n_stack > 1) is not fused; use the per-step path")
-        return self.venv.rollout_policy(T, weights, **kw)
+        return self._pass_through("rollout_policy", T, weights, **kw)
 
     def rollout_mlp_policy(self, T, params, hidden, **kw):
         """As rollout_policy: only the trivial stack passes through."""
-        if self.n_stack > 1:
-            raise NotImplementedError("rollout_mlp_policy: frame stacking (n_stack > 1) is not fused; use the per-step path")
-        return self.venv.rollout_mlp_policy(T, params, hidden, **kw)
+        return self._pass_through("rollout_mlp_policy", T, params, hidden, **kw)
 
 
 class RunningMeanStd(object):
@@ -265,46 +264,36 @@ class DeviceVecNormalize(DeviceVecEnvWrapper):
     def get_original_obs(self):
         return self.old_obs
 
-    def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False):
-        """The wrapped env's fused policy rollout on NORMALISED observations: the current statistics (sqrt(var + eps) as std,
-        clip_obs) are handed to the kernel and stay frozen for the whole call.  With training = False this equals the per-step
-        path.  With training = True the statistics are then updated ONCE, from the returned raw observation planes — only rows up
-        to and including each env's first done when freeze_after_done is set (all rows otherwise): a different schedule than
-        step()'s update before every action.  Returns the raw planes; rewards are not normalised."""
+    def _rollout_frozen(self, call, *args, per_env=True, freeze_after_done=False):
+        """`call` (the wrapped env's rollout_policy / rollout_mlp_policy) on NORMALISED observations: the current statistics
+        (sqrt(var + eps) as std, clip_obs) are handed to the kernel and stay frozen for the whole call.  With training = False this
+        equals the per-step path.  With training = True the statistics are then updated ONCE, from the returned raw observation
+        planes — only rows up to and including each env's first done when freeze_after_done is set (all rows otherwise): a different
+        schedule than step()'s update before every action.  Returns the raw planes; rewards are not normalised."""
         if not self.norm_obs:
-            return self.venv.rollout_policy(T, weights, per_env=per_env, freeze_after_done=freeze_after_done)
+            return call(*args, per_env=per_env, freeze_after_done=freeze_after_done)
         mean = self.obs_rms.mean.reshape(-1).contiguous()
         std = torch.sqrt(self.obs_rms.var + self.epsilon).reshape(-1).contiguous()
-        out = self.venv.rollout_policy(T, weights, per_env=per_env, freeze_after_done=freeze_after_done, obs_mean=mean, obs_std=std,
-                                       clip_obs=self.clip_obs)
+        out = call(*args, per_env=per_env, freeze_after_done=freeze_after_done, obs_mean=mean, obs_std=std, clip_obs=self.clip_obs)
         if self.training:
             obs = out["obs"]
             if freeze_after_done:
-                done = ((out["done"] & 1) != 0).to(torch.int32)                       # (bit 1: srlhip_config.info_bits)
-                live = (torch.cumsum(done, 0) - done) == 0                            # no done BEFORE this row
-                self.obs_rms.update_weighted(obs, live)                               # (no gather: the call stays enqueue-only)
+                self.obs_rms.update_weighted(obs, ~first_done_masks(out["done"])[1])  # (no gather: the call stays enqueue-only)
             else:
                 self.obs_rms.update(obs.reshape(-1, obs.shape[-1]))
         return out
 
+    def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False):
+        """The wrapped env's fused policy rollout on NORMALISED observations: the current statistics are handed to the kernel and
+        stay frozen for the whole call; with training = True they are updated ONCE afterwards from the returned raw observation
+        planes — a different schedule than step()'s update before every action (_rollout_frozen has the details).  Returns the
+        raw planes; rewards are not normalised."""
+        return self._rollout_frozen(self.venv.rollout_policy, T, weights, per_env=per_env, freeze_after_done=freeze_after_done)
+
     def rollout_mlp_policy(self, T, params, hidden, per_env=True, freeze_after_done=False):
         """rollout_policy's schedule for the MLP policy: the current statistics are frozen for the call and, with training = True,
         updated once afterwards from the live rows of the returned raw observation planes."""
-        if not self.norm_obs:
-            return self.venv.rollout_mlp_policy(T, params, hidden, per_env=per_env, freeze_after_done=freeze_after_done)
-        mean = self.obs_rms.mean.reshape(-1).contiguous()
-        std = torch.sqrt(self.obs_rms.var + self.epsilon).reshape(-1).contiguous()
-        out = self.venv.rollout_mlp_policy(T, params, hidden, per_env=per_env, freeze_after_done=freeze_after_done, obs_mean=mean,
-                                           obs_std=std, clip_obs=self.clip_obs)
-        if self.training:
-            obs = out["obs"]
-            if freeze_after_done:
-                done = ((out["done"] & 1) != 0).to(torch.int32)                       # (bit 1: srlhip_config.info_bits)
-                live = (torch.cumsum(done, 0) - done) == 0                            # no done BEFORE this row
-                self.obs_rms.update_weighted(obs, live)
-            else:
-                self.obs_rms.update(obs.reshape(-1, obs.shape[-1]))
-        return out
+        return self._rollout_frozen(self.venv.rollout_mlp_policy, T, params, hidden, per_env=per_env, freeze_after_done=freeze_after_done)
 
     def reset(self):
         obs = self.venv.reset()

@@ -468,64 +468,51 @@ class HipVecEnv(object):
         self.step_async(actions)
         return self.step_wait()
 
-    def rollout(self, n_steps, actions=None):
-        """Fused device-side rollout (no per-step host round trip): dict of [T][N] planes, global env-id order.  With several shards
-        every GPU runs its rollout at the same time (one host thread per shard: the foreign calls release the GIL).  `None` actions as in
-        step(): -1, or on a Kuka env with continuous actions `None` / a row of NaNs."""
+    def _fused(self, prepare, run):
+        """One fused call on every shard.  After the encoder refusal and the pending step: x = prepare(sharded) once — the per-shard
+        argument, as given for the only shard, as an array to be cut otherwise — then run(handle, x, rows), rows = the slice of global
+        env ids the handle serves (None: the only shard, all of x).  With several shards every GPU runs at the same time (one host
+        thread per shard: the foreign calls release the GIL) -> the shards' [T][n] planes as one dict of [T][N] planes, global
+        env-id order."""
         if self._enc is not None:
             raise NotImplementedError("fused rollouts with a learned SRL encoder: use srlhip.pixel_env.PixelStateVecEnv")
         if self._pending:
             self.step_wait()
-        if actions is not None and not self.cfg.is_discrete:
-            actions = _lib.none_rows(actions, self._h.action_dim, 2)
         if len(self._shards) == 1:
-            return self._h.rollout(n_steps, actions=actions)
-        acts = None if actions is None else np.asarray(actions)
-
-        def run(sh):
-            return sh.h.rollout(n_steps, actions=None if acts is None else np.ascontiguousarray(acts[:, sh.lo:sh.hi]))
+            return run(self._h, prepare(False), None)
+        x = prepare(True)
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(len(self._shards)) as pool:
-            parts = list(pool.map(run, self._shards))
+            parts = list(pool.map(lambda sh: run(sh.h, x, slice(sh.lo, sh.hi)), self._shards))
         return {k: (None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=1)) for k in parts[0]}
+
+    def rollout(self, n_steps, actions=None):
+        """Fused device-side rollout (no per-step host round trip): dict of [T][N] planes, global env-id order; several shards run at
+        the same time (_fused).  `None` actions as in step(): -1, or on a Kuka env with continuous actions `None` / a row of NaNs."""
+        def prepare(sharded):
+            a = actions
+            if a is not None and not self.cfg.is_discrete:
+                a = _lib.none_rows(a, self._h.action_dim, 2)
+            return np.asarray(a) if sharded and a is not None else a
+        return self._fused(prepare, lambda h, a, rows: h.rollout(
+            n_steps, actions=a if a is None or rows is None else np.ascontiguousarray(a[:, rows])))
+
+    def _fused_policy(self, params, dtype, per_env, call):
+        """call(handle, params) through _fused: each shard gets its rows of per-env `params` (an array of `dtype`)"""
+        return self._fused(lambda sharded: np.asarray(params, dtype=dtype) if sharded else params,
+                           lambda h, w, rows: call(h, np.ascontiguousarray(w[rows]) if per_env and rows is not None else w))
 
     def rollout_policy(self, n_steps, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0):
         """Fused rollout under a linear policy chosen inside the kernel (_lib.Handle.rollout_policy): dict of [T][N] planes, global
         env-id order.  Shards like rollout(): each shard gets its slice of per-env weights and runs on its own GPU at the same time."""
-        if self._enc is not None:
-            raise NotImplementedError("fused rollouts with a learned SRL encoder: use srlhip.pixel_env.PixelStateVecEnv")
-        if self._pending:
-            self.step_wait()
         kw = dict(per_env=per_env, freeze_after_done=freeze_after_done, obs_mean=obs_mean, obs_std=obs_std, clip_obs=clip_obs)
-        if len(self._shards) == 1:
-            return self._h.rollout_policy(n_steps, weights, **kw)
-        w = np.asarray(weights, dtype=np.float64)
-
-        def run(sh):
-            return sh.h.rollout_policy(n_steps, np.ascontiguousarray(w[sh.lo:sh.hi]) if per_env else w, **kw)
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(len(self._shards)) as pool:
-            parts = list(pool.map(run, self._shards))
-        return {k: (None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=1)) for k in parts[0]}
+        return self._fused_policy(weights, np.float64, per_env, lambda h, w: h.rollout_policy(n_steps, w, **kw))
 
     def rollout_mlp_policy(self, n_steps, params, hidden, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0):
         """rollout_policy with a one-hidden-layer ReLU MLP (_lib.Handle.rollout_mlp_policy): each shard gets its rows of per-env
         `params` (float32 [N][P])."""
-        if self._enc is not None:
-            raise NotImplementedError("fused rollouts with a learned SRL encoder: use srlhip.pixel_env.PixelStateVecEnv")
-        if self._pending:
-            self.step_wait()
         kw = dict(per_env=per_env, freeze_after_done=freeze_after_done, obs_mean=obs_mean, obs_std=obs_std, clip_obs=clip_obs)
-        if len(self._shards) == 1:
-            return self._h.rollout_mlp_policy(n_steps, params, hidden, **kw)
-        w = np.asarray(params, dtype=np.float32)
-
-        def run(sh):
-            return sh.h.rollout_mlp_policy(n_steps, np.ascontiguousarray(w[sh.lo:sh.hi]) if per_env else w, hidden, **kw)
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(len(self._shards)) as pool:
-            parts = list(pool.map(run, self._shards))
-        return {k: (None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=1)) for k in parts[0]}
+        return self._fused_policy(params, np.float32, per_env, lambda h, w: h.rollout_mlp_policy(n_steps, w, hidden, **kw))
 
     def get_images(self):
         if self._pending:

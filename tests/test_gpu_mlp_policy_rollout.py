@@ -386,6 +386,7 @@ def test_refusals_name_what_they_refuse_and_leave_the_handle_usable(name, kind, 
     W = np.zeros((n, 4096), np.float32)               # never read
     assert _call(h, 4, _pol(W, 100)) == -95
     assert word in h.last_error() and "rollout_mlp_policy" in h.last_error(), h.last_error()
+    assert h.last_error().startswith("rollout_mlp_policy:"), h.last_error()
     again = h.reset(host_rand=host_rand)              # the refusal left the handle usable
     assert again.shape == before.shape
     if cfg.rng_mode != _lib.RNG_HOST:
@@ -405,6 +406,7 @@ def test_two_button_joint_space_actions_are_refused_by_name():
     W = np.zeros((n, 4096), np.float32)               # never read
     assert _call(h, 4, _pol(W, 100)) == -95
     assert "Kuka2Button" in h.last_error() and "joint-space" in h.last_error() and "rollout_mlp_policy" in h.last_error(), h.last_error()
+    assert h.last_error().startswith("rollout_mlp_policy:"), h.last_error()
     assert h.reset().shape == before.shape            # the refusal left the handle usable
     h.close()
 

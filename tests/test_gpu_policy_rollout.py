@@ -423,6 +423,7 @@ def test_refusals_name_what_they_refuse_and_leave_the_handle_usable(name, kind, 
     W = np.zeros((n, 32, 8))                          # larger than any policy shape: never read
     assert _call(h, 4, _pol(W)) == -95
     assert word in h.last_error(), h.last_error()
+    assert h.last_error().startswith("rollout_policy:"), h.last_error()
     again = h.reset(host_rand=host_rand)              # the refusal left the handle usable
     assert again.shape == before.shape
     if cfg.rng_mode != _lib.RNG_HOST:
