@@ -222,6 +222,7 @@ int srlhip_rollout(srlhip_handle h, int32_t T, const void *actions_TN,
  * observation of the state the call found, afterwards the one the previous step produced — after an auto-reset the new episode's
  * first one):  score_a = sum_d (double)x_d * W[d][a] in float64, d ascending, x = o or its frozen VecNormalize image;
  * discrete actions: a = argmax, lowest index wins a tie; continuous actions: the row (float)score_a, not clipped.
+ * (A score that is zero carries the IEEE sign of that sum: -0.0 where every product x_d * W[d][a] is -0.0, else +0.0.)
  * Everything behind the action is srlhip_rollout's step.  act_out_TN receives the actions taken (the `None` rows of frozen envs
  * included); any output may be NULL.
  * Needs cfg.auto_reset, a device RNG mode, ground-truth observations and a MobileRobot env, KukaButtonGymEnv, KukaMovingButtonGymEnv
@@ -253,6 +254,8 @@ int srlhip_rollout_policy(srlhip_handle h, int32_t T, const srlhip_linear_policy
  * l, l+16, ... in that order and the 16 partial sums are then reduced in a fixed pattern — so scores agree with any other summation
  * order only to float64 rounding (|error| <= 2^-46 * (|b2_a| + sum_j |W2[a][j]| * (|b1_j| + sum_d |W1[j][d] * x_d|)) for H <= 128),
  * but the order is FIXED: two calls on equal state and parameters give equal bits.
+ * Fifteen of the sixteen partial sums start from +0.0 (fc_out's bias sits with lane 0), so a score that is zero is +0.0 whatever the
+ * signs of b2_a and of the zero products.
  * Action selection (strict argmax, lowest index first / the row (float)score_a), freeze_after_done, auto-reset, NULL output planes,
  * chunked calls, graph capture and the parked resident kernel are srlhip_rollout_policy's, and so is the set of refusals
  * (SRLHIP_ENOTSUP naming the cause: joints / joints_position / raw_pixels observations, KukaRandButtonGymEnv, the lumped model,

@@ -51,7 +51,12 @@ def numpy_policy(prev_obs, W, per_env, mean=None, std=None, clip=10.0):
     return score, np.abs(terms).sum(2)
 
 
+POLICY_TOL = 2.0 ** -50      # at most 3 products and 2 additions in float64: gamma_3 <= 3 * 2^-53; twice that (two scores are compared) < 2^-50
+
+
 def check_policy(h, obs0, out, W, per_env, freeze, mean=None, std=None, clip=10.0):
+    """tol_a = 2^-50 sum_d |x_d W[d][a]|.  A discrete action a has score[a] >= max(score) - tol_a, and no lower index k has
+    score[k] >= score[a] + tol_a; a continuous one lies in [f32(score - tol), f32(score + tol)] — for almost every entry one float."""
     n = h.num_envs
     prev = np.concatenate([obs0[None], out["obs"][:-1]], 0)
     score, scale = numpy_policy(prev, W, per_env, mean, std, clip)
@@ -61,29 +66,28 @@ def check_policy(h, obs0, out, W, per_env, freeze, mean=None, std=None, clip=10.
     if freeze:
         assert frozen.any(), "the case must freeze somebody"
     act = out["actions"]
+    tol = POLICY_TOL * scale                          # [T][N][A]
     if h.cfg.is_discrete:
+        A = score.shape[2]
         assert np.all(act[frozen] == -1), "frozen envs take -1"
-        assert np.all(act[~frozen] >= 0), "nobody is frozen early"
-        order = np.argsort(-score, axis=2, kind="stable")
-        top, second = order[:, :, 0], order[:, :, 1]
-        s1, s2 = np.take_along_axis(score, top[..., None], 2)[..., 0], np.take_along_axis(score, second[..., None], 2)[..., 0]
-        sc = np.maximum(np.take_along_axis(scale, top[..., None], 2)[..., 0], np.take_along_axis(scale, second[..., None], 2)[..., 0])
-        near_tie = (s1 - s2) < 1e-9 * (1.0 + sc)
-        skipped = int((near_tie & ~frozen).sum())
-        print("policy check: {} of {} env-steps skipped as near ties".format(skipped, act.size))
-        assert skipped <= 1e-3 * act.size
-        ok = ~frozen & ~near_tie
-        assert np.array_equal(act[ok], top[ok].astype(np.int32))
+        live = ~frozen
+        assert np.all((act[live] >= 0) & (act[live] < A)), "nobody is frozen early"
+        a = np.where(live, act, 0)
+        sa = np.take_along_axis(score, a[..., None], 2)[..., 0]
+        ta = np.take_along_axis(tol, a[..., None], 2)[..., 0]             # tol_a of the recorded action
+        print("policy check: {} of {} live env-steps off numpy's argmax".format(int((a != score.argmax(2))[live].sum()), int(live.sum())))
+        assert np.all((sa >= score.max(2) - ta)[live]), "score[a] >= max(score) - tol"
+        lower = np.arange(A)[None, None, :] < a[..., None]
+        assert np.all((~lower | (score < (sa + ta)[..., None]))[live]), "no lower index reaches score[a] + tol"
     else:
         if h.cfg.env_kind >= _lib.ENV_KUKA_BUTTON:
             assert np.isnan(act[frozen]).all(), "frozen Kuka envs take a row of NaNs"
         else:
             assert np.all(act[frozen] == 0.0), "frozen MobileRobot envs take a zero row"
-        err = np.abs(act.astype(np.float64) - score.astype(np.float32).astype(np.float64))
-        bound = 1e-6 * (1.0 + scale)
-        err[frozen] = 0.0
-        print("policy check: max |a - f32(score)| / bound = {:.3g}".format(float((err / bound).max())))
-        assert np.all(err[~frozen] <= bound[~frozen])
+        lo, hi = (score - tol).astype(np.float32), (score + tol).astype(np.float32)
+        live = ~frozen
+        print("policy check: {} of {} live entries have more than one float32 in their interval".format(int((lo != hi)[live].sum()), int(live.sum()) * act.shape[2]))
+        assert np.all((lo <= act)[live] & (act <= hi)[live]), "f32(score - tol) <= a <= f32(score + tol)"
     return frozen
 
 
