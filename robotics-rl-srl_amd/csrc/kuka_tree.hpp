@@ -569,10 +569,27 @@ struct TRows {
     double n[GL];              // scaled couplings of the own bank-A row to bank-A rows (n[own] = 0)
     double diag, lo, S, jb;
 };
-// One sweep: 12 motor rows; the button's three rows are decoupled from them here and ride on rows 0..2.
-// A whole sweep is TWO asm statements (an asm statement takes at most 30 operands; the compiler pads every asm boundary with wait
-// states): rows 0..5 with the button rows riding on 0..2, rows 6..11.  39 VALU instructions per sweep.
+// One sweep: 12 motor rows; the button's three rows are decoupled from them here and ride on rows 0..2: 39 VALU instructions and the
+// rows' 12 wait-state nops, 51 issue slots.  The compiler pads every asm boundary with a wait state and an asm statement takes at
+// most 30 operands, so the sweeps differ in how many statements they are:
+//   * the first sweep (no restart mask for row 0 yet) is sweep_free: TWO statements, rows 0..5 with the button rows, rows 6..11;
+//   * the 148 middle sweeps are ONE statement (sweeps_mid): acc (tied: counts twice), cs, 15 couplings and 12 restart masks are
+//     exactly 30 operands, so the row's t lives in a register pair that the text names and the clobber list reserves (SRL_T) and
+//     the trip count in vcc_lo.  The statement holds SRL_FREE_SWEEP_K sweeps and loops over them itself: one s_sub + the branch
+//     per K sweeps instead of two boundary slots per sweep and the compiler's 4x unrolling (profiles/NOTES.md section AH);
+//   * the last sweep also captures u row by row (sweep_last): two statements of six rows.
 struct TEs { double e[NJ]; };          // e[j] = (lane == j), plus the button lanes on 0..2: who restarts its accumulator after row j
+// Home of t inside the one-statement sweeps: a fixed pair, because an operand for it would be the 31st.  v[12:13] is what the allocator
+// had given t in the two-statement form of the configuration-specialised rollout kernel, whose register figures it leaves as they
+// were (403 VGPRs, 4 spills to AGPRs, no scratch).  Correct everywhere (the pair is clobbered, acc and u are early-clobber), but other
+// instantiations pay for it with a few registers: the given-actions twin 407 -> 409 VGPRs and 34 -> 38 spills to AGPRs, the
+// two-button kernel 100 -> 107 SGPR spills; none gains scratch (profiles/NOTES.md section AH).
+#define SRL_T "v[12:13]"
+#define SRL_T_CLOBBER "v12", "v13"
+#define SRL_FREE_SWEEP_K 4             // sweeps per trip of the looping statement (2 measured too: section AH)
+#define SRL_FREE_TRIPS 37
+#define SRL_SWEEP_K SRL_SWEEP SRL_SWEEP SRL_SWEEP SRL_SWEEP
+static_assert(SRL_FREE_SWEEP_K * SRL_FREE_TRIPS == kSolverIters - 2, "the middle sweeps: all but the first and the last");
 SRL_G void sweep_free(const TEs &E, const TRows &r, double &acc, double ep_first) {
 #if SRL_G_DEVICE
     double t;
@@ -599,6 +616,83 @@ SRL_G void sweep_free(const TEs &E, const TRows &r, double &acc, double ep_first
     pgs_row<9>(acc, r.cs, r.n[9], E.e[8]);    pgs_row<10>(acc, r.cs, r.n[10], E.e[9]); pgs_row<11>(acc, r.cs, r.n[11], E.e[10]);
 #endif
 }
+// The middle sweeps (row 0 restarts what row 11 of the sweep before left on lane 11).  ALL: the kSolverIters - 2 of them, looped
+// inside the statement; else one sweep (Kuka2Button runs the second button's rows between the sweeps).  The rows are those of
+// sweep_free instruction for instruction; acc is early-clobber like every output of a statement that writes before it has read all
+// of its inputs; t is written (v_add) two wait states (v_fma, s_nop 0) before its DPP read, in every row of every sweep.
+#define SRL_ROW(J, NJ_, EP) "v_add_f64 " SRL_T ", %1, %0 clamp\n\tv_fma_f64 %0, -%" #EP ", %0, %0\n\ts_nop 0\n\tv_fmac_f64_dpp %0, " SRL_T ", %" #NJ_ " row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"
+#define SRL_ROWB(J, NJ_) "v_fmac_f64_dpp %0, " SRL_T ", %" #NJ_ " row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"
+#define SRL_SWEEP SRL_ROW(0, 2, 17) SRL_ROWB(12, 14) SRL_ROW(1, 3, 18) SRL_ROWB(13, 15) SRL_ROW(2, 4, 19) SRL_ROWB(14, 16) SRL_ROW(3, 5, 20) \
+                  SRL_ROW(4, 6, 21) SRL_ROW(5, 7, 22) SRL_ROW(6, 8, 23) SRL_ROW(7, 9, 24) SRL_ROW(8, 10, 25) SRL_ROW(9, 11, 26) SRL_ROW(10, 12, 27) SRL_ROW(11, 13, 28)
+#define SRL_SWEEP_OPERANDS                                                                                                           \
+    "v"(r.cs), "v"(r.n[0]), "v"(r.n[1]), "v"(r.n[2]), "v"(r.n[3]), "v"(r.n[4]), "v"(r.n[5]), "v"(r.n[6]), "v"(r.n[7]), "v"(r.n[8]),   \
+    "v"(r.n[9]), "v"(r.n[10]), "v"(r.n[11]), "v"(r.n[kBM]), "v"(r.n[kBLo]), "v"(r.n[kBHi]),               /* %1, %2 .. %13, %14 .. %16 */ \
+    "v"(E.e[11]), "v"(E.e[0]), "v"(E.e[1]), "v"(E.e[2]), "v"(E.e[3]), "v"(E.e[4]), "v"(E.e[5]), "v"(E.e[6]), "v"(E.e[7]), "v"(E.e[8]), \
+    "v"(E.e[9]), "v"(E.e[10])                                                                                       /* %17 .. %28 */
+#define SRL_STR_(X) #X
+#define SRL_STR(X) SRL_STR_(X)
+template <bool ALL> SRL_G void sweeps_mid(const TEs &E, const TRows &r, double &acc) {
+#if SRL_G_DEVICE
+    if constexpr (ALL)
+        asm volatile("s_movk_i32 vcc_lo, " SRL_STR(SRL_FREE_TRIPS) " - 1\n"
+                     "1:\n\t" SRL_SWEEP_K
+                     "s_sub_u32 vcc_lo, vcc_lo, 1\n\t"             // SCC = borrow: set by the trip that finds 0
+                     "s_cbranch_scc0 1b"
+                     : "+&v"(acc) : SRL_SWEEP_OPERANDS : SRL_T_CLOBBER, "vcc", "scc");
+    else
+        asm volatile(SRL_SWEEP : "+&v"(acc) : SRL_SWEEP_OPERANDS : SRL_T_CLOBBER);
+#else
+    for (int it = 0; it < (ALL ? kSolverIters - 2 : 1); it++) sweep_free(E, r, acc, E.e[11]);
+#endif
+}
+#undef SRL_SWEEP_OPERANDS
+#undef SRL_SWEEP
+#undef SRL_ROW
+#undef SRL_ROWB
+// The last sweep: row j's u is captured on its lane, u = fma(e_j, t, u), in the slot of the row's wait-state nop (independent of
+// acc: the capture is the second wait state between the write of t and its DPP read).  u is an output written before the
+// statement has read all of its inputs: early-clobber.
+SRL_G void sweep_last(const TEs &E, const TRows &r, double &acc, double &u) {
+#if SRL_G_DEVICE
+#define SRL_ROW(J, NJ_, EP, EJ) "v_add_f64 " SRL_T ", %2, %0 clamp\n\tv_fma_f64 %0, -%" #EP ", %0, %0\n\tv_fma_f64 %1, %" #EJ ", " SRL_T ", %1\n\tv_fmac_f64_dpp %0, " SRL_T ", %" #NJ_ " row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"
+#define SRL_ROWB(J, NJ_) "v_fmac_f64_dpp %0, " SRL_T ", %" #NJ_ " row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"
+    asm volatile(SRL_ROW(0, 3, 12, 13) SRL_ROWB(12, 9) SRL_ROW(1, 4, 13, 14) SRL_ROWB(13, 10) SRL_ROW(2, 5, 14, 15) SRL_ROWB(14, 11)
+                 SRL_ROW(3, 6, 15, 16) SRL_ROW(4, 7, 16, 17) SRL_ROW(5, 8, 17, 18)
+                 : "+&v"(acc), "+&v"(u)
+                 : "v"(r.cs), "v"(r.n[0]), "v"(r.n[1]), "v"(r.n[2]), "v"(r.n[3]), "v"(r.n[4]), "v"(r.n[5]),          // %2 .. %8
+                   "v"(r.n[kBM]), "v"(r.n[kBLo]), "v"(r.n[kBHi]),                                                     // %9 .. %11
+                   "v"(E.e[11]), "v"(E.e[0]), "v"(E.e[1]), "v"(E.e[2]), "v"(E.e[3]), "v"(E.e[4]), "v"(E.e[5])         // %12 .. %18
+                 : SRL_T_CLOBBER);
+    asm volatile(SRL_ROW(6, 3, 9, 10) SRL_ROW(7, 4, 10, 11) SRL_ROW(8, 5, 11, 12) SRL_ROW(9, 6, 12, 13) SRL_ROW(10, 7, 13, 14) SRL_ROW(11, 8, 14, 15)
+                 : "+&v"(acc), "+&v"(u)
+                 : "v"(r.cs), "v"(r.n[6]), "v"(r.n[7]), "v"(r.n[8]), "v"(r.n[9]), "v"(r.n[10]), "v"(r.n[11]),        // %2 .. %8
+                   "v"(E.e[5]), "v"(E.e[6]), "v"(E.e[7]), "v"(E.e[8]), "v"(E.e[9]), "v"(E.e[10]), "v"(E.e[11])        // %9 .. %15
+                 : SRL_T_CLOBBER);
+#undef SRL_ROW
+#undef SRL_ROWB
+#else
+    double t;
+    t = pgs_row2<0, kBM>(acc, r.cs, r.n[0], r.n[kBM], E.e[11]);    u = fma(E.e[0], t, u);
+    t = pgs_row2<1, kBLo>(acc, r.cs, r.n[1], r.n[kBLo], E.e[0]);   u = fma(E.e[1], t, u);
+    t = pgs_row2<2, kBHi>(acc, r.cs, r.n[2], r.n[kBHi], E.e[1]);   u = fma(E.e[2], t, u);
+    t = pgs_row<3>(acc, r.cs, r.n[3], E.e[2]);     u = fma(E.e[3], t, u);
+    t = pgs_row<4>(acc, r.cs, r.n[4], E.e[3]);     u = fma(E.e[4], t, u);
+    t = pgs_row<5>(acc, r.cs, r.n[5], E.e[4]);     u = fma(E.e[5], t, u);
+    t = pgs_row<6>(acc, r.cs, r.n[6], E.e[5]);     u = fma(E.e[6], t, u);
+    t = pgs_row<7>(acc, r.cs, r.n[7], E.e[6]);     u = fma(E.e[7], t, u);
+    t = pgs_row<8>(acc, r.cs, r.n[8], E.e[7]);     u = fma(E.e[8], t, u);
+    t = pgs_row<9>(acc, r.cs, r.n[9], E.e[8]);     u = fma(E.e[9], t, u);
+    t = pgs_row<10>(acc, r.cs, r.n[10], E.e[9]);   u = fma(E.e[10], t, u);
+    t = pgs_row<11>(acc, r.cs, r.n[11], E.e[10]);  u = fma(E.e[11], t, u);
+#endif
+}
+#undef SRL_SWEEP_K
+#undef SRL_FREE_TRIPS
+#undef SRL_FREE_SWEEP_K
+#undef SRL_T_CLOBBER
+#undef SRL_T
+#undef SRL_STR
+#undef SRL_STR_
 // Kuka2Button: the second button's three rows live on the same lanes (kBM, kBLo, kBHi) with their own accumulator.  Without a
 // contact they couple to nothing but each other: an independent three-row chain per sweep.
 struct TRows2 { double cs, n[3], lo, S, jb; };
@@ -618,33 +712,21 @@ SRL_G double sweeps_free(const TRows &r, const TRows2 *r2 = nullptr, double *u2_
 #pragma unroll
     for (int j = 0; j < NJ; j++) E.e[j] = l == j ? 1.0 : 0.0;
     E.e[0] += l == kBM ? 1.0 : 0.0; E.e[1] += l == kBLo ? 1.0 : 0.0; E.e[2] += l == kBHi ? 1.0 : 0.0;
-    const double e0 = E.e[0], e1 = E.e[1], e2 = E.e[2];
     double acc2 = 0.0, u2 = 0.0;
     const double c_bm = l == kBM ? 1.0 : 0.0, c_blo = l == kBLo ? 1.0 : 0.0, c_bhi = l == kBHi ? 1.0 : 0.0;
     sweep_free(E, r, acc, 0.0);
-    if constexpr (NB == 2) sweep_free2(*r2, acc2, c_bm, c_blo, 0.0);
-    for (int it = 1; it < kSolverIters - 1; it++) {
-        sweep_free(E, r, acc, E.e[11]);
-        if constexpr (NB == 2) sweep_free2(*r2, acc2, c_bm, c_blo, c_bhi);
-    }
     if constexpr (NB == 2) {
+        sweep_free2(*r2, acc2, c_bm, c_blo, 0.0);
+        for (int it = 1; it < kSolverIters - 1; it++) {
+            sweeps_mid<false>(E, r, acc);
+            sweep_free2(*r2, acc2, c_bm, c_blo, c_bhi);
+        }
         t = pgs_row<kBM>(acc2, r2->cs, r2->n[0], c_bhi);   u2 = fma(c_bm, t, u2);
         t = pgs_row<kBLo>(acc2, r2->cs, r2->n[1], c_bm);   u2 = fma(c_blo, t, u2);
         t = pgs_row<kBHi>(acc2, r2->cs, r2->n[2], c_blo);  u2 = fma(c_bhi, t, u2);
         *u2_out = u2;
-    }
-    t = pgs_row2<0, kBM>(acc, r.cs, r.n[0], r.n[kBM], E.e[11]);  u = fma(e0, t, u);
-    t = pgs_row2<1, kBLo>(acc, r.cs, r.n[1], r.n[kBLo], e0);      u = fma(e1, t, u);
-    t = pgs_row2<2, kBHi>(acc, r.cs, r.n[2], r.n[kBHi], e1);      u = fma(e2, t, u);
-    t = pgs_row<3>(acc, r.cs, r.n[3], e2);         u = fma(E.e[3], t, u);
-    t = pgs_row<4>(acc, r.cs, r.n[4], E.e[3]);     u = fma(E.e[4], t, u);
-    t = pgs_row<5>(acc, r.cs, r.n[5], E.e[4]);     u = fma(E.e[5], t, u);
-    t = pgs_row<6>(acc, r.cs, r.n[6], E.e[5]);     u = fma(E.e[6], t, u);
-    t = pgs_row<7>(acc, r.cs, r.n[7], E.e[6]);     u = fma(E.e[7], t, u);
-    t = pgs_row<8>(acc, r.cs, r.n[8], E.e[7]);     u = fma(E.e[8], t, u);
-    t = pgs_row<9>(acc, r.cs, r.n[9], E.e[8]);     u = fma(E.e[9], t, u);
-    t = pgs_row<10>(acc, r.cs, r.n[10], E.e[9]);   u = fma(E.e[10], t, u);
-    t = pgs_row<11>(acc, r.cs, r.n[11], E.e[10]);  u = fma(E.e[11], t, u);
+    } else sweeps_mid<true>(E, r, acc);
+    sweep_last(E, r, acc, u);
     return u;
 }
 
