@@ -2,7 +2,9 @@
 -DSRL_TREE_PROF, shader-clock stamps at the phase boundaries of tphysics_step, accumulated by lane 0 of a workgroup) run on the
 bench configuration — 4096 envs, Philox random agent, T fused steps.  Usage (GPU box, repo root):
     SRLHIP_LIB=robotics-rl-srl_amd/csrc/build/libsrlhip_prof.so python profiles/probes/kuka_tree_phases.py [T]
-Prints cycles per phase and per step for workgroups 0 and 511 (the device printf of the kernel), then the launch time."""
+Prints cycles per phase and per step for workgroups 0 and 511 (the device printf of the kernel), one `tprof_counts` line per workgroup
+(its steps with generic / joint-limit / contact rows: the launch lasts as long as the wavefront with the most), then the launch time,
+which the 1024 printf lines dominate: compare phases, not launches."""
 import os, sys
 sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "robotics-rl-srl_amd"))
 import torch

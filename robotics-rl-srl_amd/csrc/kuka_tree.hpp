@@ -576,7 +576,9 @@ struct TRows {
 //   * the 148 middle sweeps are ONE statement (sweeps_mid): acc (tied: counts twice), cs, 15 couplings and 12 restart masks are
 //     exactly 30 operands, so the row's t lives in a register pair that the text names and the clobber list reserves (SRL_T) and
 //     the trip count in vcc_lo.  The statement holds SRL_FREE_SWEEP_K sweeps and loops over them itself: one s_sub + the branch
-//     per K sweeps instead of two boundary slots per sweep and the compiler's 4x unrolling (profiles/NOTES.md section AH);
+//     per K sweeps instead of two boundary slots per sweep and the compiler's 4x unrolling (profiles/NOTES.md section AH).
+//     A taken branch costs a lone wavefront ~23 cycles, so K is as large as the instruction cache lets it be: K = 37 is a
+//     15 KB loop body run four times (section AI: K = 4, 37 and 74 measured with the instruction-cache counters);
 //   * the last sweep also captures u row by row (sweep_last): two statements of six rows.
 struct TEs { double e[NJ]; };          // e[j] = (lane == j), plus the button lanes on 0..2: who restarts its accumulator after row j
 // Home of t inside the one-statement sweeps: a fixed pair, because an operand for it would be the 31st.  v[12:13] is what the allocator
@@ -586,9 +588,23 @@ struct TEs { double e[NJ]; };          // e[j] = (lane == j), plus the button la
 // two-button kernel 100 -> 107 SGPR spills; none gains scratch (profiles/NOTES.md section AH).
 #define SRL_T "v[12:13]"
 #define SRL_T_CLOBBER "v12", "v13"
-#define SRL_FREE_SWEEP_K 4             // sweeps per trip of the looping statement (2 measured too: section AH)
+#ifndef SRL_FREE_SWEEP_K
+#define SRL_FREE_SWEEP_K 37            // sweeps per trip of the looping statement (2, 4 and 74 measured too: sections AH, AI)
+#endif
+#define SRL_SWEEP_4 SRL_SWEEP SRL_SWEEP SRL_SWEEP SRL_SWEEP
+#define SRL_SWEEP_36 SRL_SWEEP_4 SRL_SWEEP_4 SRL_SWEEP_4 SRL_SWEEP_4 SRL_SWEEP_4 SRL_SWEEP_4 SRL_SWEEP_4 SRL_SWEEP_4 SRL_SWEEP_4
+#if SRL_FREE_SWEEP_K == 4
 #define SRL_FREE_TRIPS 37
-#define SRL_SWEEP_K SRL_SWEEP SRL_SWEEP SRL_SWEEP SRL_SWEEP
+#define SRL_SWEEP_K SRL_SWEEP_4
+#elif SRL_FREE_SWEEP_K == 37
+#define SRL_FREE_TRIPS 4
+#define SRL_SWEEP_K SRL_SWEEP_36 SRL_SWEEP
+#elif SRL_FREE_SWEEP_K == 74
+#define SRL_FREE_TRIPS 2
+#define SRL_SWEEP_K SRL_SWEEP_36 SRL_SWEEP SRL_SWEEP_36 SRL_SWEEP
+#else
+#error "SRL_FREE_SWEEP_K: 4, 37 or 74"
+#endif
 static_assert(SRL_FREE_SWEEP_K * SRL_FREE_TRIPS == kSolverIters - 2, "the middle sweeps: all but the first and the last");
 SRL_G void sweep_free(const TEs &E, const TRows &r, double &acc, double ep_first) {
 #if SRL_G_DEVICE
@@ -687,6 +703,8 @@ SRL_G void sweep_last(const TEs &E, const TRows &r, double &acc, double &u) {
 #endif
 }
 #undef SRL_SWEEP_K
+#undef SRL_SWEEP_36
+#undef SRL_SWEEP_4
 #undef SRL_FREE_TRIPS
 #undef SRL_FREE_SWEEP_K
 #undef SRL_T_CLOBBER
@@ -919,6 +937,10 @@ template <int G, int NG> SRL_G void cn_frictions_n(const BRow &b, const double *
 // alternate between two value registers — so a row is four slots: add, restart, previous row's accB fmac, own accA fmac
 // (profiles/probes/pgs_row_timing.hip: 11.4 -> 9.2 ns per row; the dependent chain add -> fmac alone is 7.9).  Same operations
 // on the same accumulators in the same order: bit-identical to cn_rowA / cn_rowA2.
+// What a sweep of cn_sweeps<NG> issues around these 54 instructions is counted on the built object by
+// profiles/probes/kuka_contact_sweep_slots.py (tests/test_isa_contact_sweep_slots.py): 57 / 79 / 103 slots per sweep for NG = 0 / 1 / 2
+// against floors of 57 / 74 / 91.  The bank-B rows stay one statement each with compiler-scheduled code between them: hand-scheduling
+// them was costed in profiles/NOTES.md section AI and not built.
 SRL_G void cn_phaseA(const TRows &r, const double *nBA, const double *eA, double e0, double e1, double e2, double &accA, double &accB) {
 #if SRL_G_DEVICE
     double t0, t1;

@@ -595,6 +595,9 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
         const unsigned long long *pp = tree::tprof_buf();
         for (int i = 0; i < tree::kProfSlots; i++) printf("tprof block %d T %d phase %d cycles %llu\n", (int)blockIdx.x, T, i, pp[i]);
     }
+    // every workgroup: how many of its first wavefront's steps carried generic / joint-limit / contact rows (the launch lasts as long as
+    // the wavefront with the most of them)
+    if (threadIdx.x == 0) { const unsigned long long *pp = tree::tprof_buf(); printf("tprof_counts block %d T %d generic %llu limit %llu contact %llu\n", (int)blockIdx.x, T, pp[17], pp[18], pp[19]); }
 #endif
     int e_out = e;
     asm volatile("" : "+v"(e_out));       // exit-store addresses are recomputed instead of being kept live across the loop
