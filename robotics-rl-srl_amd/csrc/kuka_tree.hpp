@@ -40,6 +40,14 @@ using grp::rcp;
 using grp::shfl;
 using grp::sync_scratch;
 using grp::wany;
+// a value every lane of the wavefront holds alike (a count made of wany()s), pinned to an SGPR: loop bounds and branches on it stay scalar
+SRL_G int wave_uniform(int x) {
+#if SRL_G_DEVICE
+    return __builtin_amdgcn_readfirstlane(x);
+#else
+    return x;
+#endif
+}
 
 // ---- phase stamps of the PROFILING build (make prof: -DSRL_TREE_PROF, profiles/probes/kuka_tree_phases.py): shader-clock cycles
 // between consecutive stamps, accumulated per phase by lane 0 of the workgroup in LDS, printed by workgroup 0 when the kernel ends.
@@ -1242,6 +1250,13 @@ struct GenIn {
 //   W (the own row of M^-1) in the NBA plane [k][lane], S in its own plane, and MISC[13][lane] in the NAB / NBB planes:
 //   sphere centre cc[3], n_cap[3], n_base[3], d_cap, d_base, pen_lo, pen_hi
 constexpr int SC_STASH_W = SC_NBA, SC_STASH_MISC = SC_NAB;
+// Once every lane has read its MISC values the plane carries, until the couplings are written, what the sphere lane of a contact
+// publishes for the joint lanes, PUB[normal slot][16]: nrm[3], contact point[3], tdir[3], tdir2[3], the sphere's ancestor mask.  The
+// slot's definition says whether this env's slot is a contact (DEF[5] of a NORMAL slot: 1; mu lives in the friction slot's DEF[5]).
+// The spatial axes' plane, dead behind the Jacobians, then takes the joints' unconstrained velocities (not OCC: its S is parked per env).
+constexpr int SC_PUB = SC_STASH_MISC, kPubDoubles = 16, SC_QD = SC_S;
+enum { PB_NRM = 0, PB_PT = 3, PB_T1 = 6, PB_T2 = 9, PB_SANC = 12 };
+static_assert(kNGen * kPubDoubles <= kNB * GL, "PUB fits the NAB plane");
 enum { SM_CC = 0, SM_NCAP = 3, SM_NBASE = 6, SM_DCAP = 9, SM_DBASE, SM_PENLO, SM_PENHI, SM_COUNT,
        SM_NCAP2 = SM_COUNT, SM_NBASE2 = SM_NCAP2 + 3, SM_DCAP2 = SM_NBASE2 + 3, SM_DBASE2, SM_COUNT2 };     // Kuka2Button: the second button's shapes
 static_assert(NJ * GL <= kNArows * GL && SM_COUNT2 * GL <= 2 * kNB * GL, "stash planes");
@@ -1255,8 +1270,12 @@ struct GenCtx { BRow b; int nlim_w, ngen_w; bool on_lim, on_con; };
 template <int NB = 1, int RB = 0, int OCC = 0, int DET = -1, int PART = 0>
 SRL_G GenOut general_path(const GenIn &in, GenCtx *ctx = nullptr) {
     static_assert(!OCC || (NB == 1 && RB == 0), "the two-wavefronts-per-SIMD variant covers the one-button envs");
-    // Written for a SMALL register footprint, not for speed (the path is rare): every loop over joints / slots is rolled and works
-    // on LDS-resident data, so that the common path's long-lived values are not pushed into scratch by this code's pressure.
+    // Written for a SMALL register footprint (the path is rare): every loop over joints / slots works on LDS-resident data, so that
+    // the common path's long-lived values are not pushed into scratch by this code's pressure.
+    // kLanes: the setup of the one-button envs (profiles/NOTES.md section AJ) — contact Jacobians one entry per joint lane, slot loops
+    // over the used slots only, the joints' velocities from LDS.  Kuka2Button (NB = 2) and KukaRandButton (RB) keep the rolled setup,
+    // twelve trips on the contact's lane and over all slots: their persistent kernels failed parity tests with the other one (AJ).
+    constexpr bool kLanes = NB == 1 && RB == 0;
     SRL_TSTAMP(8); SRL_TCOUNT(17);
     const double dt = kDt, inv_dt = 1.0 / kDt;
     const double *tab = in.tab;
@@ -1278,8 +1297,11 @@ SRL_G GenOut general_path(const GenIn &in, GenCtx *ctx = nullptr) {
     b.bsel = 0; b.nBC[0] = 0.0; b.nBC[1] = 0.0; b.nBC[2] = 0.0;
     b.obj = -1; b.Jo[0] = 0.0; b.Jo[1] = 0.0; b.Jo[2] = 0.0; b.jo2m = 0.0;
     int nlim = 0, ngen = 0, nlim_w = 0, ngen_w = 0;
+    // the slots some env of the wavefront uses are 0 .. ngu_w - 1 (normals / limits) and f ng .. f ng + ngu_w - 1 (friction direction f)
+    int ngu_w = 0;
+    const int ng_w = kLanes ? wave_uniform(ng) : ng, nfd_w = kLanes ? wave_uniform(nfd) : nfd;      // (the table's values, the same on every lane)
     bool on_lim = false, on_con = false;           // the own bank-B row belongs to the limit phase / the contact phase of the sweep
-    if constexpr (PART == 2) { b = ctx->b; nlim_w = ctx->nlim_w; ngen_w = ctx->ngen_w; on_lim = ctx->on_lim; on_con = ctx->on_con; }
+    if constexpr (PART == 2) { b = ctx->b; nlim_w = wave_uniform(ctx->nlim_w); ngen_w = wave_uniform(ctx->ngen_w); on_lim = ctx->on_lim; on_con = ctx->on_con; ngu_w = ngen_w < ng_w ? ngen_w : ng_w; }
     if constexpr (PART != 2) {
     {
         // ---- the parked inputs of this lane (the MISC plane is reused for the NAB couplings below)
@@ -1341,31 +1363,41 @@ SRL_G GenOut general_path(const GenIn &in, GenCtx *ctx = nullptr) {
                 d[0] = 0.0; d[1] = pen > 0 ? -pen * inv_dt : 0.0; d[2] = pen > 0 ? 0.0 : -pen * lerp * inv_dt; d[3] = blim; d[4] = 1.0;
             }
         };
+        // kLanes: a contact's Jacobian entries are computed one per joint lane below, the sphere's lane only publishes the geometry
         auto put_contact = [&](int slot, const double nrm[3], double dist, bool cap, int bsel, int obj = -1) {
             if (slot < max_gen) {
-                double *o = sc + SC_J + slot * NJ, *of = sc + SC_J + (ng + slot) * NJ;
                 double *d = sc + SC_DEF + slot * kDefDoubles, *df = sc + SC_DEF + (ng + slot) * kDefDoubles;
-                double *of2 = sc + SC_J + (nfd == 2 ? 2 * ng + slot : ng + slot) * NJ, *df2 = sc + SC_DEF + (nfd == 2 ? 2 * ng + slot : ng + slot) * kDefDoubles;
+                double *df2 = sc + SC_DEF + (nfd == 2 ? 2 * ng + slot : ng + slot) * kDefDoubles;
                 double pt3[3], tdir[3], tdir2[3];
                 const double pen = dist + slop;                           // Bullet: penetration = distance + m_linearSlop
                 const double rad = L.sph(3), smu = L.smu();
-                const uint32_t sanc = L.sanc();
 #pragma unroll
                 for (int k = 0; k < 3; k++) pt3[k] = cc[k] - rad * nrm[k];
                 // btPlaneSpace1: first tangent of the contact normal (the one friction direction of Bullet's multibody solver)
                 if (fabs(nrm[2]) > 0.7071067811865475244) { const double a = nrm[1] * nrm[1] + nrm[2] * nrm[2], kk = 1.0 / sqrt(a); tdir[0] = 0.0; tdir[1] = -nrm[2] * kk; tdir[2] = nrm[1] * kk; }
                 else { const double a = nrm[0] * nrm[0] + nrm[1] * nrm[1], kk = 1.0 / sqrt(a); tdir[0] = -nrm[1] * kk; tdir[1] = nrm[0] * kk; tdir[2] = 0.0; }
                 cross3(nrm, tdir, tdir2);                                 // the second friction direction (SOLVER_USE_2_FRICTION_DIRECTIONS)
+                if constexpr (kLanes) {
+                    double *pub = sc + SC_PUB + slot * kPubDoubles;
+#pragma unroll
+                    for (int k = 0; k < 3; k++) { pub[PB_NRM + k] = nrm[k]; pub[PB_PT + k] = pt3[k]; pub[PB_T1 + k] = tdir[k]; pub[PB_T2 + k] = tdir2[k]; }
+                    pub[PB_SANC] = (double)L.sanc();                          // only the joints the sphere's link hangs on (a 12-bit mask: exact)
+                    d[5] = 1.0;                                               // a contact: the joint lanes fill J of this slot and of its friction slots
+                } else {
+                    double *o = sc + SC_J + slot * NJ, *of = sc + SC_J + (ng + slot) * NJ;
+                    double *of2 = sc + SC_J + (nfd == 2 ? 2 * ng + slot : ng + slot) * NJ;
+                    const uint32_t sanc = L.sanc();
 #pragma unroll 4
-                for (int j = 0; j < NJ; j++) {
-                    const double *Sj = spark + j * 6;
-                    const double Swj[3] = {Sj[0], Sj[1], Sj[2]}, Svj[3] = {Sj[3], Sj[4], Sj[5]};
-                    double c3[3];
-                    cross3(Swj, pt3, c3);                                 // w_j x pt + v_j = velocity of the contact point per unit qd_j
-                    const double on = (sanc >> j) & 1u ? 1.0 : 0.0;       // only the joints the sphere's link hangs on
-                    o[j] = on * (dot3(nrm, c3) + dot3(nrm, Svj));
-                    of[j] = on * (dot3(tdir, c3) + dot3(tdir, Svj));
-                    if (nfd == 2) of2[j] = on * (dot3(tdir2, c3) + dot3(tdir2, Svj));
+                    for (int j = 0; j < NJ; j++) {
+                        const double *Sj = spark + j * 6;
+                        const double Swj[3] = {Sj[0], Sj[1], Sj[2]}, Svj[3] = {Sj[3], Sj[4], Sj[5]};
+                        double c3[3];
+                        cross3(Swj, pt3, c3);                                 // w_j x pt + v_j = velocity of the contact point per unit qd_j
+                        const double on = (sanc >> j) & 1u ? 1.0 : 0.0;       // only the joints the sphere's link hangs on
+                        o[j] = on * (dot3(nrm, c3) + dot3(nrm, Svj));
+                        of[j] = on * (dot3(tdir, c3) + dot3(tdir, Svj));
+                        if (nfd == 2) of2[j] = on * (dot3(tdir2, c3) + dot3(tdir2, Svj));
+                    }
                 }
                 d[0] = cap ? -nrm[2] : 0.0; d[1] = pen > 0 ? -pen * inv_dt : 0.0; d[2] = pen > 0 ? 0.0 : -pen * cerp * inv_dt; d[3] = 1e10; d[4] = 1.0;
                 df[0] = cap ? -tdir[2] : 0.0; df[4] = (L.friction() && smu > 0.0) ? 1.0 : 0.0; df[5] = smu;
@@ -1386,30 +1418,84 @@ SRL_G GenOut general_path(const GenIn &in, GenCtx *ctx = nullptr) {
             if (c_base2) put_contact(s_base2, n_base2, d_base2, false, 1);
         }
         if constexpr (RB) { if (c_obj) put_contact(s_cap2, n_obj, d_obj, false, 0, k_obj); }
-        sync_scratch();
-    }
-    SRL_TSTAMP(12);                         // candidates -> row definitions in LDS
-    nlim_w = 0; ngen_w = 0;
+        sync_scratch();                    // definitions (kLanes: and contact geometry) are in LDS
+        if constexpr (kLanes) {
+            nlim_w = 0; ngen_w = 0;
 #pragma nounroll
-    for (int k = 0; k < kNGen; k++) { if (wany(k < nlim)) nlim_w = k + 1; if (wany(k < ngen)) ngen_w = k + 1; }
+            for (int k = 0; k < kNGen; k++) { if (wany(k < nlim)) nlim_w = k + 1; if (wany(k < ngen)) ngen_w = k + 1; }
+            nlim_w = wave_uniform(nlim_w); ngen_w = wave_uniform(ngen_w);
+            // ---- contact Jacobians: joint lane j computes entry j of the normal row and of its friction rows, one trip per normal slot
+            // some env of the wavefront uses.  (A slot this env does not use, or uses for a joint limit, is left alone: DEF[5] is 0.)
+            ngu_w = ngen_w < ng_w ? ngen_w : ng_w;
+#pragma nounroll
+            for (int g = 0; g < ngu_w; g++) {
+                const double *pub = sc + SC_PUB + g * kPubDoubles;
+                if (L.l < NJ && sc[SC_DEF + g * kDefDoubles + 5] != 0.0) {
+                    const double nrm[3] = {pub[PB_NRM], pub[PB_NRM + 1], pub[PB_NRM + 2]}, pt3[3] = {pub[PB_PT], pub[PB_PT + 1], pub[PB_PT + 2]};
+                    const double tdir[3] = {pub[PB_T1], pub[PB_T1 + 1], pub[PB_T1 + 2]};
+                    const uint32_t sanc = (uint32_t)pub[PB_SANC];
+                    const int j = L.l;
+                    const double *Sj = spark + j * 6;
+                    const double Swj[3] = {Sj[0], Sj[1], Sj[2]}, Svj[3] = {Sj[3], Sj[4], Sj[5]};
+                    double c3[3];
+                    cross3(Swj, pt3, c3);                                 // w_j x pt + v_j = velocity of the contact point per unit qd_j
+                    const double on = (sanc >> j) & 1u ? 1.0 : 0.0;
+                    sc[SC_J + g * NJ + j] = on * (dot3(nrm, c3) + dot3(nrm, Svj));
+                    sc[SC_J + (ng + g) * NJ + j] = on * (dot3(tdir, c3) + dot3(tdir, Svj));
+                    if (nfd == 2) {
+                        const double tdir2[3] = {pub[PB_T2], pub[PB_T2 + 1], pub[PB_T2 + 2]};
+                        sc[SC_J + (2 * ng + g) * NJ + j] = on * (dot3(tdir2, c3) + dot3(tdir2, Svj));
+                    }
+                }
+            }
+            sync_scratch();
+        }
+    }
+    SRL_TSTAMP(12);                         // candidates -> row definitions in LDS (kLanes: with the wavefront's counts and the per-lane Jacobians)
+    if constexpr (!kLanes) {
+        nlim_w = 0; ngen_w = 0;
+#pragma nounroll
+        for (int k = 0; k < kNGen; k++) { if (wany(k < nlim)) nlim_w = k + 1; if (wany(k < ngen)) ngen_w = k + 1; }
+    }
     // ---- W J of every active slot: joint lane k computes (W J_s)_k = its coupling a_{k,s} (W: the parked row of M^-1 in the NBA
     //      plane); button lanes: jb wb Jb_s.  The own bank-A row's scaled couplings -a / (a_rr S_r) go straight to the NAB plane.
     {
         const bool liveA = r.S > 0.0 && r.diag > 0.0;
         const double invA = liveA ? 1.0 / (r.diag * r.S) : 0.0;
-#pragma unroll 2
-        for (int s = 0; s < kNB; s++) {
-            const bool used = used_slot(s, ngen_w);
-            double wjk = 0.0;
-            if (used) {
+        if constexpr (kLanes) {
+            // the slots no env of the wavefront uses: both coupling planes hold what a zero coupling gives, -0 * (inverse >= 0) = -0
+            // (own column: the contact geometry the planes carried was read in front of the sync above)
+#pragma unroll
+            for (int s = 0; s < kNB; s++) { sc[SC_NAB + s * GL + L.l] = -0.0; sc[SC_NBB + s * GL + L.l] = -0.0; }
+            if constexpr (!OCC) { if (L.l < NJ) sc[SC_QD + L.l] = qd_new; }      // the unconstrained velocity of every joint, for the own bank-B rows below
+            for (int f = 0; f <= nfd_w; f++)
+#pragma nounroll
+            for (int g = 0; g < ngu_w; g++) {
+                const int s = f * ng_w + g;
+                double wjk = 0.0;
                 const double *Js = sc + SC_J + s * NJ, *ds = sc + SC_DEF + s * kDefDoubles;
                 const double act = ds[4], jbs = ds[0];
 #pragma unroll
                 for (int j = 0; j < NJ; j++) wjk = fma(wpark[j * GL + L.l], act != 0.0 ? Js[j] : 0.0, wjk);   // (a slot this env does not use holds stale LDS: select, never multiply by 0)
                 if (L.jnt) sc[SC_WJ + s * NJ + L.l] = wjk;
                 else wjk = (is_button && act != 0.0 && (NB == 1 || ds[6] == 0.0)) ? r.jb * wb * jbs : 0.0;
+                sc[SC_NAB + s * GL + L.l] = -wjk * invA;
             }
-            sc[SC_NAB + s * GL + L.l] = -wjk * invA;
+        } else {
+#pragma unroll 2
+            for (int s = 0; s < kNB; s++) {
+                const bool used = used_slot(s, ngen_w);
+                double wjk = 0.0;
+                if (used) {
+                    const double *Js = sc + SC_J + s * NJ, *ds = sc + SC_DEF + s * kDefDoubles;
+                    const double act = ds[4], jbs = ds[0];
+#pragma unroll
+                    for (int j = 0; j < NJ; j++) wjk = fma(wpark[j * GL + L.l], act != 0.0 ? Js[j] : 0.0, wjk);   // (a slot this env does not use holds stale LDS: select, never multiply by 0)
+                    if (L.jnt) sc[SC_WJ + s * NJ + L.l] = wjk;
+                    else wjk = (is_button && act != 0.0 && (NB == 1 || ds[6] == 0.0)) ? r.jb * wb * jbs : 0.0;
+                }
+                sc[SC_NAB + s * GL + L.l] = -wjk * invA;
+            }
         }
     }
     sync_scratch();                        // W J complete; the parked W rows (NBA plane) are dead from here on
@@ -1454,7 +1540,7 @@ SRL_G GenOut general_path(const GenIn &in, GenCtx *ctx = nullptr) {
 #pragma unroll 4
         for (int j = 0; j < NJ; j++) {
             const double Jj = own_on ? Jr[j] : 0.0, wj = own_on ? wjr[j] : 0.0;
-            const double qj = shfl(qd_new, j);                           // the unconstrained velocity of joint j
+            const double qj = (kLanes && !OCC) ? sc[SC_QD + j] : shfl(qd_new, j);    // the unconstrained velocity of joint j
             diag = fma(Jj, wj, diag); jv = fma(Jj, qj, jv); offb = fma(wj, lo_of(j), offb);
         }
         const bool live = own_on && diag > 0.0;
@@ -1464,30 +1550,61 @@ SRL_G GenOut general_path(const GenIn &in, GenCtx *ctx = nullptr) {
         const double des = (own_on && !mine_f) ? myd[1] : 0.0, perr = (own_on && !mine_f) ? myd[2] : 0.0;
         b.cs = ((des - jv) + perr - offb) * b.inv_diag;
         // couplings of the own bank-B row to the bank-A rows j (in u units: a_rj S_j) and to the bank-B rows s
+        if constexpr (kLanes) {
+#pragma unroll 4
+            for (int j = 0; j < NJ; j++) {
+                const double a = own_on ? wjr[j] : 0.0;
+                sc[SC_NBA + j * GL + L.l] = -a * S_of(j) * b.inv_diag;
+            }
+            {
+                const bool other = NB == 2 && own_bsel;              // the row acts on ONE glider: its couplings go to that button's rows
+                const double a = other ? 0.0 : own_jb * wb, ah = other ? 0.0 : -own_jb * wb;
+                sc[SC_NBA + kBM * GL + L.l] = -a * S_of(kBM) * b.inv_diag;
+                sc[SC_NBA + kBLo * GL + L.l] = -a * S_of(kBLo) * b.inv_diag;
+                sc[SC_NBA + kBHi * GL + L.l] = -ah * S_of(kBHi) * b.inv_diag;
+            }
+        } else {
 #pragma unroll 5
-        for (int j = 0; j < kNArows; j++) {
-            double a = 0.0;
-            if (j < NJ) a = own_on ? wjr[j] : 0.0;
-            else if (j == kBM || j == kBLo) a = own_jb * wb;
-            else if (j == kBHi) a = -own_jb * wb;
-            if (NB == 2 && j >= NJ && own_bsel) a = 0.0;        // the row acts on ONE glider: its couplings go to that button's rows
-            sc[SC_NBA + j * GL + L.l] = -a * S_of(j) * b.inv_diag;
+            for (int j = 0; j < kNArows; j++) {
+                double a = 0.0;
+                if (j < NJ) a = own_on ? wjr[j] : 0.0;
+                else if (j == kBM || j == kBLo) a = own_jb * wb;
+                else if (j == kBHi) a = -own_jb * wb;
+                if (NB == 2 && j >= NJ && own_bsel) a = 0.0;        // the row acts on ONE glider: its couplings go to that button's rows
+                sc[SC_NBA + j * GL + L.l] = -a * S_of(j) * b.inv_diag;
+            }
         }
         if constexpr (NB == 2) {
             const double ab = own_bsel ? own_jb * wb * b.inv_diag : 0.0;
             b.nBC[0] = -ab * S_of(kBM); b.nBC[1] = -ab * S_of(kBLo); b.nBC[2] = ab * S_of(kBHi);
         }
-#pragma unroll 2
-        for (int s = 0; s < kNB; s++) {
-            const bool used = used_slot(s, ngen_w);
-            double a = 0.0;
-            if (used && s != L.l) {
-                const double *ws = sc + SC_WJ + s * NJ, *ds = sc + SC_DEF + s * kDefDoubles;
-                a = (ds[4] != 0.0 && (NB == 1 || (ds[6] != 0.0) == (own_bsel != 0))) ? own_jb * wb * ds[0] : 0.0;
+        if constexpr (kLanes) {
+            for (int f = 0; f <= nfd_w; f++)
+#pragma nounroll
+            for (int g = 0; g < ngu_w; g++) {
+                const int s = f * ng_w + g;
+                double a = 0.0;
+                if (s != L.l) {
+                    const double *ws = sc + SC_WJ + s * NJ, *ds = sc + SC_DEF + s * kDefDoubles;
+                    a = (ds[4] != 0.0 && (NB == 1 || (ds[6] != 0.0) == (own_bsel != 0))) ? own_jb * wb * ds[0] : 0.0;
 #pragma unroll
-                for (int j = 0; j < NJ; j++) a = fma(own_on ? Jr[j] : 0.0, ds[4] != 0.0 ? ws[j] : 0.0, a);
+                    for (int j = 0; j < NJ; j++) a = fma(own_on ? Jr[j] : 0.0, ds[4] != 0.0 ? ws[j] : 0.0, a);
+                }
+                sc[SC_NBB + s * GL + L.l] = -a * b.inv_diag;
             }
-            sc[SC_NBB + s * GL + L.l] = -a * b.inv_diag;
+        } else {
+#pragma unroll 2
+            for (int s = 0; s < kNB; s++) {
+                const bool used = used_slot(s, ngen_w);
+                double a = 0.0;
+                if (used && s != L.l) {
+                    const double *ws = sc + SC_WJ + s * NJ, *ds = sc + SC_DEF + s * kDefDoubles;
+                    a = (ds[4] != 0.0 && (NB == 1 || (ds[6] != 0.0) == (own_bsel != 0))) ? own_jb * wb * ds[0] : 0.0;
+#pragma unroll
+                    for (int j = 0; j < NJ; j++) a = fma(own_on ? Jr[j] : 0.0, ds[4] != 0.0 ? ws[j] : 0.0, a);
+                }
+                sc[SC_NBB + s * GL + L.l] = -a * b.inv_diag;
+            }
         }
         on_lim = b.on && L.l < nlim; on_con = b.on && !on_lim;
     }
@@ -1581,11 +1698,22 @@ SRL_G GenOut general_path(const GenIn &in, GenCtx *ctx = nullptr) {
     out.bodies_done = obj_rows_w; out.dvo[0] = 0.0; out.dvo[1] = 0.0; out.dvo[2] = 0.0;
     if constexpr (RB) { if (obj_rows_w) { out.dvo[0] = rr.dv[0]; out.dvo[1] = rr.dv[1]; out.dvo[2] = rr.dv[2]; } }
     const double pbb = b.on ? b.jb * b.lam * wb : 0.0;
-    for (int s = 0; s < kNB; s++) {
-        if (!used_slot(s, ngen_w)) continue;
-        out.acc_b = fma(sc[SC_NAB + s * GL + L.l], shfl(b.on ? b.lam : 0.0, s), out.acc_b);
-        out.dvb_b += shfl(b.bsel ? 0.0 : pbb, s);
-        if constexpr (NB == 2) out.dvb_b2 += shfl(b.bsel ? pbb : 0.0, s);
+    if constexpr (kLanes) {
+        for (int f = 0; f <= nfd_w; f++)
+#pragma nounroll
+        for (int g = 0; g < ngu_w; g++) {
+            const int s = f * ng_w + g;
+            out.acc_b = fma(sc[SC_NAB + s * GL + L.l], shfl(b.on ? b.lam : 0.0, s), out.acc_b);
+            out.dvb_b += shfl(b.bsel ? 0.0 : pbb, s);
+            if constexpr (NB == 2) out.dvb_b2 += shfl(b.bsel ? pbb : 0.0, s);
+        }
+    } else {
+        for (int s = 0; s < kNB; s++) {
+            if (!used_slot(s, ngen_w)) continue;
+            out.acc_b = fma(sc[SC_NAB + s * GL + L.l], shfl(b.on ? b.lam : 0.0, s), out.acc_b);
+            out.dvb_b += shfl(b.bsel ? 0.0 : pbb, s);
+            if constexpr (NB == 2) out.dvb_b2 += shfl(b.bsel ? pbb : 0.0, s);
+        }
     }
     sync_scratch();                          // scratch is reused by the next step
     SRL_TSTAMP(16);
