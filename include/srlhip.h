@@ -445,6 +445,26 @@ int srlhip_kuka_kernel(srlhip_handle h);
  * tests/test_gpu_group_primitives.py checks them against the definitions the CPU-side emulation of the same source uses. */
 int srlhip_selftest_group_primitives(int32_t device_id, const double *q7, double *out, int32_t out_doubles);
 
+/* Diagnostic, tests only: runs a small scripted draw program on every random generator form of the library (csrc/rng.hpp, csrc/kuka_group.hpp;
+ * the interpreter is csrc/rng_probe.hpp) on device_id, without an env handle, and returns every drawn value as raw bits.
+ *   generator  0 Mt19937 (one lane per env)   1 GroupMt (16 lanes per env)   2 Lane0Rng<Mt19937> (16 lanes, lane 0 draws)
+ *              3 Philox (one lane per env, `stream` 0 / 1)   4 GroupPhilox (stream 0)   5 GroupActions (stream 1); 1, 2, 4, 5 write 16 lanes
+ *   keys       uint32 [2][n_envs]: MT19937 seed digits (key_len [n_envs] = 1 or 2 of them, seeded by srlhip_seed's own kernel) / Philox key
+ *   stride     MT forms: env stride of the state words in device memory (>= n_envs)
+ *   mask       [n_envs] or NULL: an env with mask 0 never draws (its out rows stay 0, its state as seeded)
+ *   state_in   NULL, or the start state in state_out's layout (MT: instead of seeding; Philox family: the start counters, default 0)
+ *   script     int32 [n_ops][3] = (op, index of the first argument in args, repeat):  0 raw word (Philox: the 4 words of a block, forms 0 1 3)
+ *              1 double01   2 uniform(lo, hi)   3 normal(loc, scale)   4 bounded(r) -> [0, r] (the only draw of form 5)
+ *              5 store + load through the state in device memory, as at a kernel boundary   6 Philox family: counter = start counter + arg
+ *   skip       int32 [n_envs]: draws env e throws away before its script: raw words (MT), blocks (form 3), normal(0, 1) (form 4), bounded(5) (form 5)
+ *   out        uint64 [n_envs][lanes][values]: float64 bits / zero-extended integers, lanes = 16 for forms 1 2 4 5, else 1
+ *   state_out  uint64 per env: MT forms 627 (624 state words, index, has_gauss, bits of the cached deviate), Philox family 1 (counter)
+ * SRLHIP_EINVAL for a script the form cannot run or buffers too small for it. */
+int srlhip_selftest_rng(int32_t device_id, int32_t generator, int32_t stream, int32_t n_envs, int32_t stride, const uint32_t *keys,
+                        const int32_t *key_len, const uint8_t *mask, const uint64_t *state_in, const int32_t *script, int32_t n_ops,
+                        const double *args, int32_t n_args, const int32_t *skip, uint64_t *out, int64_t out_words, uint64_t *state_out,
+                        int64_t state_words);
+
 const char *srlhip_last_error(srlhip_handle h);
 int srlhip_abi_version(void);
 

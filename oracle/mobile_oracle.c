@@ -201,3 +201,17 @@ void oracle_np_random_draws(const uint32_t *key, int key_len, int n, double *uni
     for (i = 0; i < n; i++) gauss[i] = np_rng_gauss(&r);
     for (i = 0; i < n; i++) randint3[i] = np_rng_randint(&r, 3);
 }
+
+/* Test hook: n consecutive blocks of the Philox stream of philox.h from counter ctr — per block its four words, the double
+ * of words 0 / 1 and the Box-Muller deviate (libm's log, sqrt, cos). */
+void oracle_philox_draws(uint32_t k0, uint32_t k1, uint64_t ctr, uint32_t stream, int n, uint32_t *words4, double *uniform01,
+                         double *gauss) {
+    int i;
+    for (i = 0; i < n; i++) {
+        philox_t p; p.k0 = k0; p.k1 = k1; p.ctr = ctr + (uint64_t)i; p.stream = stream;
+        philox_block(&p, words4 + 4 * i);
+        uniform01[i] = philox_to_double(words4[4 * i], words4[4 * i + 1]);
+        p.ctr = ctr + (uint64_t)i;
+        gauss[i] = philox_std_normal(&p);
+    }
+}

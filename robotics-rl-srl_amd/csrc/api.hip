@@ -173,9 +173,7 @@ int seed_impl(Handle *h, const uint8_t *mask, const int64_t *seeds) {
     if (h->cfg.rng_mode == SRLHIP_RNG_MT19937) {
         if ((rc = stage_in(h, &h->st_rand, &h->st_rand_sz, digits.data(), digits.size() * 4))) return rc;
         if ((rc = stage_in(h, &h->st_noise, &h->st_noise_sz, len.data(), len.size() * 4))) return rc;
-        hipLaunchKernelGGL(mt_seed_k, grid, block, 0, h->stream, h->rng.mt, n, d_mask,
-                           static_cast<const uint32_t *>(h->st_rand), static_cast<const int32_t *>(h->st_noise));
-        SRL_HIP_CHECK(h, hipGetLastError());
+        SRL_HIP_CHECK(h, mt_seed_launch(h->rng.mt, n, d_mask, static_cast<const uint32_t *>(h->st_rand), static_cast<const int32_t *>(h->st_noise), h->stream));
         SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));
     }
     return 0;
@@ -227,6 +225,12 @@ int field_lookup(Handle *h, int field, void **dptr, size_t *elem, int *count) {
 }
 
 }  // namespace
+
+// RandomState.seed for the envs of a view: srlhip_seed's launch, also what the generator self-test (rng_probe.hip) seeds with
+hipError_t srl::mt_seed_launch(const Mt19937View &v, int n, const uint8_t *d_mask, const uint32_t *d_digits, const int32_t *d_len, hipStream_t stream) {
+    hipLaunchKernelGGL(mt_seed_k, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, v, n, d_mask, d_digits, d_len);
+    return hipGetLastError();
+}
 
 extern "C" {
 
@@ -1007,6 +1011,15 @@ int srlhip_selftest_group_primitives(int32_t device_id, const double *q7, double
     if (!q7 || !out) return SRLHIP_EINVAL;
     if (hipSetDevice(device_id) != hipSuccess) return SRLHIP_EHIP;
     return kuka_group_probe(q7, out, out_doubles);
+}
+
+int srlhip_selftest_rng(int32_t device_id, int32_t generator, int32_t stream, int32_t n_envs, int32_t stride, const uint32_t *keys,
+                        const int32_t *key_len, const uint8_t *mask, const uint64_t *state_in, const int32_t *script, int32_t n_ops,
+                        const double *args, int32_t n_args, const int32_t *skip, uint64_t *out, int64_t out_words, uint64_t *state_out,
+                        int64_t state_words) {
+    if (hipSetDevice(device_id) != hipSuccess) return SRLHIP_EHIP;
+    return rng_probe_run(generator, stream, n_envs, stride, keys, key_len, mask, state_in, script, n_ops, args, n_args, skip, out, out_words,
+                         state_out, state_words);
 }
 
 int srlhip_sync(srlhip_handle hh) {

@@ -97,6 +97,12 @@ void kuka_default_model(double *table138);
 int kuka_set_tree_model(Handle *h, const double *table510);
 void kuka_default_tree_model(double *table510);
 int kuka_group_probe(const double *q7_host, double *out_host, int out_doubles);
+// api.hip: the launch of srlhip_seed's MT19937 seeding kernel (digits [2][n], len [n]: device pointers; mask may be null)
+hipError_t mt_seed_launch(const Mt19937View &v, int n, const uint8_t *d_mask, const uint32_t *d_digits, const int32_t *d_len, hipStream_t stream);
+// rng_probe.hip: srlhip_selftest_rng (host pointers)
+int rng_probe_run(int generator, int stream, int n, int stride, const uint32_t *keys, const int32_t *key_len, const uint8_t *mask,
+                  const uint64_t *state_in, const int32_t *script, int n_ops, const double *args, int n_args, const int32_t *skip,
+                  uint64_t *out, int64_t out_words, uint64_t *state_out, int64_t state_words);
 int kuka_persist_blocks(Handle *h, int *capacity);   // persistent stepping: real workgroups of the resident kernel (0: this handle has no persistent form); capacity: how many the device holds at once
 int kuka_persist_start(Handle *h, const void *d_actions, float *d_obs, float *d_rew, uint8_t *d_done, const PersistArgs &pa);
 

@@ -23,6 +23,7 @@ static long g_clamp_cnt[2];
 #define SRL_GDBG_COUNTS(any, gl, gc, gb) do { if (g_gdbg_on) { g_gdbg[6][0] += 1; g_gdbg[6][1] += (any); g_gdbg[6][2] += (gl); g_gdbg[6][3] += (gc); g_gdbg[6][4] += (gb); } } while (0)
 #include "kuka_group.hpp"
 #include "kuka_tree.hpp"
+#include "rng_probe.hpp"
 
 using namespace srl;
 using namespace srl::kuka;
@@ -603,4 +604,70 @@ extern "C" void hostcheck_kuka_tree_default_model(double *t510) { srl::kuka::Tre
 extern "C" void hostcheck_kuka_tree_set_model(const double *t510) {
     g_tree_model_set = t510 != nullptr;
     if (t510) memcpy(&g_tree_model, t510, sizeof g_tree_model);
+}
+
+
+// =====================================================================================================================
+// The generator self-test (rng_probe.hpp) on the host: srlhip_selftest_rng's arguments (device_id is ignored), the same interpreter
+// text, the group forms under the fiber harness (one env per group: a wavefront-wide vote is the group's vote here).
+namespace {
+struct ProbeFiberArgs { const rngprobe::Args *a; int64_t e; };
+template <int GEN> void probe_group_body(void *p) {
+    ProbeFiberArgs &f = *static_cast<ProbeFiberArgs *>(p);
+    rngprobe::run_script<GEN>(*f.a, f.e, grp::lane_id(), grp::GL);
+}
+}  // namespace
+
+extern "C" int hostcheck_rng_probe(int32_t device_id, int32_t generator, int32_t stream, int32_t n, int32_t stride, const uint32_t *keys,
+                                   const int32_t *key_len, const uint8_t *mask, const uint64_t *state_in, const int32_t *script, int32_t n_ops,
+                                   const double *args, int32_t n_args, const int32_t *skip, uint64_t *out, int64_t out_words, uint64_t *state_out,
+                                   int64_t state_words) {
+    using namespace rngprobe;
+    (void)device_id;
+    const int64_t values = script_values(generator, script, n_ops, args, n_args);
+    if (values < 0 || n < 1 || n > 4096 || !keys || !skip || !out || !state_out || (stream != 0 && stream != 1)) return -22;
+    const bool mt = is_mt(generator), group = is_group(generator);
+    const int lanes = group ? grp::GL : 1, sw = mt ? kMtStateWords : 1;
+    if (mt && (stride < n || stride > 8192 || (!state_in && !key_len))) return -22;
+    if (out_words < (int64_t)n * lanes * values || state_words < (int64_t)n * sw) return -22;
+    for (int e = 0; e < n; e++) if (skip[e] < 0 || skip[e] > kMaxSkip || (mt && !state_in && key_len[e] != 1 && key_len[e] != 2)) return -22;
+    memset(out, 0, sizeof(uint64_t) * (size_t)n * lanes * values);
+    const size_t s = mt ? (size_t)stride : 1;
+    std::vector<uint32_t> words(MT_N * s, 0u); std::vector<int32_t> mti(s, 0), has(s, 0); std::vector<double> gauss(s, 0.0);
+    std::vector<uint64_t> ctr(n, 0);
+    Args a; memset(&a, 0, sizeof a);
+    a.mt = Mt19937View{words.data(), mti.data(), has.data(), gauss.data(), (int64_t)s};
+    a.keys = keys; a.ctr = ctr.data(); a.stream = stream; a.n = n; a.n_ops = n_ops; a.mask = mask; a.script = script; a.args = args;
+    a.skip = skip; a.out = out; a.values = values;
+    for (int e = 0; e < n; e++) {
+        if (!mt) { if (state_in) ctr[e] = state_in[e]; continue; }
+        if (state_in) {
+            const uint64_t *st = state_in + (size_t)e * kMtStateWords;
+            if (st[MT_N] > (uint64_t)MT_N || st[MT_N + 1] > 1) return -22;
+            for (int k = 0; k < MT_N; k++) words[k * s + e] = (uint32_t)st[k];
+            mti[e] = (int32_t)st[MT_N]; has[e] = (int32_t)st[MT_N + 1]; memcpy(&gauss[e], &st[MT_N + 2], 8);
+        } else {                  // as api.hip's mt_seed_k
+            const uint32_t key[2] = {keys[e], keys[n + e]};
+            Mt19937 m; m.load(a.mt, e); m.seed_by_array(key, key_len[e]); m.store(a.mt, e);
+        }
+    }
+    for (int e = 0; e < n; e++) {
+        if (mask && !mask[e]) continue;
+        ProbeFiberArgs f{&a, e};
+        switch (generator) {
+            case GEN_MT: run_script<GEN_MT>(a, e, 0, 1); break;
+            case GEN_PHILOX: run_script<GEN_PHILOX>(a, e, 0, 1); break;
+            case GEN_GROUP_MT: run_group(probe_group_body<GEN_GROUP_MT>, &f); break;
+            case GEN_LANE0_MT: run_group(probe_group_body<GEN_LANE0_MT>, &f); break;
+            case GEN_GROUP_PHILOX: run_group(probe_group_body<GEN_GROUP_PHILOX>, &f); break;
+            default: run_group(probe_group_body<GEN_GROUP_ACTIONS>, &f);
+        }
+    }
+    for (int e = 0; e < n; e++) {
+        if (!mt) { state_out[e] = ctr[e]; continue; }
+        uint64_t *st = state_out + (size_t)e * kMtStateWords;
+        for (int k = 0; k < MT_N; k++) st[k] = words[k * s + e];
+        st[MT_N] = (uint64_t)(uint32_t)mti[e]; st[MT_N + 1] = (uint64_t)(uint32_t)has[e]; memcpy(&st[MT_N + 2], &gauss[e], 8);
+    }
+    return 0;
 }

@@ -6,7 +6,14 @@
 //    Reproduces the stream behind the reference's `self.np_random`
 //    (environments/srl_env.py:71-78 -> gym.utils.seeding.np_random ->
 //    numpy.random.RandomState): random_sample, uniform, normal (polar method
-//    with the cached second deviate), randint (masked rejection).
+//    with the cached second deviate), randint (masked rejection).  Words,
+//    random_sample, uniform, randint, the words a draw consumes and the state
+//    are numpy's bit for bit, on the host and on the device.  The VALUE of a
+//    Gaussian deviate is numpy's bit for bit only in host code (libm); on the
+//    device log / sqrt (Philox: cos too) come from the device math library:
+//    about 1 - 4 % of the deviates differ from numpy's in the last bits, each
+//    within numpy's own worst error + 1 ulp of the exact value (measured by
+//    tests/test_gpu_rng_streams.py, figures in DESIGN.md).
 //  * gym_hash_seed() : gym==0.11.0 seeding.hash_seed (sha512 of str(seed)).
 //  * Philox4x32-10 : counter-based stream for the throughput mode.
 #pragma once
@@ -22,7 +29,8 @@ constexpr int MT_N = 624;
 constexpr int MT_M = 397;
 
 // numpy's derived draws on top of any source of tempered 32-bit words (G::u32()): shared by the per-env generator below and by
-// the lane-group generator of the Kuka kernels (kuka_group.hpp: GroupMt), so that both produce the same stream bit for bit.
+// the lane-group generator of the Kuka kernels (kuka_group.hpp: GroupMt), so that both produce the same stream bit for bit
+// (one device code for both: a Gaussian deviate's value too — against numpy see the header).
 // numpy rk_double / random_sample: 53-bit double in [0, 1)
 template <class G> SRL_HD double mt_double01(G &gen) {
     uint32_t a = gen.u32() >> 5, b = gen.u32() >> 6;

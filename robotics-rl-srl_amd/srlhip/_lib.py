@@ -39,7 +39,7 @@ EXPORTS = [
     "srlhip_obs_bytes", "srlhip_action_dim", "srlhip_num_actions", "srlhip_seed", "srlhip_reset",
     "srlhip_reset_rand_count", "srlhip_step", "srlhip_step_async", "srlhip_step_wait", "srlhip_step_pending", "srlhip_set_persistent", "srlhip_rollout", "srlhip_rollout_policy", "srlhip_rollout_mlp_policy", "srlhip_get_state", "srlhip_set_state",
     "srlhip_device_ptr", "srlhip_render", "srlhip_episode_stats", "srlhip_episode_records", "srlhip_episode_stats_device", "srlhip_sync", "srlhip_copy_async", "srlhip_stream", "srlhip_timing_begin",
-    "srlhip_timing_end", "srlhip_last_error", "srlhip_selftest_group_primitives", "srlhip_kuka_kernel", "srlhip_kuka_default_model", "srlhip_set_kuka_model", "srlhip_kuka_tree_default_model", "srlhip_set_kuka_tree_model",
+    "srlhip_timing_end", "srlhip_last_error", "srlhip_selftest_group_primitives", "srlhip_selftest_rng", "srlhip_kuka_kernel", "srlhip_kuka_default_model", "srlhip_set_kuka_model", "srlhip_kuka_tree_default_model", "srlhip_set_kuka_tree_model",
     "srlhip_graph_begin", "srlhip_graph_end", "srlhip_graph_launch", "srlhip_graph_destroy",
     "srlhip_encoder_supported", "srlhip_encoder_feature_count", "srlhip_encoder_create", "srlhip_encoder_forward", "srlhip_encoder_overflow",
     "srlhip_encoder_phase_cycles",
@@ -151,6 +151,7 @@ def load():
     lib.srlhip_episode_stats_device.argtypes = [vp, vp, vp, vp]
     lib.srlhip_episode_records.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
     lib.srlhip_selftest_group_primitives.argtypes = [i32, vp, vp, i32]
+    lib.srlhip_selftest_rng.argtypes = [i32] * 5 + [vp] * 5 + [i32, vp, i32, vp, vp, ctypes.c_int64, vp, ctypes.c_int64]
     lib.srlhip_kuka_kernel.argtypes = [vp]
     lib.srlhip_kuka_default_model.argtypes = [vp]
     lib.srlhip_set_kuka_model.argtypes = [vp, vp]
