@@ -457,6 +457,7 @@ const srl::kuka::TreeModel *tree_model() {
 double *g_tree_bodies = nullptr;         // KukaRandButton: [n][11][7] body state at the end of the next tree rollout (x y z vx vy vz on)
 uint8_t *g_tree_ik_flag = nullptr; int32_t *g_tree_ik_fin = nullptr;     // IK conditioning flag: [T][n] sticky bit after each step, [n] final Env::ikx
 int g_tree_occ = 0;                      // 1: the two-wavefronts-per-SIMD variant's code path (OCC = 1: shared work area, per-env park, recomputed candidates)
+int g_tree_split = 0;                    // 1: the physics step cut at the action (tphysics_pre2 / tphysics_post2), as the per-step kernels of the default configuration run it
 template <int NB, int RB, int OCC, class R>
 void tree_env_body(GroupArgs &a, R &rng) {
     using namespace tree;
@@ -484,6 +485,10 @@ void tree_env_body(GroupArgs &a, R &rng) {
     double ep_ret = 0, last_ret = 0; int ep_len = 0, last_len = 0, n_fin = 0;
     for (int t = 0; t < T; t++) {
         const size_t row = (size_t)t * n + e_idx;
+        PreStep pre2;                                  // the cut exists for one button, no free bodies, the default solver details
+        bool split = false;
+        if constexpr (NB == 1 && !RB && !OCC) split = g_tree_split && lane_view(tab).detail() == 0;
+        if (split) tphysics_pre2<0>(env, g, tab, a.scratch, pre2);      // everything in front of the action
         int ac = 0; float ca[7] = {0}; bool done;
         if (a.actions) {
             if (cfg.is_discrete) ac = static_cast<const int32_t *>(a.actions)[row];
@@ -497,7 +502,13 @@ void tree_env_body(GroupArgs &a, R &rng) {
             }
             if (a.act_out && lead) { if (cfg.is_discrete) static_cast<int32_t *>(a.act_out)[row] = ac; else memcpy(static_cast<float *>(a.act_out) + row * adim, ca, sizeof(float) * adim); }
         }
-        const double reward = tenv_step<NB, RB, OCC>(env, g, tab, cfg, a.scratch, rng, ac, ca, L.arm ? ca[L.l] : 0.f, &done, &body, park);
+        double reward;
+        if constexpr (NB == 1 && !RB && !OCC) {
+            reward = split ? tenv_step<1, 0, 0, 0, 2>(env, g, tab, cfg, a.scratch, rng, ac, ca, L.arm ? ca[L.l] : 0.f, &done, &body, nullptr, nullptr, &pre2)
+                           : tenv_step<1, 0, 0>(env, g, tab, cfg, a.scratch, rng, ac, ca, L.arm ? ca[L.l] : 0.f, &done, &body, park);
+        } else {
+            reward = tenv_step<NB, RB, OCC>(env, g, tab, cfg, a.scratch, rng, ac, ca, L.arm ? ca[L.l] : 0.f, &done, &body, park);
+        }
         if (a.q_trace && L.arm) a.q_trace[row * ND + L.l] = g.q;
         if (a.grip_trace && lead) memcpy(a.grip_trace + row * 3, env.grip, sizeof(double) * 3);
         if (g_tree_ik_flag && lead) g_tree_ik_flag[row] = (uint8_t)(env.ikx & 1);
@@ -600,6 +611,7 @@ extern "C" int hostcheck_kuka_tree_rollout(int is_discrete, int action_joints, i
 extern "C" void hostcheck_kuka_tree_set_body_trace(double *bodies) { g_tree_bodies = bodies; }
 extern "C" void hostcheck_kuka_tree_set_ik_trace(uint8_t *flag, int32_t *fin) { g_tree_ik_flag = flag; g_tree_ik_fin = fin; }
 extern "C" void hostcheck_kuka_tree_set_occ(int occ) { g_tree_occ = occ; }
+extern "C" void hostcheck_kuka_tree_set_split(int split) { g_tree_split = split; }
 extern "C" void hostcheck_kuka_tree_default_model(double *t510) { srl::kuka::TreeModel m; srl::kuka::default_tree_model(m); memcpy(t510, &m, sizeof m); }
 extern "C" void hostcheck_kuka_tree_set_model(const double *t510) {
     g_tree_model_set = t510 != nullptr;

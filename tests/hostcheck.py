@@ -106,6 +106,13 @@ def tree_default_model():
     return t
 
 
+def tree_set_split(on):
+    """tree_rollout() takes the physics step cut at the action (csrc/kuka_tree.hpp tphysics_pre2 in front of each env step's action,
+    tphysics_post2 behind it) where the per-step kernels of the default configuration do: one button, no free bodies, OCC off, the
+    default solver details.  Off: tphysics_step throughout."""
+    lib().hostcheck_kuka_tree_set_split(int(bool(on)))
+
+
 def tree_set_model(table):
     """Runtime full-model table (510 doubles) for tree_rollout(); None -> the baked model."""
     import numpy as np

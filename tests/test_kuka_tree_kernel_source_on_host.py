@@ -290,3 +290,29 @@ def test_occ_variant_shared_work_area_and_recomputed_candidates(detail, tighten)
         assert ((a["rows"][:, :, 1] // 1000) > 0).sum() > 50
     else:
         assert a["rows"][:, :, 0].sum() > 10
+
+
+# ---- the physics step cut at the action (the per-step kernels of the default configuration)
+@pytest.mark.parametrize("case", ["contacts", "limits", "repeat"])
+def test_split_step_in_front_of_and_behind_the_action(case):
+    """tphysics_pre2 on the state before the action is read, then tenv_step<1, 0, 0, 0, 2> (tphysics_post2, or tphysics_step where the
+    button's motor is not on): the route of the persistent and the given-action launching kernel.  Same trajectories as the oracle:
+    contact + friction steps (the general path's PART = 1 / PART = 2 halves), joint-limit rows with the tightened table and an
+    overflowing row budget, and action_repeat = 2, where an uncut repeat step follows every cut first step."""
+    t = detail_table(0, tighten=case == "limits", budget=3 if case == "limits" else None)
+    try:
+        kuka_clib.set_tree_model(t); hostcheck.tree_set_model(t)
+        hostcheck.tree_set_split(True)
+        if case == "contacts":
+            a = run(6, 900, 5, rng_mode=kuka_clib.RNG_MT19937, random_target=True)
+        elif case == "limits":
+            a = run(4, 600, 91, rng_mode=kuka_clib.RNG_PHILOX, random_target=True)
+        else:
+            a = run(4, 350, 31, rng_mode=kuka_clib.RNG_MT19937, random_target=True, action_repeat=2)
+    finally:
+        hostcheck.tree_set_split(False)
+        hostcheck.tree_set_model(None); kuka_clib.set_full(True)
+    if case == "contacts":
+        assert a["rows"][:, :, 0].sum() > 10 and a["rows"][:, :, 1].sum() > 10 and a["done"].sum() >= 4
+    elif case == "limits":
+        assert ((a["rows"][:, :, 1] // 1000) > 0).sum() > 50
