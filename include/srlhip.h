@@ -330,6 +330,57 @@ int srlhip_device_ptr(srlhip_handle h, int32_t field, void **dptr);
  * cfg.obs_mode == SRLHIP_OBS_RAW_PIXELS.  img_out follows cfg.io_device. */
 int srlhip_render(srlhip_handle h, void *img_out);
 
+/* ---- JPEG encoding of device-resident frames (dataset recording) ------------------------------------------------------------
+ * Replaces the per-frame cv2.imwrite of the recorder (state_representation/episode_saver.py saveImage; here Pillow's
+ * save(quality=95) in srlhip/recorder.py) and the copy of every raw frame to the host in front of it, for a whole batch.
+ * images_dev uint8 [n][H][W][C] on device_id, H and W in 8..1024, C = 3 -> one stream per frame, C = 6 (multi_view / fpv) -> two:
+ * stream 2i = channels 0..2 of frame i, stream 2i + 1 = channels 3..5 (the recorder's _1.jpg / _2.jpg).  n_streams = n * C / 3.
+ * blob_dev needs n_streams * cap_per_stream bytes; stream s is blob_dev[offsets_dev[s] .. offsets_dev[s + 1]) — the streams are packed
+ * back to back, bytes at and past offsets_dev[n_streams] are never written.  A stream larger than cap_per_stream is not written:
+ * overflow_dev[s] = 1 (else 0) and its length in offsets_dev is 0.  The call only enqueues (three launches) on hip_stream (NULL = the
+ * default stream), allocates nothing and may be captured into a graph.  SRLHIP_EINVAL: quality outside 1..100, C not 3 or 6, a side
+ * outside 8..1024, a null buffer.
+ *
+ * FORMAT: baseline sequential JFIF that every libjpeg reads — SOI, APP0 (JFIF 1.01, no units, 1:1), DQT 0 and 1 (8-bit), SOF0 (Y 2x2,
+ * Cb 1x1, Cr 1x1: 4:2:0), DHT DC0 AC0 DC1 AC1 (the Annex K.3 tables), DRI = 1 MCU, SOS, entropy-coded data, EOI:
+ * srlhip_jpeg_header_bytes() = 629 bytes in front of the data.  Every 16x16 MCU is followed by RSTm (m = MCU index mod 8), the last one
+ * by EOI, so every MCU starts byte-aligned from DC predictor 0.  The last byte of an MCU is padded with 1-bits; 0x00 follows every
+ * 0xFF of the data.  MCU order: rows top to bottom, left to right; inside an MCU Y0 Y1 (top) Y2 Y3 (bottom), Cb, Cr.
+ *
+ * ARITHMETIC CONTRACT (integers only; csrc/jpeg.hpp is its one implementation for device and host, tests/jpeg_ref.py restates it in
+ * numpy; >> is an arithmetic shift, / truncates):
+ *   padding   pixel (y, x) past the frame reads pixel (min(y, H - 1), min(x, W - 1))
+ *   colour    Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *             Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *             Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16          (all within 0..255, no clamp needed)
+ *   chroma    the Cb (Cr) of a 2x2 cell is (a + b + c + d + 2) >> 2 of its four pixels' Cb (Cr), taken after the padding
+ *   shift     every sample - 128
+ *   DCT       K[u][x] = round(4096 s(u) cos((2x + 1) u pi / 16)), s(0) = 1 / sqrt 2, s(u > 0) = 1: K[0][x] = 2896, the other rows hold
+ *             +- 4017 3784 3406 2896 2276 1567 799.  Rows first: r[y][u] = (sum_x K[u][x] p[y][x] + 2^8) >> 9 (16 x the orthonormal
+ *             1-D transform, |r| <= 8034); then columns: c[v][u] = (sum_y K[v][y] r[y][u] + 2^13) >> 14 — c is 8 x the orthonormal
+ *             2-D DCT, the scale libjpeg's integer DCT hands its quantiser.  All sums are exact in int32 (< 2^28).
+ *   quantiser t = clamp((base * scale + 50) / 100, 1, 255), base = the Annex K.1 (Y) / K.2 (Cb, Cr) entry, scale = 5000 / quality for
+ *             quality < 50, else 200 - 2 quality (libjpeg's rule); with d = 8 t:  q = sign(c) * ((|c| + d / 2) / d)  (half away from zero)
+ *   coding    zigzag order; DC: difference to the previous block of the component INSIDE the MCU (Y0 -> Y1 -> Y2 -> Y3 from 0; Cb and Cr
+ *             from 0), category code + category bits; AC: (run, category) codes, ZRL for every 16 zeros in front of a non-zero
+ *             coefficient, EOB when the block ends in zeros; negative values v as the low bits of v - 1. */
+int srlhip_jpeg_encode(int32_t device_id, const uint8_t *images_dev, int32_t n, int32_t img_h, int32_t img_w, int32_t n_channels,
+                       int32_t quality, uint8_t *blob_dev, int64_t cap_per_stream, int64_t *offsets_dev, int32_t *overflow_dev,
+                       void *hip_stream);
+/* srlhip_render + srlhip_jpeg_encode on the handle's stream: rasterises the CURRENT state of every env into the handle's scratch exactly
+ * as srlhip_render does and encodes those frames (num_envs streams, 2 num_envs with multi_view / fpv).  Pointers follow cfg.io_device;
+ * cap_per_stream = blob_cap / n_streams.  A host-pointer handle copies offsets_out [n_streams + 1] and overflow_out [n_streams] first,
+ * then only the offsets_out[n_streams] bytes of blob that were written.  SRLHIP_EINVAL while a srlhip_step_async is pending; a
+ * resident kernel parks. */
+int srlhip_render_jpeg(srlhip_handle h, int32_t quality, void *blob_out, int64_t blob_cap, int64_t *offsets_out, int32_t *overflow_out);
+/* Host only: the size of the header in front of the entropy-coded data (the smallest stream is this + one MCU + EOI). */
+size_t srlhip_jpeg_header_bytes(void);
+/* Host only, no GPU needed: ONE stream through the same source on the CPU (pixel (y, x) at image + (y * img_w + x) * pix_stride, three
+ * bytes R G B; pix_stride >= 3) — so that the arithmetic above can be checked without a device.  *len = the stream's size; when it
+ * exceeds cap nothing is written and the call returns SRLHIP_ENOMEM. */
+int srlhip_jpeg_encode_host(const uint8_t *image, int32_t img_h, int32_t img_w, int32_t pix_stride, int32_t quality, uint8_t *out,
+                            size_t cap, size_t *len);
+
 /* Per-env statistics of the most recently FINISHED episode and the number of
  * finished episodes: what stable_baselines.bench.Monitor records
  * (environments/utils.py:54).  HOST pointers, any may be NULL. */

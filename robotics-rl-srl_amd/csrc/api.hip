@@ -366,7 +366,7 @@ int srlhip_destroy(srlhip_handle hh) {
     if (h->persist_stage) (void)hipFree(h->persist_stage);
     if (h->kuka) kuka_free(h);
     for (void *p : h->allocs) (void)hipFree(p);
-    void *st[] = {h->st_actions, h->st_noise, h->st_obs, h->st_rew, h->st_done, h->st_mask, h->st_rand};
+    void *st[] = {h->st_actions, h->st_noise, h->st_obs, h->st_rew, h->st_done, h->st_mask, h->st_rand, h->st_jpeg};
     for (void *p : st) if (p) (void)hipFree(p);
     for (void *p : h->act_plane) if (p) (void)hipFree(p);
     if (h->pin_in) (void)hipHostFree(h->pin_in);
@@ -910,6 +910,38 @@ int srlhip_render(srlhip_handle hh, void *img_out) {
     if (!h->cfg.io_device) {
         SRL_HIP_CHECK(h, hipMemcpyAsync(img_out, d_img, bytes, hipMemcpyDeviceToHost, h->stream));
         SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    }
+    return 0;
+}
+
+int srlhip_render_jpeg(srlhip_handle hh, int32_t quality, void *blob_out, int64_t blob_cap, int64_t *offsets_out, int32_t *overflow_out) {
+    if (!hh) return SRLHIP_EINVAL;
+    Handle *h = reinterpret_cast<Handle *>(hh);
+    if (!blob_out || !offsets_out || !overflow_out || blob_cap < 0) return h->fail(SRLHIP_EINVAL, "render_jpeg: null buffer");
+    if (quality < 1 || quality > 100) return h->fail(SRLHIP_EINVAL, "render_jpeg: quality must be in 1..100");
+    if (h->step_pending) return h->fail(SRLHIP_EINVAL, "render_jpeg: a srlhip_step_async is pending (call srlhip_step_wait first)");
+    int rc = set_device(h);                            // (parks a resident kernel)
+    if (rc) return rc;
+    const int ch = h->cfg.multi_view ? 6 : 3;
+    const size_t ns = (size_t)h->n * (ch / 3), frames = ((size_t)h->cfg.img_h * h->cfg.img_w * ch * h->n + 15) & ~(size_t)15;
+    const int64_t cap = blob_cap / (int64_t)ns;
+    // scratch: the frames; on a host-pointer handle also offsets [ns + 1], overflow [ns] and the blob's ns slots of `cap` bytes
+    const size_t off_at = frames, ovf_at = off_at + 8 * (ns + 1), blob_at = (ovf_at + 4 * ns + 15) & ~(size_t)15;
+    if ((rc = ensure(h, &h->st_jpeg, &h->st_jpeg_sz, h->cfg.io_device ? frames : blob_at + (size_t)cap * ns))) return rc;
+    uint8_t *d = static_cast<uint8_t *>(h->st_jpeg);
+    if ((rc = raster_render(h, d))) return rc;
+    uint8_t *d_blob = h->cfg.io_device ? static_cast<uint8_t *>(blob_out) : d + blob_at;
+    int64_t *d_off = h->cfg.io_device ? offsets_out : reinterpret_cast<int64_t *>(d + off_at);
+    int32_t *d_ovf = h->cfg.io_device ? overflow_out : reinterpret_cast<int32_t *>(d + ovf_at);
+    if ((rc = jpeg_encode_launch(d, h->n, h->cfg.img_h, h->cfg.img_w, ch, quality, d_blob, cap, d_off, d_ovf, h->stream)))
+        return h->fail(rc, "render_jpeg: frames of 8..1024 pixels a side only, or the launch failed");
+    if (!h->cfg.io_device) {
+        SRL_HIP_CHECK(h, hipMemcpyAsync(offsets_out, d_off, 8 * (ns + 1), hipMemcpyDeviceToHost, h->stream));
+        SRL_HIP_CHECK(h, hipMemcpyAsync(overflow_out, d_ovf, 4 * ns, hipMemcpyDeviceToHost, h->stream));
+        SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+        const int64_t used = offsets_out[ns];
+        if (used < 0 || used > blob_cap) return h->fail(SRLHIP_EHIP, "render_jpeg: the encoder reported an impossible size");
+        if (used) SRL_HIP_CHECK(h, hipMemcpy(blob_out, d_blob, (size_t)used, hipMemcpyDeviceToHost));
     }
     return 0;
 }

@@ -115,6 +115,10 @@ int raster_render(Handle *h, void *d_img);
 struct RasterGripJoint { double parent, xyz[3], Rj[9], axis[3]; };
 struct RasterKukaView { const double *sq, *cq, *bq, *bx, *by, *bz, *b2q, *b2x, *b2y, *objs, *rb, *gsq, *gcq; RasterGripJoint gj[5]; const float *grip; int64_t n; int32_t two, rand_objects, has_tm; };
 
+// jpeg.hip: srlhip_jpeg_encode behind its argument checks: three launches on `stream`, no allocation, no synchronisation (0 or SRLHIP_E*)
+int jpeg_encode_launch(const uint8_t *images_dev, int n, int img_h, int img_w, int n_channels, int quality, uint8_t *blob_dev,
+                       int64_t cap_per_stream, int64_t *offsets_dev, int32_t *overflow_dev, hipStream_t stream);
+
 struct KukaState;   // defined in kuka.hip
 
 struct Handle {
@@ -159,6 +163,8 @@ struct Handle {
     float4 *raster_rays[2];
     uint32_t *raster_bg[2];
     float *raster_grip = nullptr;         // [42][n] full Kuka model: the gripper capsules' end points, then the arm's joint origins (raster_grip_k, refreshed by every render)
+    void *st_jpeg = nullptr;         // srlhip_render_jpeg on a host-pointer handle: blob, then offsets, then overflow flags (grow-only)
+    size_t st_jpeg_sz = 0;
     void *pin_in, *pin_out;          // pinned host bounce buffers of srlhip_step (host-pointer mode)
     // host-pointer handles (io_device = 0): stats.last_return / last_length live in ONE mapped pinned host block ([n] f64, then [n] i32)
     // that the kernels address directly, so the per-step API reads an ended episode's (r, l) without a device copy (srlhip_episode_records)

@@ -73,6 +73,24 @@ class _Fleet(object):
     def render(self):
         return np.concatenate([h.render() for h, _, _ in self.parts])
 
+    def render_jpeg(self, lanes):
+        """--device-jpeg: every lane's frame as encoded on its GPU (srlhip_render_jpeg, quality 95 like the recorder's Pillow path) ->
+        what EpisodeSaver.saveImage takes per lane: bytes, or a pair of bytes with two views.  A stream that did not fit its slot
+        falls back to render() + Pillow for that lane alone; `lanes` = the lanes the caller will save."""
+        views = 2 if self.cfg.multi_view else 1
+        out, raw = [], {}
+        for h, lo, hi in self.parts:
+            streams = h.render_jpeg(quality=95)
+            for i in range(hi - lo):
+                mine = streams[views * i:views * (i + 1)]
+                if any(s is None for s in mine) and (lo + i) in lanes:
+                    if lo not in raw:
+                        raw[lo] = h.render()
+                    out.append(raw[lo][i])
+                else:
+                    out.append(mine[0] if views == 1 else tuple(mine))
+        return out
+
     def ground_truth_and_target(self):
         if self.kuka:
             return self._cat(_lib.F_KUKA_GRIPPER).T.copy(), self._cat(_lib.F_KUKA_BUTTON_POS).T.copy()
@@ -130,7 +148,7 @@ def run_batched(args):
         fleet.seed_and_reset(sd, mask)
         if savers is not None:
             gt, tgt = fleet.ground_truth_and_target()
-            frames_rgb = fleet.render()
+            frames_rgb = fleet.render_jpeg(set(np.nonzero(mask)[0])) if getattr(args, "device_jpeg", False) else fleet.render()
             for i in np.nonzero(mask)[0]:
                 savers[i].reset(frames_rgb[i], tgt[i], gt[i])
         t_ep[mask] = 0
@@ -152,7 +170,7 @@ def run_batched(args):
         if savers is not None:
             gt, _ = fleet.ground_truth_and_target()
             rew = fleet.last_reward()
-            frames_rgb = fleet.render()
+            frames_rgb = fleet.render_jpeg(set(np.nonzero(active)[0])) if getattr(args, "device_jpeg", False) else fleet.render()
             for i in np.nonzero(active)[0]:
                 r = float(rew[i]) if args.shape_reward else int(rew[i])
                 a = int(actions[i]) if cfg.is_discrete else actions[i]
@@ -195,6 +213,7 @@ _FLAGS = [
     (("--device-id",), dict(type=int, default=0, help="HIP device ordinal")),
     (("--device-ids",), dict(type=str, default=None, help="GPUs the --num-cpu lanes are spread over: 'all' or e.g. 0,1,2,3 (default: --device-id only)")),
     (("--img-size",), dict(type=int, default=224, help="recorded frame size (reference: 224)")),
+    (("--device-jpeg",), dict(action="store_true", help="encode the recorded frames to JPEG on the GPU (srlhip_render_jpeg) instead of copying raw frames to the host for Pillow")),
 ]
 
 

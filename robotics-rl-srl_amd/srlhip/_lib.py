@@ -44,6 +44,7 @@ EXPORTS = [
     "srlhip_encoder_supported", "srlhip_encoder_feature_count", "srlhip_encoder_create", "srlhip_encoder_forward", "srlhip_encoder_overflow",
     "srlhip_encoder_phase_cycles",
     "srlhip_encoder_destroy", "srlhip_encoder_last_error", "srlhip_encoder_pack_bytes", "srlhip_encoder_pack", "srlhip_encoder_pack_i8_bytes", "srlhip_encoder_pack_i8", "srlhip_encoder_pack_first_layer",
+    "srlhip_jpeg_encode", "srlhip_render_jpeg", "srlhip_jpeg_header_bytes", "srlhip_jpeg_encode_host",
 ]
 
 
@@ -182,6 +183,11 @@ def load():
     lib.srlhip_encoder_pack_i8_bytes.argtypes = []
     lib.srlhip_encoder_pack_i8.argtypes = [vp, vp, i32, vp, ctypes.c_size_t, vp]
     lib.srlhip_encoder_pack_first_layer.argtypes = [i32, vp, vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_float)]
+    lib.srlhip_jpeg_encode.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, ctypes.c_int64, vp, vp, vp]
+    lib.srlhip_render_jpeg.argtypes = [vp, i32, vp, ctypes.c_int64, vp, vp]
+    lib.srlhip_jpeg_header_bytes.restype = ctypes.c_size_t
+    lib.srlhip_jpeg_header_bytes.argtypes = []
+    lib.srlhip_jpeg_encode_host.argtypes = [vp, i32, i32, i32, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     _lib = lib
     return lib
 
@@ -419,6 +425,18 @@ class Handle(object):
         self._check(self._lib.srlhip_render(self._h, _ptr(out)), "srlhip_render")
         return out
 
+    def render_jpeg(self, quality=95, cap_per_stream=None):
+        """srlhip_render_jpeg on a host-pointer handle: the current frame of every env as a baseline JPEG stream, encoded on the device
+        -> list of bytes, num_envs of them (multi_view / fpv: 2 * num_envs, env i's two cameras at 2i and 2i + 1).  A stream larger
+        than cap_per_stream (default 1024 + H * W * 3) comes back as None."""
+        assert not self.cfg.io_device, "render_jpeg returns host bytes: device-pointer handles call srlhip_render_jpeg with their own buffers"
+        ns = self.num_envs * (2 if self.cfg.multi_view else 1)
+        cap = int(cap_per_stream) if cap_per_stream is not None else 1024 + self.cfg.img_h * self.cfg.img_w * 3
+        blob, offsets, overflow = np.empty(ns * cap, np.uint8), np.zeros(ns + 1, np.int64), np.zeros(ns, np.int32)
+        self._check(self._lib.srlhip_render_jpeg(self._h, int(quality), _ptr(blob), ctypes.c_int64(blob.nbytes), _ptr(offsets), _ptr(overflow)),
+                    "srlhip_render_jpeg")
+        return split_streams(blob, offsets, overflow)
+
     def set_kuka_model(self, table):
         """Install a runtime model table (srlhip_kuka_model: 138 float64, see srlhip.kuka_model) — reset() afterwards."""
         t = np.ascontiguousarray(table, dtype=np.float64)
@@ -568,6 +586,38 @@ def none_rows(actions, dim, lead_ndim=1):
             return nan_row if x is None else np.asarray(x, dtype=np.float32).reshape(dim)
         return np.stack([rows(y, depth - 1) for y in x]) if len(x) else np.zeros((0, dim), np.float32)
     return rows(actions, lead_ndim)
+
+
+def split_streams(blob, offsets, overflow):
+    """(blob, offsets [ns + 1], overflow [ns]) of srlhip_jpeg_encode / srlhip_render_jpeg as host arrays -> list of bytes, None where a stream overflowed"""
+    return [None if overflow[s] else blob[offsets[s]:offsets[s + 1]].tobytes() for s in range(len(overflow))]
+
+
+def jpeg_header_bytes():
+    return int(load().srlhip_jpeg_header_bytes())
+
+
+def jpeg_encode(images_dev_ptr, n, h, w, c, quality, blob_dev_ptr, cap_per_stream, offsets_dev_ptr, overflow_dev_ptr, device_id=0, stream=0):
+    """srlhip_jpeg_encode, raw: device pointers (uint8 [n][h][w][c] frames in; blob of n * c / 3 * cap_per_stream bytes, int64 offsets
+    [n * c / 3 + 1], int32 overflow [n * c / 3] out); only enqueues on `stream`.  Returns the library's status code."""
+    return load().srlhip_jpeg_encode(int(device_id), _ptr(images_dev_ptr), int(n), int(h), int(w), int(c), int(quality), _ptr(blob_dev_ptr),
+                                     ctypes.c_int64(cap_per_stream), _ptr(offsets_dev_ptr), _ptr(overflow_dev_ptr),
+                                     ctypes.c_void_p(stream) if stream else None)
+
+
+def jpeg_encode_host(frame, quality, cap=None):
+    """srlhip_jpeg_encode_host: one uint8 [h][w][3] frame (any pixel stride: a 3-channel view of a 6-channel frame passes as it is)
+    through the kernels' own source on the CPU -> bytes; raises SrlHipError on a refusal."""
+    frame = np.asarray(frame)
+    assert frame.dtype == np.uint8 and frame.ndim == 3 and frame.shape[2] == 3 and frame.strides[2] == 1
+    h, w = frame.shape[:2]
+    assert frame.strides[0] == w * frame.strides[1], "rows must follow each other without padding"
+    cap = int(cap) if cap is not None else 1024 + 4 * h * w * 3
+    out, n = np.zeros(cap, np.uint8), ctypes.c_size_t(0)
+    rc = load().srlhip_jpeg_encode_host(ctypes.c_void_p(frame.ctypes.data), h, w, int(frame.strides[1]), int(quality), _ptr(out), cap, ctypes.byref(n))
+    if rc:
+        raise SrlHipError("srlhip_jpeg_encode_host failed ({}), stream size {}".format(rc, n.value))
+    return out[:n.value].tobytes()
 
 
 def encoder_supported(img_h, img_w, n_channels):

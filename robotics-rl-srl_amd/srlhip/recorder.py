@@ -2,7 +2,7 @@
 same folder layout and npz keys that srl_zoo trains from —
   <path>/<name>/record_XXX/frameNNNNNN.jpg, preprocessed_data.npz{rewards, actions, episode_starts},
   ground_truth.npz{target_positions, ground_truth_states, images_path}, dataset_config.json, env_globals.json.
-JPEGs are written with Pillow (cv2 is not installed); like the reference (which runs
+JPEGs are written with Pillow (cv2 is not installed) — or arrive already encoded from the device (srlhip_render_jpeg); like the reference (which runs
 cv2.COLOR_BGR2RGB on an RGB array before cv2.imwrite) the stored file is the RGB frame."""
 import json
 import os
@@ -40,6 +40,14 @@ class EpisodeSaver(object):
     def saveImage(self, observation):
         image_path = "{}/{}/frame{:06d}".format(self.data_folder, self.episode_folder, self.episode_step)
         self.images_path.append("{}/{}/frame{:06d}".format(self.name, self.episode_folder, self.episode_step))
+        if isinstance(observation, bytes) or (isinstance(observation, (tuple, list)) and len(observation) == 2 and
+                                              all(isinstance(o, bytes) for o in observation)):
+            # already encoded (Handle.render_jpeg): one stream, or the two views of a multi_view frame — written as they are
+            views = [observation] if isinstance(observation, bytes) else observation
+            for k, data in enumerate(views):
+                with open("{}{}.jpg".format(image_path, "" if len(views) == 1 else "_{}".format(k + 1)), "wb") as f:
+                    f.write(data)
+            return
         if observation is None or np.size(observation) == 0:
             return                                  # ground-truth-only recording (no rasteriser output)
         from PIL import Image
