@@ -38,14 +38,6 @@ __global__ void key_seed_k(RngState r, int n, const uint8_t *mask, const uint32_
     r.ctr[e] = 0; r.act_ctr[e] = 0;
 }
 
-int ensure(Handle *h, void **buf, size_t *cap, size_t bytes) {
-    if (*cap >= bytes) return 0;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr; *cap = 0;
-    SRL_HIP_CHECK(h, hipMalloc(buf, bytes));
-    *cap = bytes;
-    return 0;
-}
 int ensure_pinned(Handle *h, void **buf, size_t *cap, size_t bytes) {
     if (*cap >= bytes) return 0;
     if (*buf) (void)hipHostFree(*buf);

@@ -46,11 +46,19 @@ struct MobileParams {
     int32_t n;
 };
 
+// Everything mobile_rollout_ep_k's segment lanes read from the per-env state, as planes of their own (mobile.hip).  Passed to kernels
+// BY VALUE.  An all-null set as a destination: write nowhere.
+struct MobileSnapSet {
+    MobileState s;
+    uint64_t *ctr, *actr;        // rng.ctr, rng.act_ctr
+    double *ep_return;           // stats.ep_return, stats.ep_length
+    int32_t *ep_length;
+};
+
 struct Handle;
 
 // mobile.hip
 int mobile_alloc(Handle *h);
-void mobile_free(Handle *h);
 int mobile_reset(Handle *h, const uint8_t *d_mask, const double *d_host_rand, float *d_obs);
 int mobile_step(Handle *h, const void *d_actions, const double *d_noise, float *d_obs, float *d_rew,
                 uint8_t *d_done);
@@ -130,24 +138,15 @@ struct Handle {
     RngState rng;
     EpisodeStats stats;
     MobileState mobile;
-    // read-only snapshot of everything mobile_rollout_ep_k's segment lanes read from the live state (taken by a copy kernel
-    // right before the launch): a lane may start after the lane that writes its env's final state has retired
-    MobileState mobile_snap = {};
-    uint64_t *snap_ctr = nullptr;
-    double *snap_ep_return = nullptr;
-    int32_t *snap_ep_length = nullptr;
-    // ... and its twin (round 5): the lane that leaves an env's final state also writes it into the OTHER snapshot set, which the next
-    // rollout launch reads — back-to-back rollouts need no mobile_snapshot_k launch (4.8 us of a 52 us rollout).  snap_cur = the set the
-    // next launch reads; snap_valid = that set equals the live state (cleared by everything else that touches the state)
-    MobileState mobile_snap2 = {};
-    uint64_t *snap2_ctr = nullptr, *snap2_actr = nullptr;
-    double *snap2_ep_return = nullptr;
-    int32_t *snap2_ep_length = nullptr;
+    // Two snapshot sets in turn.  A rollout launch reads set snap_cur — a lane may start after the lane that writes its env's final
+    // state has retired, so the lanes never read the live state — and the lane that leaves an env's final state also writes it into the
+    // other set, which the next launch reads: back-to-back rollouts need no mobile_snapshot_k launch.  snap_valid = set snap_cur equals
+    // the live state (cleared by everything else that touches the state)
+    MobileSnapSet snap[2] = {};
     int snap_cur = 0;
     bool snap_valid = false;
     // synthetic-agent rollouts of the MobileRobot family: the [T][N] action plane of the NEXT rollout is drawn by spare workgroups
     // of the current rollout's launch (mobile_rollout_ep_k), from the action-stream counters in the snapshot; two planes in turn
-    uint64_t *snap_actr = nullptr;
     void *act_plane[2] = {nullptr, nullptr};
     size_t act_plane_sz[2] = {0, 0};
     bool prefetch_valid = false;
@@ -207,6 +206,16 @@ struct Handle {
         if (e__ != hipSuccess)                                                                     \
             return (h)->fail(SRLHIP_EHIP, std::string(#expr ": ") + hipGetErrorString(e__));       \
     } while (0)
+
+// a grow-only device buffer: at least `bytes` at *buf afterwards (contents are not kept; the caller orders the free against the stream)
+inline int ensure(Handle *h, void **buf, size_t *cap, size_t bytes) {
+    if (*cap >= bytes) return 0;
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr; *cap = 0;
+    SRL_HIP_CHECK(h, hipMalloc(buf, bytes));
+    *cap = bytes;
+    return 0;
+}
 
 inline int obs_dim_of(const srlhip_config &c) {
     switch (c.env_kind) {

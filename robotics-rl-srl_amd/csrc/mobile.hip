@@ -1,35 +1,35 @@
-// mobile.hip — MobileRobot family stepper for gfx950 (MI355X).
+// mobile.hip — the MobileRobot family (MobileRobotGymEnv, 1D, 2Target, LineTarget) for gfx950 (MI355X).
 //
 // Replaces, for a whole batch of envs per launch:
-//   reset   mobile_robot_env.py:159-222 (+ variants: 1D :58-74, 2Target :35-67,
-//           LineTarget :56-64) — only the RNG draws and state init; every
-//           pybullet call on this path is scene loading / rendering.
+//   reset   mobile_robot_env.py:159-222 (+ variants: 1D :58-74, 2Target :35-67, LineTarget :56-64) — only the RNG draws and the
+//           state init; every pybullet call on this path is scene loading / rendering.
 //   step    mobile_robot_env.py:235-280, _reward :345-363, _termination :336-343
 //           (2Target reward :162-181, LineTarget reward :108-125, 1D step :108-147)
 //
-// Mapping: one lane per env, structure-of-arrays state (env index fastest) so
-// a wavefront's 64 loads/stores of a field are one coalesced 512-byte row.
-// Arithmetic is float64 with -ffp-contract=off, the reference's numpy f64; the
-// only fused op is the explicit fma chain of np.linalg.norm's ddot (see
-// step_env()).  ~40 flops per env-step: the path is HBM/launch bound, no LDS, no
-// MFMA.  mobile_rollout_k keeps the state in VGPRs for T steps and streams the
-// [T][N] observation / reward / done planes with non-temporal stores.
+// One lane per env, structure-of-arrays state (env index fastest: a wavefront's 64 loads / stores of a field are one coalesced
+// 512-byte row).  Arithmetic is float64 with -ffp-contract=off, the reference's numpy f64; the only fused op is the explicit fma
+// chain of np.linalg.norm's ddot (step_env).  ~40 flops per env-step, no LDS, no MFMA: every kernel here is bound by launch and
+// memory latency or by the issue stream of one wavefront's recurrence (measurements: profiles/NOTES.md sections I, Y, AD, AE, AM).
 //
-// The sequential part of a rollout is only the state recurrence.  The synthetic agent's actions do not depend
-// on the state, so they are drawn by a separate, fully parallel kernel (mobile_sample_actions_k: one thread per
-// (step, env), Philox is random access) into the [T][N] action plane; the recurrence kernel then reads them one
-// step ahead of use (software-pipelined load) and is specialised at compile time on the env kind and the action type.
-// At the 4096-env BASELINE size only 64 wavefronts exist, so the launch time is T x (cycles per step of one
-// wavefront): taking the 10-round Philox block out of that chain is what matters — and so is cutting the chain
-// itself: with counter-based streams the episodes of an env are independent of each other, so a T-step rollout runs
-// as ceil(T / 251) + 1 segments per env on separate lanes (mobile_rollout_ep_k below).
-// Round 4: what is left is the issue stream of ONE wavefront over 251 steps, so the step was cut from ~200 to 57 instructions —
-// the shaped reward's float64 square root is a template parameter (with a run-time flag it was evaluated every step and
-// selected away), interior steps run in straight-line chunks of 8 (no per-step predicate, no reset body to branch around, no
-// plane checks; the next chunk's actions are requested ahead of the chunk's stores), and the sampler workgroups index the plane
-// without 64-bit divisions: 0.095 -> 0.053 ms per 4096-env x 2048-step rollout with the synthetic agent (of which ~15 us are the
-// sampler workgroups' 8.4 M Philox blocks sharing the SIMDs), 0.0375 ms with caller-supplied actions
-// (profiles/probes/mobile_chain_probe.py, profiles/r04_mobile_*).
+// One definition each of reset_env / step_env / observe (the env), EpisodeLane (Monitor's accounting), store_step (an output row),
+// gather_actions (actions from a plane) and policy_input / policy_action (a policy's action) serves every kernel below:
+//
+//   kernel                    actions come from                          RNG modes            entry point
+//   mobile_reset_k            —                                          host, Philox, MT     srlhip_reset
+//   mobile_sample_actions_k   (draws the synthetic agent's [T][N] plane, Philox stream 1 of the env, in every device RNG mode)
+//   mobile_rollout_k          a [T][N] plane: the caller's or sampled    host (T = 1), Philox, MT   srlhip_step, srlhip_rollout
+//   mobile_rollout_ep_k       the same plane, episodes on separate lanes Philox + auto_reset, T >= 32   srlhip_rollout
+//   mobile_rollout_policy_k   a linear policy of the env's observation   Philox, MT           srlhip_rollout_policy
+//   mobile_rollout_mlp_k      a one-hidden-layer MLP of it, 16 lanes/env Philox, MT           srlhip_rollout_mlp_policy
+//   mobile_persist_k          the host's mapped plane, one step per token Philox, MT          srlhip_set_persistent + srlhip_step
+//
+// Bit identity (all of it tested): mobile_rollout_k is oracle/mobile_oracle.c, step for step, in every RNG mode.
+// mobile_rollout_ep_k leaves the outputs, final state, counters and episode fields mobile_rollout_k leaves for the same plane.
+// The two policy kernels replayed through mobile_rollout_k with their recorded actions as a given plane reproduce themselves, and
+// their scores are numpy's float64 expressions (tests/policy_exact.py).  mobile_persist_k is T = 1 launches of mobile_rollout_k.
+// A T-step launch equals T single-step launches, episode fields included (tests/test_gpu_mobile_episode_fields.py).
+#include <type_traits>
+
 #include "internal.hpp"
 
 namespace srl {
@@ -203,15 +203,51 @@ __device__ __forceinline__ void step_env(const MobileParams &pp, MobileEnv &m, i
     done = m.counter > 250;                           // terminated is never set (:336-343)
 }
 
-__device__ __forceinline__ void account(const EpisodeStats &st, int e, double reward, bool done) {
-    double r = st.ep_return[e] + reward;
-    int32_t l = st.ep_length[e] + 1;
-    st.last_reward[e] = reward;
-    if (done) {
-        st.last_return[e] = r; st.last_length[e] = l; st.n_finished[e] += 1;
-        r = 0.0; l = 0;
+// Register copy of one env's episode accounting (EpisodeStats: bench.Monitor) for the length of a launch.  What follows an ended
+// episode — a reset, a frozen policy — stays with the caller.
+struct EpisodeLane {
+    double ep_ret = 0.0, last_ret = 0.0, last_reward = 0.0;
+    int32_t ep_len = 0, last_len = 0, n_fin = 0, n_fin0 = 0;
+    __device__ __forceinline__ void load(const EpisodeStats &st, int e) {
+        ep_ret = st.ep_return[e]; ep_len = st.ep_length[e]; n_fin = n_fin0 = st.n_finished[e];
     }
-    st.ep_return[e] = r; st.ep_length[e] = l;
+    __device__ __forceinline__ void add(double reward) { ep_ret += reward; ep_len += 1; last_reward = reward; }     // a step that ends no episode
+    // a step; on_end() — the caller's reset, its frozen flag — runs inside the branch that closes the episode.  (One branch: with a
+    // returned flag and a second `if` at the call site, mobile_rollout_k's 16-step chunks were unrolled by 8 only and their action
+    // arrays went to scratch — profiles/NOTES.md section AM.)
+    template <class F>
+    __device__ __forceinline__ void step(double reward, bool done, F &&on_end) {
+        add(reward);
+        if (done) { last_ret = ep_ret; last_len = ep_len; n_fin += 1; ep_ret = 0.0; ep_len = 0; on_end(); }
+    }
+    __device__ __forceinline__ bool ended() const { return n_fin != n_fin0; }     // an episode ended since load()
+    // Monitor's record at system scope, for a host that reads it while the launch is still running (the step signal, the resident kernel)
+    __device__ __forceinline__ void publish(const EpisodeStats &st, int e) const {
+        __hip_atomic_store(st.last_return + e, last_ret, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(st.last_length + e, last_len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    // Monitor's record of the last finished episode (last_return, last_length) is written only when an episode ended in this launch
+    // and is never read: on host-pointer handles those two planes are mapped host memory — srlhip_episode_records — and a read or an
+    // unconditional write-back would cross PCIe in every launch.  LAST = false: the caller has publish()ed every record already.
+    template <bool LAST = true>
+    __device__ __forceinline__ void store(const EpisodeStats &st, int e) const {
+        st.ep_return[e] = ep_ret; st.ep_length[e] = ep_len;
+        if (LAST && ended()) { st.last_return[e] = last_ret; st.last_length[e] = last_len; }
+        st.n_finished[e] = n_fin; st.last_reward[e] = last_reward;
+    }
+};
+
+// One row of the streamed [T][n] output planes: the observation (1D: one float, otherwise one 8-byte store per lane — a wavefront's row
+// is 512 contiguous bytes), the reward, done.  CHECKED: a null plane is skipped.
+template <bool CHECKED>
+__device__ __forceinline__ void store_step(const MobileParams &p, int64_t row, float o0, float o1, double reward, bool done,
+                                           float *__restrict__ obs, float *__restrict__ rew, uint8_t *__restrict__ done_out) {
+    if (!CHECKED || obs) {
+        if (p.kind == SRLHIP_ENV_MOBILE_1D) __builtin_nontemporal_store(o0, obs + row);
+        else __builtin_nontemporal_store(f32x2{o0, o1}, reinterpret_cast<f32x2 *>(obs + 2 * row));
+    }
+    if (!CHECKED || rew) __builtin_nontemporal_store((float)reward, rew + row);
+    if (!CHECKED || done_out) __builtin_nontemporal_store((uint8_t)done, done_out + row);
 }
 
 template <int MODE>
@@ -238,25 +274,17 @@ mobile_reset_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, cons
 }
 
 // Synthetic random-agent action (rl_baselines/random_agent.py:36) from Philox stream 1 of the env.  Discrete: action i is word i % 4 of
-// block i / 4 (multiply-shift into [0, m]) — FOUR actions per Philox block (round 6: the sampler's 131 072 blocks per 4096 x 2048
-// rollout were 27 us of the whole chip beside a 25 us recurrence; oracle/mobile_oracle.c draws the same way); continuous: one block per
-// action (two float64 uniforms).  `actr` counts ACTIONS.
+// block i / 4 (multiply-shift into [0, m]) — four actions per Philox block, drawn block by block in sample_plane_entry;
+// continuous: one block per action (two float64 uniforms).  oracle/mobile_oracle.c draws the same way.  `actr` counts ACTIONS.
 __device__ __forceinline__ int discrete_from_word(const MobileParams &p, uint32_t w) {
     const uint32_t m = p.kind == SRLHIP_ENV_MOBILE_1D ? 1u : 3u;
     return (int)(uint32_t)(((uint64_t)w * ((uint64_t)m + 1)) >> 32);
 }
-__device__ __forceinline__ void sample_action(const MobileParams &p, uint32_t k0, uint32_t k1, uint64_t actr,
-                                              int &a, float &a0, float &a1) {
-    Philox ph; ph.k0 = k0; ph.k1 = k1; ph.stream = 1;
+__device__ __forceinline__ float2 sample_continuous_action(uint32_t k0, uint32_t k1, uint64_t actr) {
+    Philox ph; ph.k0 = k0; ph.k1 = k1; ph.stream = 1; ph.ctr = actr;
     uint32_t o[4];
-    if (p.is_discrete) {
-        ph.ctr = actr >> 2; ph.block(o);
-        a = discrete_from_word(p, o[actr & 3]);
-    } else {
-        ph.ctr = actr; ph.block(o);
-        a0 = (float)(-1.0 + 2.0 * Philox::to_double(o[0], o[1]));
-        a1 = (float)(-1.0 + 2.0 * Philox::to_double(o[2], o[3]));
-    }
+    ph.block(o);
+    return make_float2((float)(-1.0 + 2.0 * Philox::to_double(o[0], o[1])), (float)(-1.0 + 2.0 * Philox::to_double(o[2], o[3])));
 }
 
 // All T x N synthetic actions of a rollout at once, into a [T][N] action plane whose row 0 is action base[e] + offset of env e's stream.
@@ -290,14 +318,34 @@ __device__ __forceinline__ void sample_plane_entry(const MobileParams &p, const 
         return;
     }
     if (t >= T) return;
-    const int64_t i = (int64_t)t * p.n + e;
-    int a = 0; float a0 = 0.f, a1 = 0.f;
-    sample_action(p, key[e], key[p.n + e], base[e] + offset + (uint64_t)t, a, a0, a1);
-    static_cast<float2 *>(act)[i] = make_float2(a0, a1);
+    static_cast<float2 *>(act)[(int64_t)t * p.n + e] = sample_continuous_action(key[e], key[p.n + e], base[e] + offset + (uint64_t)t);
 }
 __global__ void __launch_bounds__(kBlock)
 mobile_sample_actions_k(MobileParams p, RngState rs, int T, PlaneMap pm, void *__restrict__ act) {
     sample_plane_entry(p, rs.key, rs.act_ctr, 0, blockIdx.x, pm, T, act);
+}
+
+// The actions of kChunk consecutive steps of env e from a [T][n] plane.  They are fetched a chunk at a time because on gfx9 loads and
+// stores share one in-order counter (vmcnt): waiting for a load also drains every output store issued before it, so one wait per
+// kChunk steps instead of one per step keeps the streamed stores in flight.  Rows past t_last are clamped (fetched, never used).
+// (ai / af are the caller's two plain arrays: inside one struct they are not promoted to registers.)
+constexpr int kChunk = 16;
+__device__ __forceinline__ void gather_actions(const MobileParams &p, const void *__restrict__ actions, int t0, int t_last, int e,
+                                               int (&ai)[kChunk], float2 (&af)[kChunk]) {
+    const int32_t *act_i = static_cast<const int32_t *>(actions);
+    const float2 *act_f = static_cast<const float2 *>(actions);
+#pragma unroll
+    for (int k = 0; k < kChunk; k++) {
+        const int64_t r = (int64_t)min(t0 + k, t_last) * p.n + e;
+        if (p.is_discrete) ai[k] = act_i[r]; else af[k] = act_f[r];
+    }
+    // one full drain per chunk (vmcnt(0), expcnt / lgkmcnt untouched): afterwards no step of the chunk waits on memory
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+}
+__device__ __forceinline__ void chunk_action(const MobileParams &p, const int (&ai)[kChunk], const float2 (&af)[kChunk], int k,
+                                             int &a, float &a0, float &a1) {
+    a = p.is_discrete ? ai[k] : 0;
+    a0 = p.is_discrete ? 0.f : af[k].x; a1 = p.is_discrete ? 0.f : af[k].y;
 }
 
 // One launch == T consecutive VecEnv steps; T == 1 with plain stores is the per-step entry point, T > 1 the fused
@@ -316,60 +364,30 @@ mobile_rollout_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, in
     rng_load<MODE>(rng, rs, e, p.n, nullptr, 0, noise);
     MobileEnv m;
     load_env(s, e, m);
-    // (Monitor's record of the last finished episode is written only when an episode finishes in this launch and is never read: on
-    //  host-pointer handles those two planes are mapped host memory — srlhip_episode_records — and a read / an unconditional write-back
-    //  would cross PCIe in every launch)
-    double ep_ret = st.ep_return[e], last_ret = 0.0, last_reward = 0.0;
-    int32_t ep_len = st.ep_length[e], last_len = 0, n_fin = st.n_finished[e];
-    const int32_t n_fin0 = n_fin;
-    const int32_t *act_i = static_cast<const int32_t *>(actions);
-    const float2 *act_f = static_cast<const float2 *>(actions);
-    // Actions are fetched kChunk steps at a time: on gfx9 loads and stores share one in-order counter (vmcnt), so waiting
-    // for a load also drains every output store issued before it.  One wait per kChunk steps instead of one per step
-    // keeps the streamed stores in flight.
-    constexpr int kChunk = 16;
+    EpisodeLane ep;
+    ep.load(st, e);
     for (int t0 = 0; t0 < T; t0 += kChunk) {
         int ai[kChunk]; float2 af[kChunk];
-#pragma unroll
-        for (int k = 0; k < kChunk; k++) {
-            const int64_t r = (int64_t)min(t0 + k, T - 1) * p.n + e;
-            if (p.is_discrete) ai[k] = act_i[r]; else af[k] = act_f[r];
-        }
-        // one full drain per chunk (vmcnt(0), expcnt / lgkmcnt untouched): afterwards no step of the chunk waits on memory
-        __builtin_amdgcn_s_waitcnt(0x0F70);
+        gather_actions(p, actions, t0, T - 1, e, ai, af);
 #pragma unroll
         for (int k = 0; k < kChunk; k++) {
             const int t = t0 + k;
             if (t >= T) continue;                     // (uniform) tail of the last chunk
             const int64_t row = (int64_t)t * p.n + e;
-            const int a = p.is_discrete ? ai[k] : 0;
-            const float a0 = p.is_discrete ? 0.f : af[k].x, a1 = p.is_discrete ? 0.f : af[k].y;
+            int a; float a0, a1;
+            chunk_action(p, ai, af, k, a, a0, a1);
             double dv = 0.1 + rng.normal(0.0, 0.0);       // DELTA_POS + N(0, NOISE_STD = 0): drawn, value 0
             double reward; bool done;
             step_env<KIND, DISC>(p, m, a, a0, a1, dv, reward, done);
-            ep_ret += reward; ep_len += 1; last_reward = reward;
-            if (done) {
-                last_ret = ep_ret; last_len = ep_len; n_fin += 1; ep_ret = 0.0; ep_len = 0;
-                if (p.auto_reset) reset_env(p, rng, m);
-            }
+            ep.step(reward, done, [&] { if (p.auto_reset) reset_env(p, rng, m); });
             float o0, o1;
             observe(p, m, o0, o1);
-            if (obs) {
-                if (p.kind == SRLHIP_ENV_MOBILE_1D) __builtin_nontemporal_store(o0, obs + row);
-                else {
-                    __builtin_nontemporal_store(f32x2{o0, o1}, reinterpret_cast<f32x2 *>(obs + 2 * row));       // one 8-byte store per lane: a wavefront row is 512 contiguous bytes
-                }
-            }
-            if (rew) __builtin_nontemporal_store((float)reward, rew + row);
-            if (done_out) __builtin_nontemporal_store((uint8_t)done, done_out + row);
+            store_step<true>(p, row, o0, o1, reward, done, obs, rew, done_out);
         }
     }
     if (sig.done) {
         // early completion signal of a single-step launch (step_signal.hpp): per eighth of the grid the last WAVEFRONT to arrive reports
-        if (n_fin != n_fin0) {           // Monitor's record: the host reads it right after the step
-            __hip_atomic_store(st.last_return + e, last_ret, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(st.last_length + e, last_len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        if (ep.ended()) ep.publish(st, e);           // Monitor's record: the host reads it right after the step
         const int g8 = (int)blockIdx.x & 7;
         const int real = strided_real(g8, (p.n + 63) / 64, kBlock / 64);      // wavefronts with a live lane in the workgroups of this eighth
         const uint32_t xcc = xcd_id();
@@ -388,9 +406,39 @@ mobile_rollout_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, in
     store_env(s, e, m);
     rng_store<MODE>(rng, rs, e);
     if (advance_actr) rs.act_ctr[e] += (uint64_t)T;
-    st.ep_return[e] = ep_ret; st.ep_length[e] = ep_len;
-    if (n_fin != n_fin0) { st.last_return[e] = last_ret; st.last_length[e] = last_len; }
-    st.n_finished[e] = n_fin; st.last_reward[e] = last_reward;
+    ep.store(st, e);
+}
+
+// What the two policy kernels share: the statistics of the observation normalisation (frozen for the call), a policy's input
+// x = clip((o - mean) / sd) in float64, rounded to float32 as the reference's observation is, and the action taken from A float64 scores.
+template <int D>
+__device__ __forceinline__ void policy_stats(const PolicyArgs &pol, double (&mean)[D], double (&sd)[D]) {
+#pragma unroll
+    for (int d = 0; d < D; d++) { mean[d] = pol.normalize ? pol.mean[d] : 0.0; sd[d] = pol.normalize ? pol.std[d] : 1.0; }
+}
+template <int D>
+__device__ __forceinline__ void policy_input(const float *o, const PolicyArgs &pol, const double (&mean)[D], const double (&sd)[D], float (&x)[D]) {
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+        x[d] = o[d];
+        if (pol.normalize) x[d] = (float)fmin(fmax(((double)o[d] - mean[d]) / sd[d], -pol.clip), pol.clip);
+    }
+}
+// discrete: the strict arg-max (`a`; -1, the reference's `None`, once frozen); continuous: the first two scores as float32 (a0, a1; a zero
+// row once frozen: MobileRobot's step has no continuous `None`).  The action goes to row `row` of act_out when there is one.
+template <int DISC, int A>
+__device__ __forceinline__ void policy_action(const double (&score)[A], bool frozen, int64_t row, void *__restrict__ act_out, int &a, float &a0, float &a1) {
+    a = 0; a0 = 0.f; a1 = 0.f;
+    if (DISC) {
+        double best = score[0];
+#pragma unroll
+        for (int k = 1; k < A; k++) if (score[k] > best) { best = score[k]; a = k; }       // strict: the lowest index wins a tie
+        if (frozen) a = -1;
+        if (act_out) __builtin_nontemporal_store(a, static_cast<int32_t *>(act_out) + row);
+    } else {
+        a0 = frozen ? 0.f : (float)score[0]; a1 = frozen ? 0.f : (float)score[1];
+        if (act_out) __builtin_nontemporal_store(f32x2{a0, a1}, reinterpret_cast<f32x2 *>(act_out) + row);
+    }
 }
 
 // srlhip_rollout_policy: the third action source.  The action of every step is a linear map of the env's own current observation
@@ -417,58 +465,38 @@ mobile_rollout_policy_k(MobileParams p, MobileState s, RngState rs, EpisodeStats
     for (int d = 0; d < D; d++) {
 #pragma unroll
         for (int a = 0; a < A; a++) W[d][a] = w[d * A + a];
-        mean[d] = pol.normalize ? pol.mean[d] : 0.0;
-        sd[d] = pol.normalize ? pol.std[d] : 1.0;
     }
-    double ep_ret = st.ep_return[e], last_ret = 0.0, last_reward = 0.0;
-    int32_t ep_len = st.ep_length[e], last_len = 0, n_fin = st.n_finished[e];
-    const int32_t n_fin0 = n_fin;
+    policy_stats<D>(pol, mean, sd);
+    EpisodeLane ep;
+    ep.load(st, e);
     float o[2];
     observe(p, m, o[0], o[1]);
     bool frozen = false;
     for (int t = 0; t < T; t++) {
         const int64_t row = (int64_t)t * p.n + e;
+        float x[D];
+        policy_input<D>(o, pol, mean, sd, x);
         double score[A];
 #pragma unroll
         for (int d = 0; d < D; d++) {
-            float x = o[d];
-            if (pol.normalize) x = (float)fmin(fmax(((double)o[d] - mean[d]) / sd[d], -pol.clip), pol.clip);
 #pragma unroll
-            for (int a = 0; a < A; a++) score[a] = d == 0 ? (double)x * W[0][a] : score[a] + (double)x * W[d][a];
+            for (int a = 0; a < A; a++) score[a] = d == 0 ? (double)x[0] * W[0][a] : score[a] + (double)x[d] * W[d][a];
         }
-        int a = 0; float a0 = 0.f, a1 = 0.f;
-        if (DISC) {
-            double best = score[0];
-#pragma unroll
-            for (int k = 1; k < A; k++) if (score[k] > best) { best = score[k]; a = k; }       // strict: the lowest index wins a tie
-            if (frozen) a = -1;                                                              // the reference's `None`
-            if (act_out) __builtin_nontemporal_store(a, static_cast<int32_t *>(act_out) + row);
-        } else {
-            a0 = frozen ? 0.f : (float)score[0]; a1 = frozen ? 0.f : (float)score[1];         // (MobileRobot's step has no continuous `None`)
-            if (act_out) __builtin_nontemporal_store(f32x2{a0, a1}, reinterpret_cast<f32x2 *>(act_out) + row);
-        }
+        int a; float a0, a1;
+        policy_action<DISC, A>(score, frozen, row, act_out, a, a0, a1);
         double dv = 0.1 + rng.normal(0.0, 0.0);       // DELTA_POS + N(0, NOISE_STD = 0): drawn, value 0
         double reward; bool done;
         step_env<KIND, DISC>(p, m, a, a0, a1, dv, reward, done);
-        ep_ret += reward; ep_len += 1; last_reward = reward;
-        if (done) {
-            last_ret = ep_ret; last_len = ep_len; n_fin += 1; ep_ret = 0.0; ep_len = 0;
+        ep.step(reward, done, [&] {
             reset_env(p, rng, m);                     // (the entry point requires auto_reset)
             if (pol.freeze) frozen = true;            // from the NEXT step on
-        }
+        });
         observe(p, m, o[0], o[1]);
-        if (obs) {
-            if (KIND == SRLHIP_ENV_MOBILE_1D) __builtin_nontemporal_store(o[0], obs + row);
-            else __builtin_nontemporal_store(f32x2{o[0], o[1]}, reinterpret_cast<f32x2 *>(obs + 2 * row));
-        }
-        if (rew) __builtin_nontemporal_store((float)reward, rew + row);
-        if (done_out) __builtin_nontemporal_store((uint8_t)done, done_out + row);
+        store_step<true>(p, row, o[0], o[1], reward, done, obs, rew, done_out);
     }
     store_env(s, e, m);
     rng_store<MODE>(rng, rs, e);
-    st.ep_return[e] = ep_ret; st.ep_length[e] = ep_len;
-    if (n_fin != n_fin0) { st.last_return[e] = last_ret; st.last_length[e] = last_len; }
-    st.n_finished[e] = n_fin; st.last_reward[e] = last_reward;
+    ep.store(st, e);
 }
 
 // srlhip_rollout_mlp_policy: the action of every step is a one-hidden-layer ReLU MLP of the env's own current observation (the CMA-ES
@@ -529,17 +557,15 @@ mobile_rollout_mlp_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st
 #pragma unroll
     for (int a = 0; a < A; a++) { const float x = w[H * D + H + A * H + a]; B2[a] = l == 0 ? x : 0.f; }
     double mean[D], sd[D];
-#pragma unroll
-    for (int d = 0; d < D; d++) { mean[d] = pol.normalize ? pol.mean[d] : 0.0; sd[d] = pol.normalize ? pol.std[d] : 1.0; }
+    policy_stats<D>(pol, mean, sd);
     typename RngSel<MODE>::type rng = {};
     MobileEnv m = {};
-    double ep_ret = 0.0, last_ret = 0.0, last_reward = 0.0;
-    int32_t ep_len = 0, last_len = 0, n_fin = 0, n_fin0 = 0;
+    EpisodeLane ep;
     float o[2] = {0.f, 0.f};
     if (lead) {
         rng_load<MODE>(rng, rs, e, p.n, nullptr, 0, nullptr);
         load_env(s, e, m);
-        ep_ret = st.ep_return[e]; ep_len = st.ep_length[e]; n_fin = n_fin0 = st.n_finished[e];
+        ep.load(st, e);
         observe(p, m, o[0], o[1]);
     }
     bool frozen = false;
@@ -547,19 +573,15 @@ mobile_rollout_mlp_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st
         double score[A];
 #pragma unroll
         for (int a = 0; a < A; a++) score[a] = (double)B2[a];
-        double x[D];
+        float od[D], x[D];
 #pragma unroll
-        for (int d = 0; d < D; d++) {
-            const float od = row_lead_f32(o[d]);
-            float xf = od;
-            if (pol.normalize) xf = (float)fmin(fmax(((double)od - mean[d]) / sd[d], -pol.clip), pol.clip);
-            x[d] = (double)xf;
-        }
+        for (int d = 0; d < D; d++) od[d] = row_lead_f32(o[d]);
+        policy_input<D>(od, pol, mean, sd, x);
 #pragma unroll
         for (int u = 0; u < kMlpUnits; u++) {
             double hu = (double)B1[u];
 #pragma unroll
-            for (int d = 0; d < D; d++) hu += (double)W1[u][d] * x[d];
+            for (int d = 0; d < D; d++) hu += (double)W1[u][d] * (double)x[d];
             hu = hu > 0.0 ? hu : 0.0;
 #pragma unroll
             for (int a = 0; a < A; a++) score[a] += (double)W2[a][u] * hu;
@@ -568,41 +590,23 @@ mobile_rollout_mlp_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st
         for (int a = 0; a < A; a++) score[a] = row_sum16(score[a]);
         if (lead) {
             const int64_t row = (int64_t)t * p.n + e;
-            int a = 0; float a0 = 0.f, a1 = 0.f;
-            if (DISC) {
-                double best = score[0];
-#pragma unroll
-                for (int k = 1; k < A; k++) if (score[k] > best) { best = score[k]; a = k; }       // strict: the lowest index wins a tie
-                if (frozen) a = -1;                                                              // the reference's `None`
-                if (act_out) __builtin_nontemporal_store(a, static_cast<int32_t *>(act_out) + row);
-            } else {
-                a0 = frozen ? 0.f : (float)score[0]; a1 = frozen ? 0.f : (float)score[1];         // (MobileRobot's step has no continuous `None`)
-                if (act_out) __builtin_nontemporal_store(f32x2{a0, a1}, reinterpret_cast<f32x2 *>(act_out) + row);
-            }
+            int a; float a0, a1;
+            policy_action<DISC, A>(score, frozen, row, act_out, a, a0, a1);
             double dv = 0.1 + rng.normal(0.0, 0.0);       // DELTA_POS + N(0, NOISE_STD = 0): drawn, value 0
             double reward; bool done;
             step_env<KIND, DISC>(p, m, a, a0, a1, dv, reward, done);
-            ep_ret += reward; ep_len += 1; last_reward = reward;
-            if (done) {
-                last_ret = ep_ret; last_len = ep_len; n_fin += 1; ep_ret = 0.0; ep_len = 0;
+            ep.step(reward, done, [&] {
                 reset_env(p, rng, m);                     // (the entry point requires auto_reset)
                 if (pol.freeze) frozen = true;            // from the NEXT step on
-            }
+            });
             observe(p, m, o[0], o[1]);
-            if (obs) {
-                if (KIND == SRLHIP_ENV_MOBILE_1D) __builtin_nontemporal_store(o[0], obs + row);
-                else __builtin_nontemporal_store(f32x2{o[0], o[1]}, reinterpret_cast<f32x2 *>(obs + 2 * row));
-            }
-            if (rew) __builtin_nontemporal_store((float)reward, rew + row);
-            if (done_out) __builtin_nontemporal_store((uint8_t)done, done_out + row);
+            store_step<true>(p, row, o[0], o[1], reward, done, obs, rew, done_out);
         }
     }
     if (!lead) return;
     store_env(s, e, m);
     rng_store<MODE>(rng, rs, e);
-    st.ep_return[e] = ep_ret; st.ep_length[e] = ep_len;
-    if (n_fin != n_fin0) { st.last_return[e] = last_ret; st.last_length[e] = last_len; }
-    st.n_finished[e] = n_fin; st.last_reward[e] = last_reward;
+    ep.store(st, e);
 }
 
 // Persistent stepping (srlhip_set_persistent; the protocol is step_signal.hpp's): ONE launch stays resident with every env's state in
@@ -623,8 +627,9 @@ mobile_persist_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, co
     rng_load<MODE>(rng, rs, ee, p.n, nullptr, 0, nullptr);
     MobileEnv m;
     load_env(s, ee, m);
-    double ep_ret = st.ep_return[ee], last_ret = 0.0, last_reward = st.last_reward[ee];
-    int32_t ep_len = st.ep_length[ee], last_len = 0, n_fin = st.n_finished[ee];
+    EpisodeLane ep;
+    ep.load(st, ee);
+    ep.last_reward = st.last_reward[ee];               // (a resident kernel may park before it has taken a step)
     // start barrier: every workgroup has registered -> 1: direct outputs, 2: written-through outputs, 3: told to stop while waiting
     if (threadIdx.x == 0) {
         uint32_t verdict = 0;
@@ -685,16 +690,13 @@ mobile_persist_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, co
             double dv = 0.1 + rng.normal(0.0, 0.0);       // DELTA_POS + N(0, NOISE_STD = 0): drawn, value 0
             double reward; bool done;
             step_env<KIND, DISC>(p, m, a, a0, a1, dv, reward, done);
-            ep_ret += reward; ep_len += 1; last_reward = reward;
-            if (done) {
-                last_ret = ep_ret; last_len = ep_len; n_fin += 1; ep_ret = 0.0; ep_len = 0;
+            ep.step(reward, done, [&] {
                 if (p.auto_reset) reset_env(p, rng, m);
-                __hip_atomic_store(st.last_return + e, last_ret, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);        // Monitor's record, with the step
-                __hip_atomic_store(st.last_length + e, last_len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
+                ep.publish(st, e);                        // Monitor's record, with the step
+            });
             float o0, o1;
             observe(p, m, o0, o1);
-            if (direct) {
+            if (direct) {                                  // (per-env planes in the host's mapped memory: not store_step's streamed rows)
                 if (od == 1) obs[e] = o0; else { obs[2 * e] = o0; obs[2 * e + 1] = o1; }
                 rew[e] = (float)reward; done_out[e] = (uint8_t)done;
             } else {
@@ -716,8 +718,7 @@ mobile_persist_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, co
     if (!valid) return;
     store_env(s, e, m);
     rng_store<MODE>(rng, rs, e);
-    st.ep_return[e] = ep_ret; st.ep_length[e] = ep_len;
-    st.n_finished[e] = n_fin; st.last_reward[e] = last_reward;
+    ep.store<false>(st, e);                                // every record was published with its step
 }
 
 // Episode-parallel rollout (Philox mode with auto-reset).  In the MobileRobot family an episode always lasts exactly
@@ -734,30 +735,28 @@ constexpr int kEpisodeSteps = 251;
 // Everything a segment lane reads from the per-env state.  The lanes of one env are NOT guaranteed to be co-resident
 // (beyond ~0.5 M lanes later blocks are dispatched after earlier ones retire), and the lane that finishes an env's rollout
 // overwrites its state: the segments therefore read this snapshot, taken by mobile_snapshot_k in stream order right
-// before the launch, and only write the live state.
-struct MobileSnap { MobileState s; const uint64_t *ctr; const double *ep_return; const int32_t *ep_length; };
-// where the lane that leaves an env's final state ALSO writes it: the snapshot set the next launch will read (null planes: nowhere)
-struct MobileSnapOut { MobileState s; uint64_t *ctr, *actr; double *ep_return; int32_t *ep_length; };
+// before the launch, and only write the live state (MobileSnapSet, internal.hpp: the kernel reads one set; the lane that leaves an
+// env's final state ALSO writes it into the other one, which the next launch will read — an all-null set: nowhere).
 // The synthetic agent's NEXT action plane, drawn by the workgroups of a rollout launch beyond its segment lanes (the rollout itself
 // is a latency-bound recurrence on 10 x N lanes: the chip has room) so that the following rollout starts without a sampler launch:
 // block base[e] + T + t of env e's action stream (base = the counters in the snapshot: the live ones move when the rollout ends).
 struct NextPlane { void *act; const uint64_t *base; int ep_blocks; PlaneMap pm; };
 
 __global__ void __launch_bounds__(kBlock)
-mobile_snapshot_k(int n, MobileState s, RngState rs, EpisodeStats st, MobileState d, uint64_t *ctr, double *ep_return, int32_t *ep_length, uint64_t *actr) {
+mobile_snapshot_k(int n, MobileState s, RngState rs, EpisodeStats st, MobileSnapSet d) {
     const int e = blockIdx.x * kBlock + threadIdx.x;
     if (e >= n) return;
-    actr[e] = rs.act_ctr[e];
-    d.pos_x[e] = s.pos_x[e]; d.pos_y[e] = s.pos_y[e]; d.tgt_x[e] = s.tgt_x[e]; d.tgt_y[e] = s.tgt_y[e];
-    d.tgt2_x[e] = s.tgt2_x[e]; d.tgt2_y[e] = s.tgt2_y[e]; d.counter[e] = s.counter[e]; d.cur_target[e] = s.cur_target[e];
-    ctr[e] = rs.ctr[e]; ep_return[e] = st.ep_return[e]; ep_length[e] = st.ep_length[e];
+    d.actr[e] = rs.act_ctr[e];
+    d.s.pos_x[e] = s.pos_x[e]; d.s.pos_y[e] = s.pos_y[e]; d.s.tgt_x[e] = s.tgt_x[e]; d.s.tgt_y[e] = s.tgt_y[e];
+    d.s.tgt2_x[e] = s.tgt2_x[e]; d.s.tgt2_y[e] = s.tgt2_y[e]; d.s.counter[e] = s.counter[e]; d.s.cur_target[e] = s.cur_target[e];
+    d.ctr[e] = rs.ctr[e]; d.ep_return[e] = st.ep_return[e]; d.ep_length[e] = st.ep_length[e];
 }
 
 template <int KIND, int DISC, int SHAPE, int PLANES>      // PLANES: 0 check every output plane, 1 obs / reward / done present, 2 those and act_out
 __global__ void __launch_bounds__(kBlock)
-mobile_rollout_ep_k(MobileParams p, MobileState s, MobileSnap snap, RngState rs, EpisodeStats st, int T, int draws_per_reset, int smax,
+mobile_rollout_ep_k(MobileParams p, MobileState s, MobileSnapSet snap, RngState rs, EpisodeStats st, int T, int draws_per_reset, int smax,
                     const void *__restrict__ actions, float *__restrict__ obs, float *__restrict__ rew,
-                    uint8_t *__restrict__ done_out, int advance_actr, NextPlane next, void *__restrict__ act_out, MobileSnapOut snap_out) {
+                    uint8_t *__restrict__ done_out, int advance_actr, NextPlane next, void *__restrict__ act_out, MobileSnapSet snap_out) {
     p.kind = KIND; p.is_discrete = DISC; p.shape_reward = SHAPE;            // compile-time constants from here on
     if ((int)blockIdx.x >= next.ep_blocks) {                               // spare workgroups: the next rollout's action plane
         sample_plane_entry(p, rs.key, next.base, (uint64_t)T, blockIdx.x - (uint32_t)next.ep_blocks, next.pm, T, next.act);
@@ -778,19 +777,19 @@ mobile_rollout_ep_k(MobileParams p, MobileState s, MobileSnap snap, RngState rs,
     rng.p.k0 = rs.key[e]; rng.p.k1 = rs.key[p.n + e]; rng.p.stream = 0;
     const uint64_t ctr0 = snap.ctr[e];
     MobileEnv m;
-    double ep_ret = 0.0, seg_ret = 0.0, last_reward = 0.0;
-    int32_t ep_len = 0, seg_len = 0;
+    // this SEGMENT's accounting: at most one episode ends in it, so last_ret / last_len are the segment's own finished episode, and
+    // the env's count of finished episodes is arithmetic (n_completed), not a lane's count
+    EpisodeLane ep;
     if (j == 0) {
         load_env(snap.s, e, m);
         rng.p.ctr = ctr0;
-        ep_ret = snap.ep_return[e]; ep_len = snap.ep_length[e];
+        ep.ep_ret = snap.ep_return[e]; ep.ep_len = snap.ep_length[e];
     } else {
         rng.p.ctr = ctr0 + (uint64_t)(j - 1) * (uint64_t)draws_per_reset;
         reset_env(p, rng, m);                                              // the reset the previous segment ends with
     }
     const int32_t *act_i = static_cast<const int32_t *>(actions);
     const float2 *act_f = static_cast<const float2 *>(actions);
-    constexpr int kChunk = 16;                                             // see mobile_rollout_k: one vmcnt drain per chunk
     int t_start = t_lo;
     // Fast loop: whole chunks of INTERIOR steps.  Inside a segment `done` can only fire at the step that ends its episode
     // (t_end - 1), so every earlier step needs no reset; with all four output planes present (ALL) and every lane of the wavefront
@@ -825,13 +824,10 @@ mobile_rollout_ep_k(MobileParams p, MobileState s, MobileSnap snap, RngState rs,
                 const double dv = 0.1 + rng.normal(0.0, 0.0);
                 double reward; bool done;
                 step_env<KIND, DISC, SHAPE>(p, m, a, a0, a1, dv, reward, done);     // done is false here (interior step)
-                ep_ret += reward; ep_len += 1; last_reward = reward;
+                ep.add(reward);
                 float o0, o1;
                 observe(p, m, o0, o1);
-                if (p.kind == SRLHIP_ENV_MOBILE_1D) __builtin_nontemporal_store(o0, obs + row);
-                else __builtin_nontemporal_store(f32x2{o0, o1}, reinterpret_cast<f32x2 *>(obs + 2 * row));
-                __builtin_nontemporal_store((float)reward, rew + row);
-                __builtin_nontemporal_store((uint8_t)0, done_out + row);
+                store_step<false>(p, row, o0, o1, reward, false, obs, rew, done_out);
             }
             t_start += kFast;
         };
@@ -853,19 +849,14 @@ mobile_rollout_ep_k(MobileParams p, MobileState s, MobileSnap snap, RngState rs,
     }
     for (int t0 = t_start; t0 < t_hi; t0 += kChunk) {
         int ai[kChunk]; float2 af[kChunk];
-#pragma unroll
-        for (int k = 0; k < kChunk; k++) {
-            const int64_t r = (int64_t)min(t0 + k, t_hi - 1) * p.n + e;
-            if (p.is_discrete) ai[k] = act_i[r]; else af[k] = act_f[r];
-        }
-        __builtin_amdgcn_s_waitcnt(0x0F70);
+        gather_actions(p, actions, t0, t_hi - 1, e, ai, af);
 #pragma unroll
         for (int k = 0; k < kChunk; k++) {
             const int t = t0 + k;
             if (t < t_hi) {
                 const int64_t row = (int64_t)t * p.n + e;
-                const int a = p.is_discrete ? ai[k] : 0;
-                const float a0 = p.is_discrete ? 0.f : af[k].x, a1 = p.is_discrete ? 0.f : af[k].y;
+                int a; float a0, a1;
+                chunk_action(p, ai, af, k, a, a0, a1);
                 if (act_out) {                                             // the plane is internal: hand the actions taken to the caller
                     if (p.is_discrete) __builtin_nontemporal_store(a, static_cast<int32_t *>(act_out) + row);
                     else static_cast<float2 *>(act_out)[row] = make_float2(a0, a1);
@@ -873,37 +864,28 @@ mobile_rollout_ep_k(MobileParams p, MobileState s, MobileSnap snap, RngState rs,
                 const double dv = 0.1 + rng.normal(0.0, 0.0);              // DELTA_POS + N(0, NOISE_STD = 0): draws nothing
                 double reward; bool done;
                 step_env<KIND, DISC, SHAPE>(p, m, a, a0, a1, dv, reward, done);
-                ep_ret += reward; ep_len += 1; last_reward = reward;
-                if (done) {
-                    seg_ret = ep_ret; seg_len = ep_len; ep_ret = 0.0; ep_len = 0;
-                    reset_env(p, rng, m);
-                }
+                ep.step(reward, done, [&] { reset_env(p, rng, m); });
                 float o0, o1;
                 observe(p, m, o0, o1);
-                if (obs) {
-                    if (p.kind == SRLHIP_ENV_MOBILE_1D) __builtin_nontemporal_store(o0, obs + row);
-                    else {
-                        __builtin_nontemporal_store(f32x2{o0, o1}, reinterpret_cast<f32x2 *>(obs + 2 * row));       // one 8-byte store per lane: a wavefront row is 512 contiguous bytes
-                    }
-                }
-                if (rew) __builtin_nontemporal_store((float)reward, rew + row);
-                if (done_out) __builtin_nontemporal_store((uint8_t)done, done_out + row);
+                store_step<true>(p, row, o0, o1, reward, done, obs, rew, done_out);
             }
         }
     }
+    // The exit is not EpisodeLane::store: the fields of one env are left by different lanes.  (last_return / last_length: written when
+    // an episode ended, never read — the rule stated there)
     if (t_end <= T && j == n_completed - 1) {        // the last episode that finished inside the rollout
-        st.last_return[e] = seg_ret; st.last_length[e] = seg_len;
+        st.last_return[e] = ep.last_ret; st.last_length[e] = ep.last_len;
     }
     if (last) {
         store_env(s, e, m);
         rs.ctr[e] = rng.p.ctr;
         const uint64_t actr = rs.act_ctr[e] + (advance_actr ? (uint64_t)T : 0);
         if (advance_actr) rs.act_ctr[e] = actr;
-        st.ep_return[e] = ep_ret; st.ep_length[e] = ep_len; st.last_reward[e] = last_reward;
+        st.ep_return[e] = ep.ep_ret; st.ep_length[e] = ep.ep_len; st.last_reward[e] = ep.last_reward;
         st.n_finished[e] += n_completed;
         if (snap_out.ctr) {                  // the next launch's snapshot (this launch reads the other set)
             store_env(snap_out.s, e, m);
-            snap_out.ctr[e] = rng.p.ctr; snap_out.actr[e] = actr; snap_out.ep_return[e] = ep_ret; snap_out.ep_length[e] = ep_len;
+            snap_out.ctr[e] = rng.p.ctr; snap_out.actr[e] = actr; snap_out.ep_return[e] = ep.ep_ret; snap_out.ep_length[e] = ep.ep_len;
         }
     }
 }
@@ -927,54 +909,60 @@ int mobile_reset_rand_count(const srlhip_config &c) {
     }
 }
 
-int mobile_alloc(Handle *h) {
-    MobileState &s = h->mobile;
-    size_t n = (size_t)h->n;
+namespace {
+
+int alloc_state(Handle *h, MobileState &s) {
+    const size_t n = (size_t)h->n;
     int rc = 0;
-    if ((rc = h->dalloc(&s.pos_x, n)) || (rc = h->dalloc(&s.pos_y, n)) || (rc = h->dalloc(&s.tgt_x, n)) ||
-        (rc = h->dalloc(&s.tgt_y, n)) || (rc = h->dalloc(&s.tgt2_x, n)) || (rc = h->dalloc(&s.tgt2_y, n)) ||
-        (rc = h->dalloc(&s.counter, n)) || (rc = h->dalloc(&s.cur_target, n)))
-        return rc;
+    (void)((rc = h->dalloc(&s.pos_x, n)) || (rc = h->dalloc(&s.pos_y, n)) || (rc = h->dalloc(&s.tgt_x, n)) ||
+           (rc = h->dalloc(&s.tgt_y, n)) || (rc = h->dalloc(&s.tgt2_x, n)) || (rc = h->dalloc(&s.tgt2_y, n)) ||
+           (rc = h->dalloc(&s.counter, n)) || (rc = h->dalloc(&s.cur_target, n)));
+    return rc;
+}
+
+// Run-time configuration -> template arguments: f is a generic lambda that receives std::integral_constants and launches (or names)
+// the instantiation they select.  Only the combinations a caller dispatches on exist in the library.
+template <int V> using Const = std::integral_constant<int, V>;
+template <int... Vs, class F>
+void dispatch_int(int v, F &&f) { (void)(((v == Vs) && (f(Const<Vs>{}), true)) || ...); }
+template <class F>
+void dispatch_device_rng(int rng_mode, F &&f) { dispatch_int<SRLHIP_RNG_PHILOX, SRLHIP_RNG_MT19937>(rng_mode, f); }
+template <class F>
+void dispatch_env(const MobileParams &p, F &&f) {           // f(kind, is_discrete)
+    dispatch_int<SRLHIP_ENV_MOBILE, SRLHIP_ENV_MOBILE_1D, SRLHIP_ENV_MOBILE_2TARGET, SRLHIP_ENV_MOBILE_LINE>(p.kind, [&](auto kind) {
+        dispatch_int<0, 1>(p.is_discrete ? 1 : 0, [&](auto disc) { f(kind, disc); });
+    });
+}
+// MobileRobot1D / 2Target take discrete actions only (srlhip_create refuses the other combination): not instantiated for the policy kernels
+constexpr bool policy_combination(int kind, int disc) { return disc || (kind != SRLHIP_ENV_MOBILE_1D && kind != SRLHIP_ENV_MOBILE_2TARGET); }
+
+}  // namespace
+
+int mobile_alloc(Handle *h) {
+    int rc = alloc_state(h, h->mobile);
+    if (rc) return rc;
     if (h->cfg.rng_mode == SRLHIP_RNG_PHILOX) {
         // snapshot planes of the episode-parallel rollout (launch_rollout_ep): allocated with the handle, never lazily — a
         // first rollout may sit inside srlhip_graph_begin / srlhip_graph_end, where hipMalloc is illegal
-        MobileState &d = h->mobile_snap;
-        if ((rc = h->dalloc(&d.pos_x, n)) || (rc = h->dalloc(&d.pos_y, n)) || (rc = h->dalloc(&d.tgt_x, n)) || (rc = h->dalloc(&d.tgt_y, n)) ||
-            (rc = h->dalloc(&d.tgt2_x, n)) || (rc = h->dalloc(&d.tgt2_y, n)) || (rc = h->dalloc(&d.counter, n)) || (rc = h->dalloc(&d.cur_target, n)) ||
-            (rc = h->dalloc(&h->snap_ep_return, n)) || (rc = h->dalloc(&h->snap_ep_length, n)) || (rc = h->dalloc(&h->snap_ctr, n)) ||
-            (rc = h->dalloc(&h->snap_actr, n)))
-            return rc;
-        MobileState &d2 = h->mobile_snap2;
-        if ((rc = h->dalloc(&d2.pos_x, n)) || (rc = h->dalloc(&d2.pos_y, n)) || (rc = h->dalloc(&d2.tgt_x, n)) || (rc = h->dalloc(&d2.tgt_y, n)) ||
-            (rc = h->dalloc(&d2.tgt2_x, n)) || (rc = h->dalloc(&d2.tgt2_y, n)) || (rc = h->dalloc(&d2.counter, n)) || (rc = h->dalloc(&d2.cur_target, n)) ||
-            (rc = h->dalloc(&h->snap2_ep_return, n)) || (rc = h->dalloc(&h->snap2_ep_length, n)) || (rc = h->dalloc(&h->snap2_ctr, n)) ||
-            (rc = h->dalloc(&h->snap2_actr, n)))
-            return rc;
+        const size_t n = (size_t)h->n;
+        for (MobileSnapSet &d : h->snap)
+            if ((rc = alloc_state(h, d.s)) || (rc = h->dalloc(&d.ep_return, n)) || (rc = h->dalloc(&d.ep_length, n)) ||
+                (rc = h->dalloc(&d.ctr, n)) || (rc = h->dalloc(&d.actr, n)))
+                return rc;
     }
     return 0;
 }
-
-void mobile_free(Handle *) {}
 
 int mobile_reset(Handle *h, const uint8_t *d_mask, const double *d_host_rand, float *d_obs) {
     h->snap_valid = false;
     MobileParams p = params_of(h);
     dim3 grid((h->n + kBlock - 1) / kBlock), block(kBlock);
     int stride = mobile_reset_rand_count(h->cfg);
-    switch (h->cfg.rng_mode) {
-        case SRLHIP_RNG_HOST:
-            if (!d_host_rand) return h->fail(SRLHIP_EINVAL, "reset: RNG_HOST needs host_rand");
-            hipLaunchKernelGGL(mobile_reset_k<SRLHIP_RNG_HOST>, grid, block, 0, h->stream, p, h->mobile, h->rng,
-                               h->stats, d_mask, d_host_rand, stride, d_obs);
-            break;
-        case SRLHIP_RNG_PHILOX:
-            hipLaunchKernelGGL(mobile_reset_k<SRLHIP_RNG_PHILOX>, grid, block, 0, h->stream, p, h->mobile, h->rng,
-                               h->stats, d_mask, d_host_rand, stride, d_obs);
-            break;
-        default:
-            hipLaunchKernelGGL(mobile_reset_k<SRLHIP_RNG_MT19937>, grid, block, 0, h->stream, p, h->mobile, h->rng,
-                               h->stats, d_mask, d_host_rand, stride, d_obs);
-    }
+    if (h->cfg.rng_mode == SRLHIP_RNG_HOST && !d_host_rand) return h->fail(SRLHIP_EINVAL, "reset: RNG_HOST needs host_rand");
+    dispatch_int<SRLHIP_RNG_HOST, SRLHIP_RNG_PHILOX, SRLHIP_RNG_MT19937>(h->cfg.rng_mode, [&](auto mode) {
+        hipLaunchKernelGGL(mobile_reset_k<decltype(mode)::value>, grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, d_mask,
+                           d_host_rand, stride, d_obs);
+    });
     SRL_HIP_CHECK(h, hipGetLastError());
     return 0;
 }
@@ -990,18 +978,10 @@ void launch_rollout(Handle *h, const MobileParams &p, int T, const void *d_actio
         sig = h->step_signal; h->step_signal_armed = true;
         h->signal_eighths = strided_eighths((int)grid.x);
     }
-#define SRL_GO(KIND, DISC)                                                                                              \
-    hipLaunchKernelGGL((mobile_rollout_k<MODE, KIND, DISC>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T, \
-                       d_actions, d_noise, d_obs, d_rew, d_done, advance_actr, sig)
-#define SRL_KIND(KIND) { if (p.is_discrete) SRL_GO(KIND, 1); else SRL_GO(KIND, 0); }
-    switch (p.kind) {
-        case SRLHIP_ENV_MOBILE: SRL_KIND(SRLHIP_ENV_MOBILE) break;
-        case SRLHIP_ENV_MOBILE_1D: SRL_KIND(SRLHIP_ENV_MOBILE_1D) break;
-        case SRLHIP_ENV_MOBILE_2TARGET: SRL_KIND(SRLHIP_ENV_MOBILE_2TARGET) break;
-        default: SRL_KIND(SRLHIP_ENV_MOBILE_LINE)
-    }
-#undef SRL_KIND
-#undef SRL_GO
+    dispatch_env(p, [&](auto kind, auto disc) {
+        hipLaunchKernelGGL((mobile_rollout_k<MODE, decltype(kind)::value, decltype(disc)::value>), grid, block, 0, h->stream, p, h->mobile,
+                           h->rng, h->stats, T, d_actions, d_noise, d_obs, d_rew, d_done, advance_actr, sig);
+    });
 }
 
 // next_plane: where the spare workgroups put the following rollout's actions (null: none); act_out: the caller's action plane
@@ -1016,18 +996,9 @@ int launch_rollout_ep(Handle *h, const MobileParams &p, int T, const void *d_act
     (void)hipStreamIsCapturing(h->stream, &capture);
     const bool chained = capture == hipStreamCaptureStatusNone;
     const int cur = h->snap_cur;
-    MobileState &sin = cur ? h->mobile_snap2 : h->mobile_snap, &sout = cur ? h->mobile_snap : h->mobile_snap2;
-    uint64_t *in_ctr = cur ? h->snap2_ctr : h->snap_ctr, *in_actr = cur ? h->snap2_actr : h->snap_actr;
-    double *in_ret = cur ? h->snap2_ep_return : h->snap_ep_return;
-    int32_t *in_len = cur ? h->snap2_ep_length : h->snap_ep_length;
+    const MobileSnapSet snap = h->snap[cur], snap_out = chained ? h->snap[cur ^ 1] : MobileSnapSet{};
     if (!h->snap_valid || !chained)
-        hipLaunchKernelGGL(mobile_snapshot_k, dim3((h->n + kBlock - 1) / kBlock), dim3(kBlock), 0, h->stream, h->n, h->mobile, h->rng, h->stats,
-                           sin, in_ctr, in_ret, in_len, in_actr);
-    const MobileSnap snap{sin, in_ctr, in_ret, in_len};
-    MobileSnapOut snap_out = {};
-    if (chained)
-        snap_out = MobileSnapOut{sout, cur ? h->snap_ctr : h->snap2_ctr, cur ? h->snap_actr : h->snap2_actr,
-                                 cur ? h->snap_ep_return : h->snap2_ep_return, cur ? h->snap_ep_length : h->snap2_ep_length};
+        hipLaunchKernelGGL(mobile_snapshot_k, dim3((h->n + kBlock - 1) / kBlock), dim3(kBlock), 0, h->stream, h->n, h->mobile, h->rng, h->stats, snap);
     h->snap_cur = chained ? cur ^ 1 : cur;
     h->snap_valid = chained;
     const int smax = 1 + (T - 1 + kEpisodeSteps - 1) / kEpisodeSteps;     // first segment of one step + whole episodes
@@ -1035,26 +1006,19 @@ int launch_rollout_ep(Handle *h, const MobileParams &p, int T, const void *d_act
     const int ep_blocks = (int)((lanes + kBlock - 1) / kBlock);
     const PlaneMap pm = plane_map(h->n);
     const int64_t extra = next_plane ? plane_rows(p, T) * pm.bpr : 0;
-    const NextPlane next{next_plane, in_actr, ep_blocks, pm};
+    const NextPlane next{next_plane, snap.actr, ep_blocks, pm};
     dim3 grid((unsigned)(ep_blocks + extra)), block(kBlock);
     const int draws = mobile_reset_rand_count(h->cfg);
     const int planes = d_obs && d_rew && d_done ? (act_out ? 2 : 1) : 0;   // the fast loop stores without checking
-#define SRL_EP(KIND, DISC, SHAPE, PLANES)                                                                               \
-    hipLaunchKernelGGL((mobile_rollout_ep_k<KIND, DISC, SHAPE, PLANES>), grid, block, 0, h->stream, p, h->mobile, snap, h->rng, h->stats, T, \
-                       draws, smax, d_actions, d_obs, d_rew, d_done, advance_actr, next, act_out, snap_out)
-#define SRL_PL(KIND, DISC, SHAPE) { if (planes == 2) SRL_EP(KIND, DISC, SHAPE, 2); else if (planes == 1) SRL_EP(KIND, DISC, SHAPE, 1); else SRL_EP(KIND, DISC, SHAPE, 0); }
-#define SRL_GO(KIND, DISC) { if (p.shape_reward) SRL_PL(KIND, DISC, 1) else SRL_PL(KIND, DISC, 0) }
-#define SRL_KIND(KIND) { if (p.is_discrete) SRL_GO(KIND, 1) else SRL_GO(KIND, 0) }
-    switch (p.kind) {
-        case SRLHIP_ENV_MOBILE: SRL_KIND(SRLHIP_ENV_MOBILE) break;
-        case SRLHIP_ENV_MOBILE_1D: SRL_KIND(SRLHIP_ENV_MOBILE_1D) break;
-        case SRLHIP_ENV_MOBILE_2TARGET: SRL_KIND(SRLHIP_ENV_MOBILE_2TARGET) break;
-        default: SRL_KIND(SRLHIP_ENV_MOBILE_LINE)
-    }
-#undef SRL_KIND
-#undef SRL_GO
-#undef SRL_PL
-#undef SRL_EP
+    dispatch_env(p, [&](auto kind, auto disc) {
+        dispatch_int<0, 1>(p.shape_reward ? 1 : 0, [&](auto shape) {
+            dispatch_int<0, 1, 2>(planes, [&](auto pl) {
+                hipLaunchKernelGGL((mobile_rollout_ep_k<decltype(kind)::value, decltype(disc)::value, decltype(shape)::value, decltype(pl)::value>),
+                                   grid, block, 0, h->stream, p, h->mobile, snap, h->rng, h->stats, T, draws, smax, d_actions, d_obs, d_rew,
+                                   d_done, advance_actr, next, act_out, snap_out);
+            });
+        });
+    });
     return 0;
 }
 
@@ -1075,12 +1039,11 @@ int mobile_rollout(Handle *h, int T, const void *d_actions, float *d_obs, float 
             // previous launch's spare workgroups filled (or fills one now), its own spare workgroups fill the other one.
             const size_t bytes = (size_t)T * h->n * (p.is_discrete ? 4 : 8);
             for (int b = 0; b < 2; b++)
-                if (h->act_plane_sz[b] < bytes) {
+                if (h->act_plane_sz[b] < bytes) {           // regrown: a launch in flight may still read or fill the old plane
                     SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));
-                    if (h->act_plane[b]) (void)hipFree(h->act_plane[b]);
-                    h->act_plane[b] = nullptr; h->act_plane_sz[b] = 0; h->prefetch_valid = false;
-                    SRL_HIP_CHECK(h, hipMalloc(&h->act_plane[b], bytes));
-                    h->act_plane_sz[b] = bytes;
+                    h->prefetch_valid = false;
+                    int rc = ensure(h, &h->act_plane[b], &h->act_plane_sz[b], bytes);
+                    if (rc) return rc;
                 }
             int cur = 0;
             if (h->prefetch_valid && h->prefetch_T == T) cur = h->prefetch_buf;
@@ -1103,12 +1066,8 @@ int mobile_rollout(Handle *h, int T, const void *d_actions, float *d_obs, float 
         const size_t bytes = (size_t)T * h->n * (p.is_discrete ? 4 : 8);
         void *plane = d_act_out;
         if (!plane) {
-            if (h->st_noise_sz < bytes) {
-                if (h->st_noise) (void)hipFree(h->st_noise);
-                h->st_noise = nullptr; h->st_noise_sz = 0;
-                SRL_HIP_CHECK(h, hipMalloc(&h->st_noise, bytes));
-                h->st_noise_sz = bytes;
-            }
+            int rc = ensure(h, &h->st_noise, &h->st_noise_sz, bytes);
+            if (rc) return rc;
             plane = h->st_noise;
         }
         const PlaneMap pm = plane_map(h->n);
@@ -1119,11 +1078,15 @@ int mobile_rollout(Handle *h, int T, const void *d_actions, float *d_obs, float 
         advance = 1;
     }
     // counter-based streams + fixed-length episodes: segments of the rollout run in parallel (mobile_rollout_ep_k)
-    if (ep_path) { int rc = launch_rollout_ep(h, p, T, d_actions, d_obs, d_rew, d_done, advance, nullptr, nullptr); if (rc) return rc; }
-    else h->snap_valid = false;          // the sequential kernels below move the live state only
-    if (ep_path) {}
-    else if (h->cfg.rng_mode == SRLHIP_RNG_PHILOX) launch_rollout<SRLHIP_RNG_PHILOX>(h, p, T, d_actions, nullptr, d_obs, d_rew, d_done, advance);
-    else launch_rollout<SRLHIP_RNG_MT19937>(h, p, T, d_actions, nullptr, d_obs, d_rew, d_done, advance);
+    if (ep_path) {
+        int rc = launch_rollout_ep(h, p, T, d_actions, d_obs, d_rew, d_done, advance, nullptr, nullptr);
+        if (rc) return rc;
+    } else {
+        h->snap_valid = false;           // the sequential kernel moves the live state only
+        dispatch_device_rng(h->cfg.rng_mode, [&](auto mode) {
+            launch_rollout<decltype(mode)::value>(h, p, T, d_actions, nullptr, d_obs, d_rew, d_done, advance);
+        });
+    }
     SRL_HIP_CHECK(h, hipGetLastError());
     return 0;
 }
@@ -1135,22 +1098,19 @@ int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, float *d_obs,
         return h->fail(SRLHIP_ENOTSUP, std::string(pol.hidden ? "rollout_mlp_policy" : "rollout_policy") + ": needs auto_reset and a device RNG mode (PHILOX or MT19937)");
     h->snap_valid = false;                      // the live state moves, the episode-parallel rollout's snapshot set does not
     dim3 grid(((int64_t)h->n * (pol.hidden ? kMlpLanes : 1) + kBlock - 1) / kBlock), block(kBlock);
-#define SRL_GO(K, MODE, KIND, DISC) hipLaunchKernelGGL((K<MODE, KIND, DISC>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T, pol, d_obs, d_rew, d_done, d_act_out)
-#define SRL_KIND(K, MODE, KIND) { if (p.is_discrete) SRL_GO(K, MODE, KIND, 1); else SRL_GO(K, MODE, KIND, 0); }
-#define SRL_MODE(K, MODE)                                                                        \
-    switch (p.kind) {                                                                            \
-        case SRLHIP_ENV_MOBILE: SRL_KIND(K, MODE, SRLHIP_ENV_MOBILE) break;                       \
-        case SRLHIP_ENV_MOBILE_1D: SRL_GO(K, MODE, SRLHIP_ENV_MOBILE_1D, 1); break;               \
-        case SRLHIP_ENV_MOBILE_2TARGET: SRL_GO(K, MODE, SRLHIP_ENV_MOBILE_2TARGET, 1); break;     \
-        default: SRL_KIND(K, MODE, SRLHIP_ENV_MOBILE_LINE)                                        \
-    }
-    // (MobileRobot1D / 2Target take discrete actions only: srlhip_create refuses the other combination)
-#define SRL_FAMILY(K) { if (h->cfg.rng_mode == SRLHIP_RNG_PHILOX) SRL_MODE(K, SRLHIP_RNG_PHILOX) else SRL_MODE(K, SRLHIP_RNG_MT19937) }
-    if (pol.hidden) SRL_FAMILY(mobile_rollout_mlp_k) else SRL_FAMILY(mobile_rollout_policy_k)
-#undef SRL_FAMILY
-#undef SRL_MODE
-#undef SRL_KIND
-#undef SRL_GO
+    dispatch_device_rng(h->cfg.rng_mode, [&](auto mode) {
+        dispatch_env(p, [&](auto kind, auto disc) {
+            constexpr int MODE = decltype(mode)::value, KIND = decltype(kind)::value, DISC = decltype(disc)::value;
+            if constexpr (policy_combination(KIND, DISC)) {
+                if (pol.hidden)
+                    hipLaunchKernelGGL((mobile_rollout_mlp_k<MODE, KIND, DISC>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T, pol,
+                                       d_obs, d_rew, d_done, d_act_out);
+                else
+                    hipLaunchKernelGGL((mobile_rollout_policy_k<MODE, KIND, DISC>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T,
+                                       pol, d_obs, d_rew, d_done, d_act_out);
+            }
+        });
+    });
     SRL_HIP_CHECK(h, hipGetLastError());
     return 0;
 }
@@ -1168,17 +1128,15 @@ int mobile_step(Handle *h, const void *d_actions, const double *d_noise, float *
 }
 
 // ---- persistent stepping, host side (api.hip: srlhip_set_persistent) --------------------------------------------------------------------
-template <int MODE> static const void *mobile_persist_fn(const MobileParams &p) {
-#define SRL_FN(KIND, DISC) reinterpret_cast<const void *>(mobile_persist_k<MODE, KIND, DISC>)
-#define SRL_KIND(KIND) (p.is_discrete ? SRL_FN(KIND, 1) : SRL_FN(KIND, 0))
-    switch (p.kind) {
-        case SRLHIP_ENV_MOBILE: return SRL_KIND(SRLHIP_ENV_MOBILE);
-        case SRLHIP_ENV_MOBILE_1D: return SRL_KIND(SRLHIP_ENV_MOBILE_1D);
-        case SRLHIP_ENV_MOBILE_2TARGET: return SRL_KIND(SRLHIP_ENV_MOBILE_2TARGET);
-        default: return SRL_KIND(SRLHIP_ENV_MOBILE_LINE);
-    }
-#undef SRL_KIND
-#undef SRL_FN
+// the resident kernel of this handle: what the occupancy query asks about is what mobile_persist_start launches
+static const void *mobile_persist_fn(const Handle *h, const MobileParams &p) {
+    const void *fn = nullptr;
+    dispatch_device_rng(h->cfg.rng_mode, [&](auto mode) {
+        dispatch_env(p, [&](auto kind, auto disc) {
+            fn = reinterpret_cast<const void *>(mobile_persist_k<decltype(mode)::value, decltype(kind)::value, decltype(disc)::value>);
+        });
+    });
+    return fn;
 }
 // workgroups of the resident kernel (0: no persistent form for this handle); capacity: how many the device holds at once;
 // eighths: which of the 8 `done` words it writes
@@ -1191,7 +1149,7 @@ int mobile_persist_blocks(Handle *h, int *capacity, uint32_t *eighths) {
     int per_cu = 0;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, c.device_id) != hipSuccess) return 0;
-    const void *fn = c.rng_mode == SRLHIP_RNG_PHILOX ? mobile_persist_fn<SRLHIP_RNG_PHILOX>(p) : mobile_persist_fn<SRLHIP_RNG_MT19937>(p);
+    const void *fn = mobile_persist_fn(h, p);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, 0) != hipSuccess) return 0;
     if (capacity) *capacity = per_cu * prop.multiProcessorCount;
     if (eighths) *eighths = strided_eighths(grid);
@@ -1199,22 +1157,12 @@ int mobile_persist_blocks(Handle *h, int *capacity, uint32_t *eighths) {
 }
 int mobile_persist_start(Handle *h, const void *d_actions, float *d_obs, float *d_rew, uint8_t *d_done, const PersistArgs &pa) {
     h->snap_valid = false; h->prefetch_valid = false;
-    const MobileParams p = params_of(h);
-    dim3 grid((h->n + kBlock - 1) / kBlock), block(kBlock);
-#define SRL_GO(MODE, KIND, DISC) hipLaunchKernelGGL((mobile_persist_k<MODE, KIND, DISC>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, d_actions, d_obs, d_rew, d_done, pa)
-#define SRL_KIND(MODE, KIND) { if (p.is_discrete) SRL_GO(MODE, KIND, 1); else SRL_GO(MODE, KIND, 0); }
-#define SRL_MODE(MODE)                                                                        \
-    switch (p.kind) {                                                                         \
-        case SRLHIP_ENV_MOBILE: SRL_KIND(MODE, SRLHIP_ENV_MOBILE) break;                       \
-        case SRLHIP_ENV_MOBILE_1D: SRL_KIND(MODE, SRLHIP_ENV_MOBILE_1D) break;                 \
-        case SRLHIP_ENV_MOBILE_2TARGET: SRL_KIND(MODE, SRLHIP_ENV_MOBILE_2TARGET) break;       \
-        default: SRL_KIND(MODE, SRLHIP_ENV_MOBILE_LINE)                                        \
-    }
-    if (h->cfg.rng_mode == SRLHIP_RNG_PHILOX) SRL_MODE(SRLHIP_RNG_PHILOX) else SRL_MODE(SRLHIP_RNG_MT19937)
-#undef SRL_MODE
-#undef SRL_KIND
-#undef SRL_GO
-    SRL_HIP_CHECK(h, hipGetLastError());
+    MobileParams p = params_of(h);
+    const void *fn = mobile_persist_fn(h, p);
+    if (!fn) return h->fail(SRLHIP_ENOTSUP, "persistent stepping: needs a device RNG mode (PHILOX or MT19937)");
+    PersistArgs args_pa = pa;
+    void *args[] = {&p, &h->mobile, &h->rng, &h->stats, &d_actions, &d_obs, &d_rew, &d_done, &args_pa};      // mobile_persist_k's parameters, in order
+    SRL_HIP_CHECK(h, hipLaunchKernel(fn, dim3((h->n + kBlock - 1) / kBlock), dim3(kBlock), args, 0, h->stream));
     return 0;
 }
 
