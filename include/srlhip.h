@@ -275,6 +275,37 @@ typedef struct srlhip_mlp_policy {
 int srlhip_rollout_mlp_policy(srlhip_handle h, int32_t T, const srlhip_mlp_policy *pol,
                               void *obs_TN, float *reward_TN, uint8_t *done_TN, void *act_out_TN);
 
+/* srlhip_rollout_mlp_policy with another action selection: the discrete action is DRAWN from the softmax of the scores, as CMA-ES does
+ * without --deterministic (rl_baselines/evolution_strategies/cma_es.py: np.random.choice(len(a), p=softmax(scores))).  Discrete action
+ * modes only.  The scores score_0 .. score_{A-1} are formed exactly as above.  At step t of the call (t = 0 .. T-1), for env e whose
+ * action-stream counter was c0 when the call began:
+ *     u   = Philox::to_double(o[0], o[1]) of the Philox4x32-10 block at counter c0 + t, stream 1, key of env e (its seed): the
+ *           generator's double01(), so u lies in [0, 1);
+ *     m   = max_k score_k;
+ *     w_k = exp(score_k - m) in float64, through the device math library;
+ *     c_k = w_0 + ... + w_k, added in index order;
+ *     z   = u * c_{A-1};
+ *     a   = the number of k < A-1 with z >= c_k      (the inverse CDF, branch-free: the last index takes whatever rounding leaves).
+ * An env frozen by freeze_after_done takes -1 as above; its draw at c0 + t is discarded, not skipped.  After the call the counter is
+ * c0 + T for every env, whatever happened in between: chunked calls equal one call, and the draws are random-access.
+ * The stream is the one srlhip_rollout(actions = NULL) draws the synthetic agent's actions from (one counter per env, reset to 0 by
+ * srlhip_seed), so a sampled rollout continues where that left off and the reverse.  What that call adds to the counter per step:
+ * MobileRobot family, discrete actions: 1 — but there the counter counts ACTIONS, four to a block (action i is word i % 4 of block
+ * i / 4), while this call reads the counter as a BLOCK index: after 40 synthetic steps from 0 the sampled call starts at block 40, and
+ * after T sampled steps the synthetic agent goes on at action c0 + T; MobileRobot continuous: 1 block; Kuka envs, discrete: 1 block;
+ * Kuka continuous: (action_dim + 1) / 2 blocks (2, or 4 in the joint-space mode).
+ * The draw does not depend on cfg.rng_mode: an MT19937 handle keeps the reference's np_random stream for the env and uses this Philox
+ * stream for the actions — the split the synthetic agent already has.
+ * The bits are fixed for a given build of this library.  exp is the device library's, so against another implementation of the
+ * contract the action is pinned only where z is not within the rounding of the c_k (tests/mlp_sample_ref.py: with the score bound
+ * above, E = 2 max_k tol_k and rho = expm1(E) + 2^-48, an action a is accepted iff (a == 0 or z (1 + rho) >= c_{a-1} (1 - rho)) and
+ * (a == A-1 or z (1 - rho) < c_a (1 + rho))).
+ * Refusals: everything srlhip_rollout_mlp_policy refuses, worded alike under the prefix "rollout_mlp_policy_sampled:", and
+ * SRLHIP_ENOTSUP for the continuous action modes (the message names "discrete": the reference never samples continuous actions).
+ * EINVAL cases, graph capture on device-pointer handles, NULL planes and the parking of a resident kernel are as above. */
+int srlhip_rollout_mlp_policy_sampled(srlhip_handle h, int32_t T, const srlhip_mlp_policy *pol,
+                                      void *obs_TN, float *reward_TN, uint8_t *done_TN, void *act_out_TN);
+
 /* Raw state access (checkpoint / parity): field ids below; arrays are
  * [num_envs] (or [k][num_envs] for vector fields) of the field's own type.
  * Always HOST pointers. */

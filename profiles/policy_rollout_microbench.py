@@ -18,7 +18,17 @@ envs (the reference's default CMA-ES population):
     mlp       srlhip_rollout_mlp_policy over T steps
     given     srlhip_rollout with the action plane the MLP rollout recorded
     per_step  the CMA-ES inner loop (cma_es.py, unchanged by the fused path): BatchedMLP.forward in float64 + argmax + where +
-              DeviceVecEnv.step, T times"""
+              DeviceVecEnv.step, T times
+
+--sampled times the sampled MLP rollout (srlhip_rollout_mlp_policy_sampled) beside the deterministic one from the same build, KukaButton
+and MobileRobot, --envs envs, the episode limit + 1 as T (1002 / 252: what CMA-ES --fused-rollout launches), H = 100, and one CMA-ES
+generation on the per-step path with softmax sampling against evaluate_fused with sampling (wall clock around a device synchronisation,
+reset included, at --envs and at 20 members):
+
+    mlp       srlhip_rollout_mlp_policy over T steps (--deterministic-only: this leg alone, e.g. on a build without the sampled entry point)
+    sampled   srlhip_rollout_mlp_policy_sampled over T steps
+    cma_per_step / cma_fused   one generation: reset + the per-step loop of CMAESModel.train (BatchedMLP.forward, softmax,
+              torch.multinomial, DeviceVecEnv.step until every member is done, checked every 16 steps) / reset + evaluate_fused"""
 import argparse
 import json
 import os
@@ -46,8 +56,19 @@ def main():
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--mlp", action="store_true")
+    ap.add_argument("--sampled", action="store_true")
+    ap.add_argument("--deterministic-only", action="store_true")
+    ap.add_argument("--no-cma", action="store_true")
     a = ap.parse_args()
     assert a.envs % 2 == 0
+    if a.sampled:
+        sampled_leg(a, "MobileRobotGymEnv-v0", 252, 2, 4, "philox", a.envs)
+        sampled_leg(a, "KukaButtonGymEnv-v0", 1002, 3, 6, "philox", a.envs)
+        if not a.deterministic_only and not a.no_cma:
+            for n in (a.envs, 20):
+                cma_leg(a, "MobileRobotGymEnv-v0", 252, n)
+                cma_leg(a, "KukaButtonGymEnv-v0", 1002, n)
+        return
     if a.mlp:
         for n in (a.envs, 20):
             mlp_leg(a, "KukaButtonGymEnv-v0", a.kuka_steps, 3, 6, "philox", n)
@@ -159,6 +180,91 @@ def mlp_leg(a, env_id, T, D, A, rng, n, H=100):
     out["mlp_over_per_step"] = out["mlp_ms"] / out["per_step_ms"]
     env.close()
     print(json.dumps(out))
+
+
+def sampled_leg(a, env_id, T, D, A, rng, n, H=100):
+    from rl_baselines.evolution_strategies.cma_es import BatchedMLP
+    env = DeviceVecEnv(env_id, n, seed=0, rng_mode=rng)
+    dev, h = env.device, env.h
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(0)
+    W = (0.5 * torch.randn((n, BatchedMLP(D, A, H).n_params), dtype=torch.float64, device=dev, generator=gen)).to(torch.float32).contiguous()
+    planes = (torch.empty((T, n, D), dtype=torch.float32, device=dev), torch.empty((T, n), dtype=torch.float32, device=dev),
+              torch.empty((T, n), dtype=torch.uint8, device=dev), torch.empty((T, n), dtype=torch.int32, device=dev))
+    ptrs = tuple(t.data_ptr() for t in planes)
+    legs = [("mlp", lambda: h.rollout_mlp_policy(T, W.data_ptr(), H, True, True, out=ptrs))]
+    if not a.deterministic_only:
+        legs.append(("sampled", lambda: h.rollout_mlp_policy(T, W.data_ptr(), H, True, True, out=ptrs, sample=True)))
+    out = {"env": env_id, "rng": rng, "envs": n, "steps": T, "hidden": H, "reps": a.reps, "freeze_after_done": True}
+    with torch.cuda.stream(env.torch_stream):
+        for name, fn in legs:
+            ms = []
+            for i in range(a.warmup + a.reps):
+                env.reset()
+                h.timing_begin()
+                fn()
+                t = h.timing_end()
+                if i >= a.warmup:
+                    ms.append(t)
+            out[name + "_ms"] = statistics.median(ms)
+            out[name + "_us_per_step"] = 1e3 * statistics.median(ms) / T
+            out[name + "_min_max_ms"] = [min(ms), max(ms)]
+    if "sampled_ms" in out:
+        out["sampled_over_mlp"] = out["sampled_ms"] / out["mlp_ms"]
+    env.close()
+    print(json.dumps(out), flush=True)
+
+
+def cma_leg(a, env_id, T, P, H=100):
+    import time
+    import types
+    from rl_baselines.evolution_strategies.cma_es import BatchedMLP, CMAESModel
+    env = CMAESModel.makeEnv(types.SimpleNamespace(env=env_id, num_cpu=P, seed=0, srl_model="ground_truth", num_stack=1))
+    dev = env.device
+    model = CMAESModel()
+    model.policy = BatchedMLP(env.observation_space.shape[0], env.action_space.n, H)
+    model.deterministic, model.continuous_actions = False, False
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(0)
+    population = 0.14 * torch.randn((P, model.policy.n_params), dtype=torch.float64, device=dev, generator=gen)
+
+    def per_step():
+        obs = env.reset()
+        done = torch.zeros(P, dtype=torch.bool, device=dev)
+        r = torch.zeros(P, dtype=torch.float64, device=dev)
+        k = 0
+        while True:
+            scores = model.policy.forward(population, obs)
+            act = torch.multinomial(torch.softmax(scores, dim=1), 1, generator=gen).squeeze(1)
+            act = torch.where(done, torch.full_like(act, -1), act).to(torch.int32).contiguous()
+            obs, reward, new_done = env.step(act)
+            done = done | (new_done != 0)
+            r += reward.to(torch.float64) * (~done).to(torch.float64)
+            k += 1
+            if k % 16 == 0 and bool(done.all()):
+                return k
+
+    def fused():
+        env.reset()
+        model.evaluate_fused(env, population, T)
+        return T
+
+    out = {"env": env_id, "population": P, "steps": T, "hidden": H, "reps": a.reps}
+    with torch.cuda.stream(env.torch_stream):
+        for name, fn in (("cma_per_step", per_step), ("cma_fused", fused)):
+            ms = []
+            for i in range(1 + a.reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out[name + "_env_steps"] = fn()
+                torch.cuda.synchronize()
+                if i >= 1:
+                    ms.append(1e3 * (time.perf_counter() - t0))
+            out[name + "_ms"] = statistics.median(ms)
+            out[name + "_min_max_ms"] = [min(ms), max(ms)]
+    out["per_step_over_fused"] = out["cma_per_step_ms"] / out["cma_fused_ms"]
+    env.close()
+    print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":

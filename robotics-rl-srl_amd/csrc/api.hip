@@ -628,6 +628,7 @@ struct PolicyCall {
     const char *what;              // what the struct calls its parameter block: "weights" / "params"
     size_t elem, count;            // bytes per parameter, parameters per policy
     int (*kuka)(Handle *, int, const PolicyArgs &, double *, float *, float *, uint8_t *, void *);
+    bool sample = false;           // srlhip_rollout_mlp_policy_sampled: the discrete action is drawn from the softmax of the scores
 };
 size_t policy_outputs(const srlhip_config &c) { return (size_t)(c.is_discrete ? num_actions_of(c) : action_dim_of(c)); }
 template <class P> PolicyArgs policy_args(const P &pol, const void *w, int32_t hidden) {
@@ -654,6 +655,7 @@ int rollout_policy(Handle *h, int32_t T, const PolicyCall &pc, PolicyArgs pa, co
     if (c.obs_mode == SRLHIP_OBS_JOINTS_POSITION) return fail(SRLHIP_ENOTSUP, "the joints_position observation mode is not supported (ground_truth only)");
     if (c.env_kind == SRLHIP_ENV_KUKA_RAND) return fail(SRLHIP_ENOTSUP, "KukaRandButtonGymEnv is not supported");
     if (!is_mobile(c.env_kind) && c.kuka_model != SRLHIP_KUKA_MODEL_FULL) return fail(SRLHIP_ENOTSUP, "the lumped Kuka model is not supported");
+    if (pc.sample && !c.is_discrete) return fail(SRLHIP_ENOTSUP, "only discrete actions are sampled (the reference never samples continuous ones)");
     int rc = set_device(h);                            // (parks a resident kernel)
     if (rc) return rc;
     const size_t D = (size_t)obs_dim_of(c), wcount = pc.count * (pa.per_env ? (size_t)h->n : 1);
@@ -676,7 +678,7 @@ int rollout_policy(Handle *h, int32_t T, const PolicyCall &pc, PolicyArgs pa, co
         if (pa.normalize) { pa.mean = blk; pa.std = blk + D; }
         if ((rc = stage_rollout_planes(h, T, dev))) return rc;
     }
-    rc = is_mobile(c.env_kind) ? mobile_rollout_policy(h, T, pa, static_cast<float *>(dev.obs), dev.rew, dev.done, dev.act)
+    rc = is_mobile(c.env_kind) ? mobile_rollout_policy(h, T, pa, pc.sample, static_cast<float *>(dev.obs), dev.rew, dev.done, dev.act)
                                : pc.kuka(h, T, pa, h->policy_hdr, static_cast<float *>(dev.obs), dev.rew, dev.done, dev.act);
     if (rc) return rc;
     return c.io_device ? 0 : fetch_rollout_planes(h, T, host, dev);      // (`packed` must outlive its copy: the synchronisation is in there)
@@ -834,19 +836,30 @@ int srlhip_rollout_policy(srlhip_handle hh, int32_t T, const srlhip_linear_polic
     return rollout_policy(h, T, pc, policy_args(*pol, pol->weights, 0), {obs_TN, reward_TN, done_TN, act_out_TN});
 }
 
-int srlhip_rollout_mlp_policy(srlhip_handle hh, int32_t T, const srlhip_mlp_policy *pol, void *obs_TN, float *reward_TN,
-                              uint8_t *done_TN, void *act_out_TN) {
+// srlhip_rollout_mlp_policy / srlhip_rollout_mlp_policy_sampled: one body, two names
+static int rollout_mlp_policy_entry(srlhip_handle hh, const std::string &name, bool sample, int32_t T, const srlhip_mlp_policy *pol,
+                                    const RolloutPlanes &host) {
     if (!hh) return SRLHIP_EINVAL;
     Handle *h = reinterpret_cast<Handle *>(hh);
-    if (!pol) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: null policy");
-    if (pol->struct_size != (int32_t)sizeof(srlhip_mlp_policy)) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: srlhip_mlp_policy.struct_size mismatch (ABI)");
-    int rc = policy_call_begin(h, "rollout_mlp_policy", T);
+    if (!pol) return h->fail(SRLHIP_EINVAL, name + ": null policy");
+    if (pol->struct_size != (int32_t)sizeof(srlhip_mlp_policy)) return h->fail(SRLHIP_EINVAL, name + ": srlhip_mlp_policy.struct_size mismatch (ABI)");
+    int rc = policy_call_begin(h, name.c_str(), T);
     if (rc) return rc;
-    if (pol->hidden < 1 || pol->hidden > 128) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: hidden must be in 1..128");
-    if (pol->reserved != 0) return h->fail(SRLHIP_EINVAL, "rollout_mlp_policy: reserved must be 0");
+    if (pol->hidden < 1 || pol->hidden > 128) return h->fail(SRLHIP_EINVAL, name + ": hidden must be in 1..128");
+    if (pol->reserved != 0) return h->fail(SRLHIP_EINVAL, name + ": reserved must be 0");
     const size_t D = (size_t)obs_dim_of(h->cfg), A = policy_outputs(h->cfg), H = (size_t)pol->hidden;
-    const PolicyCall pc{"rollout_mlp_policy", "params", 4, H * D + H + A * H + A, kuka_rollout_mlp_policy};
-    return rollout_policy(h, T, pc, policy_args(*pol, pol->params, pol->hidden), {obs_TN, reward_TN, done_TN, act_out_TN});
+    const PolicyCall pc{name.c_str(), "params", 4, H * D + H + A * H + A, sample ? kuka_rollout_mlp_policy_sampled : kuka_rollout_mlp_policy, sample};
+    return rollout_policy(h, T, pc, policy_args(*pol, pol->params, pol->hidden), host);
+}
+
+int srlhip_rollout_mlp_policy(srlhip_handle hh, int32_t T, const srlhip_mlp_policy *pol, void *obs_TN, float *reward_TN,
+                              uint8_t *done_TN, void *act_out_TN) {
+    return rollout_mlp_policy_entry(hh, "rollout_mlp_policy", false, T, pol, {obs_TN, reward_TN, done_TN, act_out_TN});
+}
+
+int srlhip_rollout_mlp_policy_sampled(srlhip_handle hh, int32_t T, const srlhip_mlp_policy *pol, void *obs_TN, float *reward_TN,
+                                      uint8_t *done_TN, void *act_out_TN) {
+    return rollout_mlp_policy_entry(hh, "rollout_mlp_policy_sampled", true, T, pol, {obs_TN, reward_TN, done_TN, act_out_TN});
 }
 
 int srlhip_get_state(srlhip_handle hh, int32_t field, void *out) {

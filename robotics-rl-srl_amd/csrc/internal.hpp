@@ -77,11 +77,12 @@ static_assert(sizeof(PolicyArgs) == 48 && offsetof(PolicyArgs, w) == 0 && offset
                   offsetof(PolicyArgs, clip) == 24 && offsetof(PolicyArgs, per_env) == 32 && offsetof(PolicyArgs, freeze) == 36 &&
                   offsetof(PolicyArgs, normalize) == 40 && offsetof(PolicyArgs, hidden) == 44,
               "PolicyArgs is a kernel argument: its layout is what the policy kernels were compiled against");
-// mobile.hip: the linear or the MLP kernel family by pol.hidden
-int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
-// kuka_tree_policy.hip / kuka_tree_mlp.hip (full model); d_hdr: the handle's 16-double policy header
+// mobile.hip: the linear or the MLP kernel family by pol.hidden; sample: the MLP's discrete action drawn from the softmax of its scores
+int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, bool sample, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
+// kuka_tree_policy.hip / kuka_tree_mlp.hip / kuka_tree_mlp_sample.hip (full model); d_hdr: the handle's 16-double policy header
 int kuka_rollout_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
 int kuka_rollout_mlp_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
+int kuka_rollout_mlp_policy_sampled(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
 int kuka_policy_header(Handle *h, double *d_hdr, const PolicyArgs &pol);      // kuka_tree_policy.hip: the one header kernel's launch
 int mobile_field(Handle *h, int field, void **dptr, size_t *elem, int *count);
 int mobile_reset_rand_count(const srlhip_config &c);

@@ -179,12 +179,16 @@ __device__ __forceinline__ double mlp_row_sum(double x) {
 // cost: profiles/NOTES.md AE).  At the loop top every lane computes its hidden units and its A
 // partial scores in float64 (unit order l, l + 16, ...), the partials are summed over the row lane 0 .. 15 in order (fmac_bcast with
 // weight 1: the same bits in every lane, the same order in every call), then the argmax / continuous row of POLICY = 1.
+// POLICY = 3 (srlhip_rollout_mlp_policy_sampled; kuka_tree_mlp_sample.hip): POLICY = 2 up to the six scores, discrete actions only
+// (JOINTS = false); the action is then drawn from their softmax with the env's own action stream (contract: include/srlhip.h), and
+// the exit store leaves that stream's counter T further on.
 template <int MODE, bool JOINTS, bool GIVEN, int NB, int RB = 0, int SPEC = 0, int PERSIST = 0, int POLICY = 0>
 __global__ void __launch_bounds__(kGroupBlock)
 kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int T, const void *actions, const double *noise,
                     float *obs, float *rew, uint8_t *done_out, void *act_out, PersistArgs pa) {
     static_assert(!PERSIST || GIVEN, "persistent stepping takes the caller's actions");
     static_assert(!POLICY || (!GIVEN && !PERSIST && !SPEC && !RB), "the policy source has generic, launching instantiations only");
+    static_assert(POLICY != 3 || !JOINTS, "only discrete actions are sampled");
     using namespace grp;
     __shared__ double scratch_all[kGroupEnvs][kTS];
     const int64_t n = p.n;
@@ -248,7 +252,7 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
     float mlp_w1[kMlpU][3], mlp_b1[kMlpU], mlp_w2[kMlpA][kMlpU], mlp_b2[kMlpA];
     const int mlp_A = cfg.is_discrete ? 6 : adim;
     (void)mlp_w1; (void)mlp_b1; (void)mlp_w2; (void)mlp_b2; (void)mlp_A;
-    if constexpr (POLICY == 2) {
+    if constexpr (POLICY >= 2) {
         const double *hdr = noise;
         const int A = cfg.is_discrete ? 6 : adim, H = (int)hdr[10];
         const float *w = static_cast<const float *>(actions) + (hdr[0] != 0.0 ? (int64_t)e * (3 * H + H + A * H + A) : 0);
@@ -380,7 +384,7 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
             asm volatile("" ::: "memory");                       // the action reads below stay behind the token (they are system-scope loads)
 #endif
         }
-        if constexpr (POLICY == 2) {
+        if constexpr (POLICY >= 2) {
             const float ob[3] = {(float)(v.grip[0] - v.bpos[0]), (float)(v.grip[1] - v.bpos[1]), (float)(v.grip[2] - v.bpos[2])};
             double x[3];
 #pragma unroll
@@ -404,7 +408,25 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
             double sc[kMlpA];
 #pragma unroll
             for (int k = 0; k < kMlpA; k++) sc[k] = k < mlp_A ? mlp_row_sum(part[k]) : 0.0;      // (uniform over the grid: rows the action form has)
-            if (cfg.is_discrete) {
+            if constexpr (POLICY == 3) {
+                // the action drawn from the softmax of the six scores (every lane of the row holds them bit for bit): lane k < 6 owns
+                // exp(sc[k] - m), the six weights come back over the row, every lane adds them up in index order and counts the partial
+                // sums z = u c_5 has reached — `a` is the same in all 16 lanes, as the step needs it.  u is the block at counter c0 + t of
+                // the env's action stream, formed by every lane (80 integer instructions next to a 50 k-cycle step) from the key and the
+                // counter the prologue loaded: those four words are all the sampling keeps live across the step.  A frozen env draws too.
+                double m = sc[0], own = sc[0];
+#pragma unroll
+                for (int k = 1; k < 6; k++) { m = sc[k] > m ? sc[k] : m; own = L.l == k ? sc[k] : own; }
+                const double wl = exp(own - m);
+                double c[6];
+                c[0] = bcast<0>(wl);
+                c[1] = c[0] + bcast<1>(wl); c[2] = c[1] + bcast<2>(wl); c[3] = c[2] + bcast<3>(wl); c[4] = c[3] + bcast<4>(wl); c[5] = c[4] + bcast<5>(wl);
+                Philox q = act;
+                q.ctr = act.ctr + (uint64_t)t;
+                const double z = q.double01() * c[5];
+#pragma unroll
+                for (int k = 0; k < 5; k++) a += z >= c[k] ? 1 : 0;
+            } else if (cfg.is_discrete) {
                 double best = sc[0];
 #pragma unroll
                 for (int k = 1; k < 6; k++) if (sc[k] > best) { best = sc[k]; a = k; }      // strict: the lowest index wins a tie
@@ -608,6 +630,7 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
         else if constexpr (MODE == SRLHIP_RNG_MT19937) rng0.store(rs.mt, e_out);
         else krng_store<MODE>(rng0, rs, e_out);
         if constexpr (!GIVEN && !POLICY) rs.act_ctr[e_out] = act.ctr;
+        if constexpr (POLICY == 3) rs.act_ctr[e_out] = act.ctr + (uint64_t)T;      // c0 + T, whatever happened in between
         st.ep_return[e_out] = ep_ret; st.ep_length[e_out] = ep_len;
         if (n_fin != n_fin0) { st.last_return[e_out] = last_ret; st.last_length[e_out] = last_len; }
         st.n_finished[e_out] = n_fin; st.last_reward[e_out] = last_reward;
@@ -684,6 +707,31 @@ int kuka_tree_policy_launch(Handle *h, const char *name, int T, const PolicyArgs
     if (c.rng_mode == SRLHIP_RNG_PHILOX) { SRL_TREE_POL_MODE(SRLHIP_RNG_PHILOX) } else { SRL_TREE_POL_MODE(SRLHIP_RNG_MT19937) }
 #undef SRL_TREE_POL_MODE
 #undef SRL_TREE_POL
+    SRL_HIP_CHECK(h, hipGetLastError());
+    return 0;
+}
+
+// srlhip_rollout_mlp_policy_sampled (POLICY = 3, kuka_tree_mlp_sample.hip): the same launch over {PHILOX, MT19937} x {Cartesian one
+// button, two buttons} — four kernels, discrete actions only (the entry point has refused the continuous modes by name).  A template
+// like its sibling, so that only the translation unit that calls it instantiates them.
+template <int POLICY>
+int kuka_tree_sampled_launch(Handle *h, const char *name, int T, const PolicyArgs &pol, double *d_hdr, float *obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
+    const srlhip_config &c = h->cfg;
+    if (!h->kuka || !h->kuka->full || c.env_kind == SRLHIP_ENV_KUKA_RAND || c.obs_mode != SRLHIP_OBS_GROUND_TRUTH || !c.auto_reset || !c.is_discrete ||
+        (c.rng_mode != SRLHIP_RNG_PHILOX && c.rng_mode != SRLHIP_RNG_MT19937))
+        return h->fail(SRLHIP_ENOTSUP, std::string(name) + ": no policy instantiation for this Kuka configuration");
+    const KukaParams p = params_of(h);
+    int rc = kuka_policy_header(h, d_hdr, pol);
+    if (rc) return rc;
+    dim3 grid(contiguous_grid((h->n + kGroupEnvs - 1) / kGroupEnvs)), block(kGroupBlock);      // as kuka_tree_policy_launch
+    const bool two = c.env_kind == SRLHIP_ENV_KUKA_2BUTTON;
+    const void *d_w = pol.w;
+    const double *hdr = d_hdr;
+    static_assert(POLICY == 3, "the sampling policy form");
+#define SRL_TREE_SMP(MODE, NB) hipLaunchKernelGGL((kuka_tree_rollout_k<MODE, false, false, NB, 0, 0, 0, POLICY>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, T, d_w, hdr, obs, d_rew, d_done, d_act_out, PersistArgs{})
+    if (c.rng_mode == SRLHIP_RNG_PHILOX) { if (two) SRL_TREE_SMP(SRLHIP_RNG_PHILOX, 2); else SRL_TREE_SMP(SRLHIP_RNG_PHILOX, 1); }
+    else { if (two) SRL_TREE_SMP(SRLHIP_RNG_MT19937, 2); else SRL_TREE_SMP(SRLHIP_RNG_MT19937, 1); }
+#undef SRL_TREE_SMP
     SRL_HIP_CHECK(h, hipGetLastError());
     return 0;
 }

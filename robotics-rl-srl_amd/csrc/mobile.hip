@@ -21,6 +21,7 @@
 //   mobile_rollout_ep_k       the same plane, episodes on separate lanes Philox + auto_reset, T >= 32   srlhip_rollout
 //   mobile_rollout_policy_k   a linear policy of the env's observation   Philox, MT           srlhip_rollout_policy
 //   mobile_rollout_mlp_k      a one-hidden-layer MLP of it, 16 lanes/env Philox, MT           srlhip_rollout_mlp_policy
+//   mobile_rollout_mlp_k<.., SAMPLE>  the same, action drawn from its softmax  Philox, MT        srlhip_rollout_mlp_policy_sampled
 //   mobile_persist_k          the host's mapped plane, one step per token Philox, MT          srlhip_set_persistent + srlhip_step
 //
 // Bit identity (all of it tested): mobile_rollout_k is oracle/mobile_oracle.c, step for step, in every RNG mode.
@@ -529,10 +530,41 @@ __device__ __forceinline__ float row_lead_f32(float x) {      // lane 0 of the r
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x150, 0xf, 0xf, false));
 }
 
-template <int MODE, int KIND, int DISC>
+// srlhip_rollout_mlp_policy_sampled: the discrete action drawn from the softmax of the A scores (contract: include/srlhip.h).  After
+// row_sum16 every lane of the row holds all A scores bit for bit, so the work goes ACROSS the row: every lane takes the maximum, lane
+// k < A the one exp(score_k - m) (the device library's float64 exp: ~100 instructions, once per step instead of A times in the lead
+// lane), the A weights come back over the row by DPP (row_newbcast:k), and the lead lane — which alone has drawn u — adds them up in
+// index order and counts the partial sums z = u * c_{A-1} has passed.  Every lane of the row must be active up to the broadcasts.
+template <int K> __device__ __forceinline__ double row_bcast_f64(double x) { return dpp_f64<0x150 + K>(x); }      // lane K of the row
+template <int A>
+__device__ __forceinline__ void softmax_weights(const double (&score)[A], int l, double (&w)[A]) {
+    double m = score[0], own = score[0];
+#pragma unroll
+    for (int k = 1; k < A; k++) { m = score[k] > m ? score[k] : m; own = l == k ? score[k] : own; }
+    const double e = exp(own - m);                  // lanes >= A repeat lane 0's: never read
+    w[0] = row_bcast_f64<0>(e); w[1] = row_bcast_f64<1>(e);
+    if constexpr (A == 4) { w[2] = row_bcast_f64<2>(e); w[3] = row_bcast_f64<3>(e); }
+}
+// the inverse CDF, branch-free: how many of c_0 .. c_{A-2} z has reached (the last index takes whatever rounding leaves)
+template <int A>
+__device__ __forceinline__ int softmax_pick(const double (&w)[A], double u) {
+    double c[A];
+    c[0] = w[0];
+#pragma unroll
+    for (int k = 1; k < A; k++) c[k] = c[k - 1] + w[k];
+    const double z = u * c[A - 1];
+    int a = 0;
+#pragma unroll
+    for (int k = 0; k < A - 1; k++) a += z >= c[k] ? 1 : 0;
+    return a;
+}
+
+// SAMPLE = false: srlhip_rollout_mlp_policy (the strict argmax / the continuous row); true: srlhip_rollout_mlp_policy_sampled
+template <int MODE, int KIND, int DISC, bool SAMPLE = false>
 __global__ void __launch_bounds__(kBlock)
 mobile_rollout_mlp_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, int T, PolicyArgs pol,
                      float *__restrict__ obs, float *__restrict__ rew, uint8_t *__restrict__ done_out, void *__restrict__ act_out) {
+    static_assert(!SAMPLE || DISC, "only discrete actions are sampled");
     constexpr int D = KIND == SRLHIP_ENV_MOBILE_1D ? 1 : 2;
     constexpr int A = DISC ? (KIND == SRLHIP_ENV_MOBILE_1D ? 2 : 4) : 2;
     const int tid = blockIdx.x * kBlock + threadIdx.x, l = tid & (kMlpLanes - 1);
@@ -562,11 +594,13 @@ mobile_rollout_mlp_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st
     MobileEnv m = {};
     EpisodeLane ep;
     float o[2] = {0.f, 0.f};
+    Philox draw = {};                                   // SAMPLE: the env's action stream (stream 1), at the counter the call found
     if (lead) {
         rng_load<MODE>(rng, rs, e, p.n, nullptr, 0, nullptr);
         load_env(s, e, m);
         ep.load(st, e);
         observe(p, m, o[0], o[1]);
+        if constexpr (SAMPLE) { draw.k0 = rs.key[e]; draw.k1 = rs.key[p.n + e]; draw.stream = 1; draw.ctr = rs.act_ctr[e]; }
     }
     bool frozen = false;
     for (int t = 0; t < T; t++) {
@@ -588,10 +622,17 @@ mobile_rollout_mlp_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st
         }
 #pragma unroll
         for (int a = 0; a < A; a++) score[a] = row_sum16(score[a]);
+        double sw[A];
+        (void)sw;
+        if constexpr (SAMPLE) softmax_weights<A>(score, l, sw);
         if (lead) {
             const int64_t row = (int64_t)t * p.n + e;
             int a; float a0, a1;
-            policy_action<DISC, A>(score, frozen, row, act_out, a, a0, a1);
+            if constexpr (SAMPLE) {
+                const int drawn = softmax_pick<A>(sw, draw.double01());      // one block per step: a frozen env's draw is discarded, not skipped
+                a = frozen ? -1 : drawn; a0 = 0.f; a1 = 0.f;
+                if (act_out) __builtin_nontemporal_store(a, static_cast<int32_t *>(act_out) + row);
+            } else policy_action<DISC, A>(score, frozen, row, act_out, a, a0, a1);
             double dv = 0.1 + rng.normal(0.0, 0.0);       // DELTA_POS + N(0, NOISE_STD = 0): drawn, value 0
             double reward; bool done;
             step_env<KIND, DISC>(p, m, a, a0, a1, dv, reward, done);
@@ -606,6 +647,7 @@ mobile_rollout_mlp_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st
     if (!lead) return;
     store_env(s, e, m);
     rng_store<MODE>(rng, rs, e);
+    if constexpr (SAMPLE) rs.act_ctr[e] = draw.ctr;   // c0 + T, whatever happened in between
     ep.store(st, e);
 }
 
@@ -1091,17 +1133,28 @@ int mobile_rollout(Handle *h, int T, const void *d_actions, float *d_obs, float 
     return 0;
 }
 
-// srlhip_rollout_policy (pol.hidden == 0: one lane per env) / srlhip_rollout_mlp_policy (16 lanes per env)
-int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
+// srlhip_rollout_policy (pol.hidden == 0: one lane per env) / srlhip_rollout_mlp_policy and, with `sample`, srlhip_rollout_mlp_policy_sampled
+// (16 lanes per env)
+int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, bool sample, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
     const MobileParams p = params_of(h);
     if ((h->cfg.rng_mode != SRLHIP_RNG_PHILOX && h->cfg.rng_mode != SRLHIP_RNG_MT19937) || !p.auto_reset)
-        return h->fail(SRLHIP_ENOTSUP, std::string(pol.hidden ? "rollout_mlp_policy" : "rollout_policy") + ": needs auto_reset and a device RNG mode (PHILOX or MT19937)");
+        return h->fail(SRLHIP_ENOTSUP, std::string(sample ? "rollout_mlp_policy_sampled" : pol.hidden ? "rollout_mlp_policy" : "rollout_policy") + ": needs auto_reset and a device RNG mode (PHILOX or MT19937)");
+    if (sample && (!pol.hidden || !p.is_discrete))
+        return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy_sampled: only the discrete actions of an MLP policy are sampled");
     h->snap_valid = false;                      // the live state moves, the episode-parallel rollout's snapshot set does not
+    if (sample) h->prefetch_valid = false;      // ... and the action-stream counters move past what the synthetic agent drew ahead
     dim3 grid(((int64_t)h->n * (pol.hidden ? kMlpLanes : 1) + kBlock - 1) / kBlock), block(kBlock);
     dispatch_device_rng(h->cfg.rng_mode, [&](auto mode) {
         dispatch_env(p, [&](auto kind, auto disc) {
             constexpr int MODE = decltype(mode)::value, KIND = decltype(kind)::value, DISC = decltype(disc)::value;
             if constexpr (policy_combination(KIND, DISC)) {
+                if constexpr (DISC == 1) {
+                    if (sample) {
+                        hipLaunchKernelGGL((mobile_rollout_mlp_k<MODE, KIND, 1, true>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T, pol,
+                                           d_obs, d_rew, d_done, d_act_out);
+                        return;
+                    }
+                }
                 if (pol.hidden)
                     hipLaunchKernelGGL((mobile_rollout_mlp_k<MODE, KIND, DISC>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T, pol,
                                        d_obs, d_rew, d_done, d_act_out);

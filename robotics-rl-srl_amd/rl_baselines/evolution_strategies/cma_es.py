@@ -17,7 +17,13 @@ device.  Learned-from-pixels policies (the reference's CNNPolicyPytorch) are not
 --fused-rollout (off by default; the envs ARS fuses; ground-truth observations, --deterministic or --continuous-actions, no frame
 stacking): one generation is reset + ONE srlhip_rollout_mlp_policy launch — the population, cast to float32 as the reference's torch
 parameters are, is the kernel's parameter plane as it is, member k's MLP picks env k's actions inside the kernel — and the returns
-come from the reward / done planes.  Softmax sampling (no --deterministic) stays on the per-step path."""
+come from the reward / done planes.  Softmax sampling (no --deterministic) stays on the per-step path unless --fused-sampling is given.
+
+--fused-sampling (off by default; needs --fused-rollout and discrete actions): the reference's default form — no --deterministic, each
+member's action drawn from the softmax of its scores (cma_es.py:228-232) — in the same one launch (srlhip_rollout_mlp_policy_sampled).
+The action draws then come from each env's own counter-based action stream (Philox stream 1, keyed by seed and env id), not from the
+`torch.multinomial` generator of the per-step path: the two paths sample the same distribution but not the same bits.  (The reference
+draws from the global np.random: no per-env stream could reproduce it either.)"""
 import math
 import pickle
 import time
@@ -149,13 +155,29 @@ class CMAESModel(object):
                             help='evaluate each generation with one fused MLP-policy rollout launch (ground-truth observations; needs '
                                  '--deterministic or --continuous-actions and --num-stack 1; not KukaRandButton). The training '
                                  'callback then fires once per generation, not once per env step')
+        parser.add_argument('--fused-sampling', action='store_true', default=False,
+                            help='with --fused-rollout and discrete actions: draw each action from the softmax of the scores inside '
+                                 'the fused launch (no --deterministic needed). The draws come from each env\'s own action stream, not '
+                                 'from the torch.multinomial generator of the per-step path: same distribution, other bits')
         return parser
 
     HIDDEN = 100                        # MLPPolicyPytorch(obs_dim, [100], n_actions)
 
-    # --fused-rollout: the argument rules and the episode limits are ARS's
+    # --fused-rollout: the episode limits are ARS's, and so are the argument rules behind CMA-ES's own for --fused-sampling
     FUSED_EPISODE_LIMIT = ARSModel.FUSED_EPISODE_LIMIT
-    check_fused_arguments = staticmethod(ARSModel.check_fused_arguments)
+
+    @staticmethod
+    def check_fused_arguments(args):
+        """--fused-sampling against the rest of the arguments, then ARS's rules for --fused-rollout, whose "--deterministic or
+        --continuous-actions" requirement --fused-sampling meets; raises ValueError before any env is built."""
+        if not getattr(args, "fused_sampling", False):
+            return ARSModel.check_fused_arguments(args)
+        if not getattr(args, "fused_rollout", False):
+            raise ValueError("--fused-sampling needs --fused-rollout")
+        if getattr(args, "continuous_actions", False):
+            raise ValueError("--fused-sampling needs discrete actions (not --continuous-actions): continuous actions are never sampled")
+        met = type(args)(**dict(vars(args), deterministic=True))       # ARS's rules with that one requirement met
+        return ARSModel.check_fused_arguments(met)
 
     @staticmethod
     def returns_from_planes(reward, done):
@@ -168,8 +190,11 @@ class CMAESModel(object):
 
     def evaluate_fused(self, env, population, T):
         """One generation in one launch (the env was just reset): member k's MLP drives env k, frozen after its first done ->
-        (r [P] float64, live_steps [P] int64)."""
-        planes = env.rollout_mlp_policy(T, population.to(torch.float32).contiguous(), self.policy.H, per_env=True, freeze_after_done=True)
+        (r [P] float64, live_steps [P] int64).  A model that is neither deterministic nor continuous samples its actions (the
+        argument rules have asked for --fused-sampling)."""
+        sample = self.deterministic is False and not self.continuous_actions       # (None, a model train() has not configured: the argmax)
+        kw = {"sample": True} if sample else {}
+        planes = env.rollout_mlp_policy(T, population.to(torch.float32).contiguous(), self.policy.H, per_env=True, freeze_after_done=True, **kw)
         return self.returns_from_planes(planes["reward"], planes["done"])
 
     @classmethod

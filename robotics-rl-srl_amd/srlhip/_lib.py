@@ -37,7 +37,7 @@ _FIELD_SHAPES = {
 EXPORTS = [
     "srlhip_abi_version", "srlhip_default_config", "srlhip_create", "srlhip_destroy", "srlhip_obs_dim",
     "srlhip_obs_bytes", "srlhip_action_dim", "srlhip_num_actions", "srlhip_seed", "srlhip_reset",
-    "srlhip_reset_rand_count", "srlhip_step", "srlhip_step_async", "srlhip_step_wait", "srlhip_step_pending", "srlhip_set_persistent", "srlhip_rollout", "srlhip_rollout_policy", "srlhip_rollout_mlp_policy", "srlhip_get_state", "srlhip_set_state",
+    "srlhip_reset_rand_count", "srlhip_step", "srlhip_step_async", "srlhip_step_wait", "srlhip_step_pending", "srlhip_set_persistent", "srlhip_rollout", "srlhip_rollout_policy", "srlhip_rollout_mlp_policy", "srlhip_rollout_mlp_policy_sampled", "srlhip_get_state", "srlhip_set_state",
     "srlhip_device_ptr", "srlhip_render", "srlhip_episode_stats", "srlhip_episode_records", "srlhip_episode_stats_device", "srlhip_sync", "srlhip_copy_async", "srlhip_stream", "srlhip_timing_begin",
     "srlhip_timing_end", "srlhip_last_error", "srlhip_selftest_group_primitives", "srlhip_selftest_rng", "srlhip_kuka_kernel", "srlhip_kuka_default_model", "srlhip_set_kuka_model", "srlhip_kuka_tree_default_model", "srlhip_set_kuka_tree_model",
     "srlhip_graph_begin", "srlhip_graph_end", "srlhip_graph_launch", "srlhip_graph_destroy",
@@ -145,6 +145,7 @@ def load():
     lib.srlhip_rollout.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     lib.srlhip_rollout_policy.argtypes = [vp, i32, ctypes.POINTER(LinearPolicy), vp, vp, vp, vp]
     lib.srlhip_rollout_mlp_policy.argtypes = [vp, i32, ctypes.POINTER(MlpPolicy), vp, vp, vp, vp]
+    lib.srlhip_rollout_mlp_policy_sampled.argtypes = [vp, i32, ctypes.POINTER(MlpPolicy), vp, vp, vp, vp]
     lib.srlhip_get_state.argtypes = [vp, i32, vp]
     lib.srlhip_set_state.argtypes = [vp, i32, vp]
     lib.srlhip_device_ptr.argtypes = [vp, i32, ctypes.POINTER(vp)]
@@ -384,17 +385,18 @@ class Handle(object):
         return hidden * self.obs_dim + hidden + a * hidden + a
 
     def rollout_mlp_policy(self, T, params, hidden, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0,
-                           want=("obs", "reward", "done", "actions"), out=None):
+                           want=("obs", "reward", "done", "actions"), out=None, sample=False):
         """srlhip_rollout_mlp_policy: rollout_policy with a one-hidden-layer ReLU MLP as the score function.  `params`: float32
         [num_envs][P] (per_env) or [P], P = mlp_param_count(hidden), in nn.Module.parameters() order (fc_in.weight [H][D],
         fc_in.bias [H], fc_out.weight [A][H], fc_out.bias [A]) — a CMA-ES population as it is.  Everything else as rollout_policy
-        (device-pointer handles: raw device pointers and `out`)."""
+        (device-pointer handles: raw device pointers and `out`).  sample=True: srlhip_rollout_mlp_policy_sampled — discrete actions
+        only, the action drawn from the softmax of the scores with the env's own action stream (include/srlhip.h has the contract)."""
         pol = self._policy_struct(MlpPolicy, per_env, freeze_after_done, obs_mean, obs_std, clip_obs)
         pol.hidden, pol.reserved = int(hidden), 0
         shape = None                                   # (hidden outside 1..128: the library refuses by name)
         if 1 <= int(hidden) <= 128:
             shape = ((self.num_envs,) if per_env else ()) + (self.mlp_param_count(int(hidden)),)
-        return self._rollout_policy_call("srlhip_rollout_mlp_policy", T, pol, "params", params, np.float32, shape,
+        return self._rollout_policy_call("srlhip_rollout_mlp_policy_sampled" if sample else "srlhip_rollout_mlp_policy", T, pol, "params", params, np.float32, shape,
                                          obs_mean, obs_std, want, out)
 
     def get_state(self, field):

@@ -119,12 +119,14 @@ class DeviceVecEnv(object):
         return self._rollout_policy(self.h.rollout_policy, T, weights, torch.float64, self.h.policy_shape(per_env),
                                     per_env, freeze_after_done, obs_mean, obs_std, clip_obs)
 
-    def rollout_mlp_policy(self, T, params, hidden, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0):
+    def rollout_mlp_policy(self, T, params, hidden, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0,
+                           sample=False):
         """srlhip_rollout_mlp_policy on tensors: rollout_policy with a one-hidden-layer ReLU MLP.  `params`: float32 CUDA tensor
         [N][P] (or [P] with per_env=False), P = h.mlp_param_count(hidden), nn.Module.parameters() order.  Enqueue-only; returns
-        the same dict of new [T][N]... tensors."""
+        the same dict of new [T][N]... tensors.  sample=True (discrete actions): srlhip_rollout_mlp_policy_sampled, the action drawn
+        from the softmax of the scores with each env's own action stream."""
         shape = ((self.num_envs,) if per_env else ()) + (self.h.mlp_param_count(int(hidden)),)
-        return self._rollout_policy(functools.partial(self.h.rollout_mlp_policy, hidden=hidden), T, params, torch.float32, shape,
+        return self._rollout_policy(functools.partial(self.h.rollout_mlp_policy, hidden=hidden, sample=sample), T, params, torch.float32, shape,
                                     per_env, freeze_after_done, obs_mean, obs_std, clip_obs)
 
     def episode_stats(self):
@@ -264,17 +266,17 @@ class DeviceVecNormalize(DeviceVecEnvWrapper):
     def get_original_obs(self):
         return self.old_obs
 
-    def _rollout_frozen(self, call, *args, per_env=True, freeze_after_done=False):
+    def _rollout_frozen(self, call, *args, per_env=True, freeze_after_done=False, **more):
         """`call` (the wrapped env's rollout_policy / rollout_mlp_policy) on NORMALISED observations: the current statistics
         (sqrt(var + eps) as std, clip_obs) are handed to the kernel and stay frozen for the whole call.  With training = False this
         equals the per-step path.  With training = True the statistics are then updated ONCE, from the returned raw observation
         planes — only rows up to and including each env's first done when freeze_after_done is set (all rows otherwise): a different
         schedule than step()'s update before every action.  Returns the raw planes; rewards are not normalised."""
         if not self.norm_obs:
-            return call(*args, per_env=per_env, freeze_after_done=freeze_after_done)
+            return call(*args, per_env=per_env, freeze_after_done=freeze_after_done, **more)
         mean = self.obs_rms.mean.reshape(-1).contiguous()
         std = torch.sqrt(self.obs_rms.var + self.epsilon).reshape(-1).contiguous()
-        out = call(*args, per_env=per_env, freeze_after_done=freeze_after_done, obs_mean=mean, obs_std=std, clip_obs=self.clip_obs)
+        out = call(*args, per_env=per_env, freeze_after_done=freeze_after_done, obs_mean=mean, obs_std=std, clip_obs=self.clip_obs, **more)
         if self.training:
             obs = out["obs"]
             if freeze_after_done:
@@ -290,10 +292,11 @@ class DeviceVecNormalize(DeviceVecEnvWrapper):
         raw planes; rewards are not normalised."""
         return self._rollout_frozen(self.venv.rollout_policy, T, weights, per_env=per_env, freeze_after_done=freeze_after_done)
 
-    def rollout_mlp_policy(self, T, params, hidden, per_env=True, freeze_after_done=False):
+    def rollout_mlp_policy(self, T, params, hidden, per_env=True, freeze_after_done=False, sample=False):
         """rollout_policy's schedule for the MLP policy: the current statistics are frozen for the call and, with training = True,
-        updated once afterwards from the live rows of the returned raw observation planes."""
-        return self._rollout_frozen(self.venv.rollout_mlp_policy, T, params, hidden, per_env=per_env, freeze_after_done=freeze_after_done)
+        updated once afterwards from the live rows of the returned raw observation planes.  `sample` passes through."""
+        return self._rollout_frozen(self.venv.rollout_mlp_policy, T, params, hidden, per_env=per_env, freeze_after_done=freeze_after_done,
+                                    **({"sample": True} if sample else {}))
 
     def reset(self):
         obs = self.venv.reset()

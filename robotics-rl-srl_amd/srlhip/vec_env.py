@@ -508,10 +508,12 @@ class HipVecEnv(object):
         kw = dict(per_env=per_env, freeze_after_done=freeze_after_done, obs_mean=obs_mean, obs_std=obs_std, clip_obs=clip_obs)
         return self._fused_policy(weights, np.float64, per_env, lambda h, w: h.rollout_policy(n_steps, w, **kw))
 
-    def rollout_mlp_policy(self, n_steps, params, hidden, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0):
+    def rollout_mlp_policy(self, n_steps, params, hidden, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0,
+                           sample=False):
         """rollout_policy with a one-hidden-layer ReLU MLP (_lib.Handle.rollout_mlp_policy): each shard gets its rows of per-env
-        `params` (float32 [N][P])."""
-        kw = dict(per_env=per_env, freeze_after_done=freeze_after_done, obs_mean=obs_mean, obs_std=obs_std, clip_obs=clip_obs)
+        `params` (float32 [N][P]).  sample=True draws the discrete action from the softmax of the scores; every shard draws from its
+        envs' own action streams, whose keys and counters follow the GLOBAL env id: the shards together equal one handle bit for bit."""
+        kw = dict(per_env=per_env, freeze_after_done=freeze_after_done, obs_mean=obs_mean, obs_std=obs_std, clip_obs=clip_obs, sample=sample)
         return self._fused_policy(params, np.float32, per_env, lambda h, w: h.rollout_mlp_policy(n_steps, w, hidden, **kw))
 
     def get_images(self):
