@@ -29,6 +29,7 @@
 #include "internal.hpp"
 #include "kuka_core.hpp"
 #include "kuka_tree_model.hpp"
+#include "raster.hpp"
 
 namespace srl {
 
@@ -37,28 +38,8 @@ struct RasterMobileView { const double *x, *y, *tx, *ty, *t2x, *t2y; const int32
 
 namespace {
 
-constexpr int kRasterBlock = 256;
-constexpr int kMaxPrims = 28;   // Kuka scene 16 (full model: body + two finger + two tip capsules; lumped 14) + second button 2 or ten distractors + ball 11
-constexpr int kTilePixels = 8192;       // LDS band buffer (24 KiB): whole 8-row tile strips, image width <= 1024
-
-enum { PRIM_PLANE = 0, PRIM_BOX = 1, PRIM_CYL = 2, PRIM_CAPSULE = 3 };
-
-struct Prim {
-    int type;
-    float r, g, b;
-    float ax, ay, az;      // plane: (., ., z0)  box: centre  cylinder: base centre  capsule: end a
-    float bx, by, bz;      // box: half extents             cylinder: (radius, ., height)  capsule: end b
-    float rad;             // capsule radius
-    float cs, sn;          // box: cos/sin of the yaw about z
-};
-
-struct Camera {
-    float ex, ey, ez;      // eye
-    float fx, fy, fz;      // forward (unit)
-    float rx, ry, rz;      // right   (unit)
-    float ux, uy, uz;      // up      (unit)
-    float tan_half_fov;
-};
+// primitives, cameras, ray tests and screen footprints: raster.hpp (the same text runs on the host under tests/)
+using namespace srlraster;
 
 struct RasterParams {
     int32_t kind, n, h, w, channels, ncam;
@@ -74,101 +55,6 @@ __device__ __forceinline__ void set_prim(Prim &p, int type, float r, float g, fl
                                          float bx, float by, float bz, float rad, float cs, float sn) {
     p.type = type; p.r = r; p.g = g; p.b = b; p.ax = ax; p.ay = ay; p.az = az; p.bx = bx; p.by = by; p.bz = bz;
     p.rad = rad; p.cs = cs; p.sn = sn;
-}
-
-// ---- ray / primitive intersection: returns t (> 0) or -1, and the surface normal ----------------------
-// The hit functions return t only, plus a 3-bit `code` that says which face / part was hit: normals are evaluated once, for
-// the nearest hit (prim_normal), not for every candidate — their divisions were a third of a capsule test.
-//   box: axis | 4 when the face normal points along +axis;  cylinder: 0 side, 1 cap;  capsule: 0 body, 1 sphere at a, 2 sphere at b
-__device__ __forceinline__ float hit_plane(const Prim &p, float oz, float dz) {
-    if (dz == 0.0f) return -1.0f;
-    const float t = (p.az - oz) / dz;
-    return t > 0.0f ? t : -1.0f;
-}
-
-__device__ __forceinline__ float hit_box(const Prim &p, float ox, float oy, float oz, float dx, float dy, float dz, int &code) {
-    // into the box frame (rotation about z by -yaw)
-    const float px = ox - p.ax, py = oy - p.ay, pz = oz - p.az;
-    const float lox = p.cs * px + p.sn * py, loy = p.cs * py - p.sn * px;
-    const float ldx = p.cs * dx + p.sn * dy, ldy = p.cs * dy - p.sn * dx;
-    float tmin = -3.0e38f, tmax = 3.0e38f;
-    int axis = 0; float sign = 0.0f;
-    const float o[3] = {lox, loy, pz}, d[3] = {ldx, ldy, dz}, h[3] = {p.bx, p.by, p.bz};
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        if (d[k] == 0.0f) {
-            if (o[k] < -h[k] || o[k] > h[k]) return -1.0f;
-        } else {
-            const float inv = 1.0f / d[k];
-            float t0 = (-h[k] - o[k]) * inv, t1 = (h[k] - o[k]) * inv;
-            float s = -1.0f;
-            if (t0 > t1) { const float tt = t0; t0 = t1; t1 = tt; s = 1.0f; }
-            if (t0 > tmin) { tmin = t0; axis = k; sign = s; }
-            if (t1 < tmax) tmax = t1;
-        }
-    }
-    if (tmin > tmax || tmin <= 0.0f) return -1.0f;
-    code = axis | (sign > 0.0f ? 4 : 0);
-    return tmin;
-}
-
-__device__ __forceinline__ float hit_cylinder(const Prim &p, float ox, float oy, float oz, float dx, float dy, float dz, int &code) {
-    const float R = p.bx, z0 = p.az, z1 = p.az + p.bz;
-    const float px = ox - p.ax, py = oy - p.ay;
-    float best = -1.0f;
-    const float a = dx * dx + dy * dy;
-    if (a > 0.0f) {
-        const float b = px * dx + py * dy, c = px * px + py * py - R * R;
-        const float disc = b * b - a * c;
-        if (disc >= 0.0f) {
-            const float t = (-b - sqrtf(disc)) / a;
-            const float z = oz + t * dz;
-            if (t > 0.0f && z >= z0 && z <= z1) { best = t; code = 0; }
-        }
-    }
-    if (dz != 0.0f) {       // caps (the top one is what a camera above ever sees)
-        const float zc = dz < 0.0f ? z1 : z0;
-        const float t = (zc - oz) / dz;
-        if (t > 0.0f && (best < 0.0f || t < best)) {
-            const float hx = px + t * dx, hy = py + t * dy;
-            if (hx * hx + hy * hy <= R * R) { best = t; code = 1; }
-        }
-    }
-    return best;
-}
-
-__device__ __forceinline__ float hit_capsule(const Prim &p, float ox, float oy, float oz, float dx, float dy, float dz, int &code) {
-    const float bax = p.bx - p.ax, bay = p.by - p.ay, baz = p.bz - p.az;
-    const float oax = ox - p.ax, oay = oy - p.ay, oaz = oz - p.az;
-    const float baba = bax * bax + bay * bay + baz * baz;
-    const float bard = bax * dx + bay * dy + baz * dz;
-    const float baoa = bax * oax + bay * oay + baz * oaz;
-    const float rdoa = dx * oax + dy * oay + dz * oaz;
-    const float oaoa = oax * oax + oay * oay + oaz * oaz;
-    const float a = baba - bard * bard;
-    float b = baba * rdoa - baoa * bard;
-    float c = baba * oaoa - baoa * baoa - p.rad * p.rad * baba;
-    float h = b * b - a * c;
-    if (h < 0.0f || baba == 0.0f) return -1.0f;
-    float t = -1.0f, y = 0.0f;
-    bool body = false;
-    code = 0;
-    if (a > 0.0f) {
-        t = (-b - sqrtf(h)) / a;
-        y = baoa + t * bard;
-        body = y > 0.0f && y < baba;
-    }
-    if (!body) {            // one of the two end spheres
-        const float ocx = y <= 0.0f ? oax : ox - p.bx, ocy = y <= 0.0f ? oay : oy - p.by, ocz = y <= 0.0f ? oaz : oz - p.bz;
-        b = dx * ocx + dy * ocy + dz * ocz;
-        c = ocx * ocx + ocy * ocy + ocz * ocz - p.rad * p.rad;
-        h = b * b - c;
-        if (h < 0.0f) return -1.0f;
-        t = -b - sqrtf(h);
-        code = y <= 0.0f ? 1 : 2;
-    }
-    if (t <= 0.0f) return -1.0f;
-    return t;
 }
 
 // normal of primitive p where the ray (eye o, unit direction d) hits it at parameter t; code as left by its hit function
@@ -406,14 +292,6 @@ __device__ __forceinline__ uint32_t shade_hit(const Prim &p, const Camera &c, fl
     return finish_pixel(true, nx, ny, nz, cr, cg, cb);
 }
 
-__device__ __forceinline__ float hit_prim(const Prim &p, const Camera &c, float dx, float dy, float dz, int &code) {
-    code = 0;
-    if (p.type == PRIM_PLANE) return hit_plane(p, c.ez, dz);
-    if (p.type == PRIM_BOX) return hit_box(p, c.ex, c.ey, c.ez, dx, dy, dz, code);
-    if (p.type == PRIM_CYL) return hit_cylinder(p, c.ex, c.ey, c.ez, dx, dy, dz, code);
-    return hit_capsule(p, c.ex, c.ey, c.ez, dx, dy, dz, code);
-}
-
 // z-test of the unit ray (dx, dy, dz) from the eye against the primitives in `mask` (wave-uniform), starting from `best`;
 // false = nothing nearer than `best`, else rgb is the shaded winner
 __device__ __forceinline__ bool trace(const Prim *prims, uint64_t mask, const Camera &c, float dx, float dy, float dz, float best,
@@ -431,47 +309,12 @@ __device__ __forceinline__ bool trace(const Prim *prims, uint64_t mask, const Ca
     return true;
 }
 
-__device__ __forceinline__ void pixel_ray(const Camera &c, float sx, float sy, float &dx, float &dy, float &dz) {
-    dx = c.fx + sx * c.rx + sy * c.ux; dy = c.fy + sx * c.ry + sy * c.uy; dz = c.fz + sx * c.rz + sy * c.uz;
-    const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
-    dx *= inv; dy *= inv; dz *= inv;
-}
-
 __device__ __forceinline__ uint32_t shade_pixel(const Prim *prims, uint64_t mask, const Camera &c, float sx, float sy) {
     float dx, dy, dz;
     pixel_ray(c, sx, sy, dx, dy, dz);
     uint32_t rgb;
     if (trace(prims, mask, c, dx, dy, dz, 3.0e38f, rgb)) return rgb;
     return finish_pixel(false, 0.0f, 0.0f, 1.0f, 0.92f, 0.92f, 0.92f);                                   // background
-}
-
-// Conservative screen rectangle (tangent-space x = X/Z, y = Y/Z in the camera frame) of a primitive: the eight
-// corners of its world-space bounding box are projected; anything reaching behind the near plane covers the screen.
-__device__ void prim_screen_rect(const Prim &p, const Camera &c, float rect[4]) {
-    float lo[3], hi[3];
-    if (p.type == PRIM_PLANE) { rect[0] = -3.0e38f; rect[1] = 3.0e38f; rect[2] = -3.0e38f; rect[3] = 3.0e38f; return; }
-    if (p.type == PRIM_BOX) {
-        const float hx = fabsf(p.cs) * p.bx + fabsf(p.sn) * p.by, hy = fabsf(p.sn) * p.bx + fabsf(p.cs) * p.by;
-        lo[0] = p.ax - hx; hi[0] = p.ax + hx; lo[1] = p.ay - hy; hi[1] = p.ay + hy; lo[2] = p.az - p.bz; hi[2] = p.az + p.bz;
-    } else if (p.type == PRIM_CYL) {
-        lo[0] = p.ax - p.bx; hi[0] = p.ax + p.bx; lo[1] = p.ay - p.bx; hi[1] = p.ay + p.bx; lo[2] = p.az; hi[2] = p.az + p.bz;
-    } else {
-        lo[0] = fminf(p.ax, p.bx) - p.rad; hi[0] = fmaxf(p.ax, p.bx) + p.rad;
-        lo[1] = fminf(p.ay, p.by) - p.rad; hi[1] = fmaxf(p.ay, p.by) + p.rad;
-        lo[2] = fminf(p.az, p.bz) - p.rad; hi[2] = fmaxf(p.az, p.bz) + p.rad;
-    }
-    const float eps = 1.0e-3f;                      // slack for float rounding of the projection
-    float x0 = 3.0e38f, x1 = -3.0e38f, y0 = 3.0e38f, y1 = -3.0e38f;
-    bool behind = false;
-    for (int k = 0; k < 8; k++) {
-        const float wx = ((k & 1) ? hi[0] : lo[0]) - c.ex, wy = ((k & 2) ? hi[1] : lo[1]) - c.ey, wz = ((k & 4) ? hi[2] : lo[2]) - c.ez;
-        const float z = wx * c.fx + wy * c.fy + wz * c.fz;
-        if (z <= 0.05f) { behind = true; break; }
-        const float x = (wx * c.rx + wy * c.ry + wz * c.rz) / z, y = (wx * c.ux + wy * c.uy + wz * c.uz) / z;
-        x0 = fminf(x0, x); x1 = fmaxf(x1, x); y0 = fminf(y0, y); y1 = fmaxf(y1, y);
-    }
-    if (behind) { rect[0] = -3.0e38f; rect[1] = 3.0e38f; rect[2] = -3.0e38f; rect[3] = 3.0e38f; return; }
-    rect[0] = x0 - eps; rect[1] = x1 + eps; rect[2] = y0 - eps; rect[3] = y1 + eps;
 }
 
 // Tile-order path: every wavefront walks 8x8 pixel tiles and z-tests, in registers, the primitives whose rectangle overlaps
@@ -499,7 +342,7 @@ raster_tiles_k(RasterParams rp, RasterKukaView kv, RasterMobileView mv, uint8_t 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lx = lane & 7, ly = lane >> 3;
     uint8_t *out = img + (int64_t)e * npix * rp.channels;
     // bands of whole 8-row tile strips that fit the LDS tile buffer; inside a band every wavefront walks 8x8 tiles
-    const int band_rows = max(8, (kTilePixels / rp.w) & ~7);
+    const int band_rows = tile_band_rows(rp.w);
     const int tiles_x = (rp.w + 7) >> 3;
     const float inv_w2 = 2.0f / (float)rp.w, inv_h2 = 2.0f / (float)rp.h;
     for (int row0 = 0; row0 < rp.h; row0 += band_rows) {
@@ -510,13 +353,10 @@ raster_tiles_k(RasterParams rp, RasterKukaView kv, RasterMobileView mv, uint8_t 
         // carry 1e-3 of slack — so reciprocals instead of divisions
         for (int t = threadIdx.x; t < ntiles; t += kRasterBlock) {
             const int tyy = t / tiles_x, txx = t - tyy * tiles_x, col0 = txx * 8, r0 = row0 + tyy * 8;
-            const float tx0 = ((float)col0 * inv_w2 - 1.0f) * c.tan_half_fov;
-            const float tx1 = ((float)(col0 + 8) * inv_w2 - 1.0f) * c.tan_half_fov;
-            const float ty1 = (1.0f - (float)r0 * inv_h2) * c.tan_half_fov;
-            const float ty0 = (1.0f - (float)(r0 + 8) * inv_h2) * c.tan_half_fov;
+            const TileRect tr = tile_rect(c, r0, col0, inv_w2, inv_h2);
             uint32_t m = 0;
             for (int k = 0; k < np; k++)
-                if (rects[k][0] <= tx1 && rects[k][1] >= tx0 && rects[k][2] <= ty1 && rects[k][3] >= ty0) m |= 1u << k;
+                if (tile_overlaps(rects[k], tr)) m |= 1u << k;
             tile_masks[t] = m;
         }
         __syncthreads();
@@ -537,8 +377,8 @@ raster_tiles_k(RasterParams rp, RasterKukaView kv, RasterMobileView mv, uint8_t 
                         trace(prims, mask, c, ray.x, ray.y, ray.z, ray.w, rgb);
                     }
                 } else {
-                    const float sx = (((float)col + 0.5f) / (float)rp.w * 2.0f - 1.0f) * c.tan_half_fov;
-                    const float sy = (1.0f - ((float)row + 0.5f) / (float)rp.h * 2.0f) * c.tan_half_fov;
+                    float sx, sy;
+                    pixel_centre(c, row, col, rp.h, rp.w, sx, sy);
                     rgb = shade_pixel(prims, mask, c, sx, sy);
                 }
                 const int i = (row - row0) * rp.w + col;
@@ -561,102 +401,6 @@ raster_tiles_k(RasterParams rp, RasterKukaView kv, RasterMobileView mv, uint8_t 
     }
 }
 
-// ---- object-order path (cameras with a cached background) ------------------------------------------------------------------
-// Screen footprint of one moving primitive in pixel units, conservative: rows r0..r1, columns c0..c1 and — for capsules — the
-// slab around the projected axis: in row r the columns within hw of xc0 + (r - r0) * kx.  W bounds the columns of any one row.
-struct Span {
-    int32_t r0, r1, c0, c1, W;
-    float xc0, kx, hw;
-    int32_t rpc, cch, inv_w;       // chunking: row spans per 64-lane chunk, chunks per row (W > 64), ceil(65536 / W)
-};
-
-// what hit_capsule derives from the capsule and the eye alone, evaluated once per (env, camera) with the same expressions
-struct CapsK { float bax, bay, baz, oax, oay, oaz, obx, oby, obz, baba, baoa, c, ca, cb; };
-
-__device__ void capsule_constants(const Prim &p, const Camera &cam, CapsK &k) {
-    k.bax = p.bx - p.ax; k.bay = p.by - p.ay; k.baz = p.bz - p.az;
-    k.oax = cam.ex - p.ax; k.oay = cam.ey - p.ay; k.oaz = cam.ez - p.az;
-    k.obx = cam.ex - p.bx; k.oby = cam.ey - p.by; k.obz = cam.ez - p.bz;
-    k.baba = k.bax * k.bax + k.bay * k.bay + k.baz * k.baz;
-    k.baoa = k.bax * k.oax + k.bay * k.oay + k.baz * k.oaz;
-    const float oaoa = k.oax * k.oax + k.oay * k.oay + k.oaz * k.oaz;
-    k.c = k.baba * oaoa - k.baoa * k.baoa - p.rad * p.rad * k.baba;
-    k.ca = k.oax * k.oax + k.oay * k.oay + k.oaz * k.oaz - p.rad * p.rad;
-    k.cb = k.obx * k.obx + k.oby * k.oby + k.obz * k.obz - p.rad * p.rad;
-}
-
-// hit_capsule with the per-capsule part taken from CapsK: same operations in the same order, so the same t
-__device__ __forceinline__ float hit_capsule_k(const CapsK &k, float dx, float dy, float dz, int &code) {
-    const float bard = k.bax * dx + k.bay * dy + k.baz * dz;
-    const float rdoa = dx * k.oax + dy * k.oay + dz * k.oaz;
-    const float a = k.baba - bard * bard;
-    float b = k.baba * rdoa - k.baoa * bard;
-    float h = b * b - a * k.c;
-    if (h < 0.0f || k.baba == 0.0f) return -1.0f;
-    float t = -1.0f, y = 0.0f;
-    bool body = false;
-    code = 0;
-    if (a > 0.0f) {
-        t = (-b - sqrtf(h)) / a;
-        y = k.baoa + t * bard;
-        body = y > 0.0f && y < k.baba;
-    }
-    if (!body) {            // one of the two end spheres
-        const bool at_a = y <= 0.0f;
-        b = dx * (at_a ? k.oax : k.obx) + dy * (at_a ? k.oay : k.oby) + dz * (at_a ? k.oaz : k.obz);
-        h = b * b - (at_a ? k.ca : k.cb);
-        if (h < 0.0f) return -1.0f;
-        t = -b - sqrtf(h);
-        code = at_a ? 1 : 2;
-    }
-    return t > 0.0f ? t : -1.0f;
-}
-
-// A capsule's surface point q = c + rad * n (c on the axis, |n| = 1) projects within rad * sqrt(1 + |c'|^2) / (Zc - rad) of
-// c' = (Xc, Yc) / Zc (Cauchy-Schwarz on Zc * n_xy - n_z * (Xc, Yc)); c' runs along the 2-D segment a'b', |c'|^2 is convex on
-// it and Zc is linear, so one radius R2 from the endpoints bounds the whole silhouette: a stadium around a'b'.
-__device__ void prim_span(const Prim &p, const Camera &c, int w, int h, Span &s) {
-    float rect[4];
-    prim_screen_rect(p, c, rect);
-    s.xc0 = 0.0f; s.kx = 0.0f; s.hw = 3.0e38f;
-    const float half_w = 0.5f * (float)w, half_h = 0.5f * (float)h, inv_tan = 1.0f / c.tan_half_fov;
-    bool slab = false;
-    float xa = 0.0f, ya = 0.0f, xb = 0.0f, yb = 0.0f, R2 = 0.0f;
-    if (p.type == PRIM_CAPSULE) {
-        const float wax = p.ax - c.ex, way = p.ay - c.ey, waz = p.az - c.ez, wbx = p.bx - c.ex, wby = p.by - c.ey, wbz = p.bz - c.ez;
-        const float za = wax * c.fx + way * c.fy + waz * c.fz, zb = wbx * c.fx + wby * c.fy + wbz * c.fz;
-        const float zmin = fminf(za, zb) - p.rad;
-        if (zmin > 0.05f) {
-            xa = (wax * c.rx + way * c.ry + waz * c.rz) / za; ya = (wax * c.ux + way * c.uy + waz * c.uz) / za;
-            xb = (wbx * c.rx + wby * c.ry + wbz * c.rz) / zb; yb = (wbx * c.ux + wby * c.uy + wbz * c.uz) / zb;
-            R2 = p.rad * sqrtf(1.0f + fmaxf(xa * xa + ya * ya, xb * xb + yb * yb)) / zmin * 1.001f + 1.0e-3f;
-            rect[0] = fmaxf(rect[0], fminf(xa, xb) - R2); rect[1] = fminf(rect[1], fmaxf(xa, xb) + R2);
-            rect[2] = fmaxf(rect[2], fminf(ya, yb) - R2); rect[3] = fminf(rect[3], fmaxf(ya, yb) + R2);
-            slab = true;
-        }
-    }
-    // tangent space -> pixel index of the pixel whose centre is there: col = (x / tan + 1) * w / 2 - 1/2, row = (1 - y / tan) * h / 2 - 1/2
-    const float cf0 = (rect[0] * inv_tan + 1.0f) * half_w - 0.5f, cf1 = (rect[1] * inv_tan + 1.0f) * half_w - 0.5f;
-    const float rf0 = (1.0f - rect[3] * inv_tan) * half_h - 0.5f, rf1 = (1.0f - rect[2] * inv_tan) * half_h - 0.5f;
-    s.c0 = (int)ceilf(fminf(fmaxf(cf0, 0.0f), (float)w)); s.c1 = (int)floorf(fminf(fmaxf(cf1, -1.0f), (float)(w - 1)));
-    s.r0 = (int)ceilf(fminf(fmaxf(rf0, 0.0f), (float)h)); s.r1 = (int)floorf(fminf(fmaxf(rf1, -1.0f), (float)(h - 1)));
-    s.W = max(s.c1 - s.c0 + 1, 0);
-    if (slab && s.W > 0 && s.r1 >= s.r0) {
-        const float dx = xb - xa, dy = yb - ya, len = sqrtf(dx * dx + dy * dy);
-        if (fabsf(dy) > 1.0e-4f * len && len > 0.0f) {
-            // the axis' column in row r: x = xa + (y_r - ya) * dx / dy with y_r = (1 - (r + 1/2) * 2 / h) * tan
-            const float slope = dx / dy, px = half_w * inv_tan;
-            const float y0 = (1.0f - ((float)s.r0 + 0.5f) / half_h) * c.tan_half_fov;
-            s.xc0 = ((xa + (y0 - ya) * slope) * inv_tan + 1.0f) * half_w - 0.5f;
-            s.kx = -slope * px * c.tan_half_fov / half_h;
-            s.hw = R2 * len / fabsf(dy) * px + 0.01f;
-            if (s.hw < 0.5f * (float)w) s.W = min(s.W, (int)floorf(2.0f * s.hw) + 2); else s.hw = 3.0e38f;
-        }
-    }
-    const int W = max(s.W, 1);
-    s.rpc = max(1, 64 / W); s.cch = (W + 63) >> 6; s.inv_w = W <= 64 ? (65536 + W - 1) / W : 0;
-}
-
 // One 256-lane workgroup per (env, cached camera).  The moving primitives are rasterised in object order: each one's footprint
 // (Span) is cut into 64-pixel chunks — several short row spans side by side — that the workgroup's wavefronts share; a lane
 // fetches its pixel's cached ray (the next chunk's load is in flight while this one is tested), runs the exact ray test of
@@ -665,7 +409,6 @@ __device__ void prim_span(const Prim &p, const Camera &c, int w, int h, Span &s)
 // Resolve: pixels without a hit take the cached background colour, the others are gathered into a dense list and shaded
 // (so the divergent normal code runs on full wavefronts); the colours replace the z-buffer words in place and the band is
 // flushed 4 pixels = 12 bytes per lane.  Pixels no footprint covers are never ray-tested.
-constexpr int kBandPixels = 2048;          // 16 KiB z-buffer + 4 KiB hit list: seven workgroups per CU
 constexpr uint32_t kNoHit = 0xffffffffu;
 
 struct Item { int k, row, col; bool valid; };
@@ -696,7 +439,7 @@ raster_k(RasterParams rp, RasterKukaView kv, RasterMobileView mv, uint8_t *img) 
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     uint8_t *out = img + (int64_t)e * npix * rp.channels;
     // bands: whole rows, a multiple of 4 pixels (the resolve and the flush work on groups of 4)
-    const int band_rows = max(1, kBandPixels / rp.w);
+    const int band_rows = span_band_rows(rp.w);
     const bool quads = (rp.w & 3) == 0 && rp.w <= kBandPixels;
     const bool packed = quads && rp.channels == 3 && ((reinterpret_cast<uintptr_t>(out)) & 3) == 0;
     for (int row0 = 0; row0 < rp.h; row0 += band_rows) {
@@ -704,11 +447,7 @@ raster_k(RasterParams rp, RasterKukaView kv, RasterMobileView mv, uint8_t *img) 
         for (int i = tid; i < (count + 1) / 2; i += kRasterBlock) reinterpret_cast<u32x4 *>(zbuf)[i] = u32x4{kNoHit, kNoHit, kNoHit, kNoHit};
         if (tid == 0) nhits = 0;
         __syncthreads();                                                   // spans written (first band) / previous band flushed
-        if (tid >= first && tid < np) {
-            const Span &s = spans[tid];
-            const int pr0 = max(s.r0, row0), pr1 = min(s.r1, last_row);
-            chunks[tid] = (pr1 >= pr0 && s.W > 0) ? ((pr1 - pr0 + s.rpc) / s.rpc) * s.cch : 0;
-        }
+        if (tid >= first && tid < np) chunks[tid] = span_band_chunks(spans[tid], row0, last_row);
         __syncthreads();
         // ---- z-test, object order --------------------------------------------------------------------------------------
         int k = first, kbase = 0;
@@ -718,18 +457,8 @@ raster_k(RasterParams rp, RasterKukaView kv, RasterMobileView mv, uint8_t *img) 
             while (k < np && q >= kbase + kcnt) { kbase += kcnt; k++; kcnt = k < np ? __builtin_amdgcn_readfirstlane(chunks[k]) : 0; }
             it.k = k; it.row = 0; it.col = 0; it.valid = false;
             if (k >= np) return it;
-            const Span &s = spans[k];
-            const int W = s.W, qq = q - kbase;
-            int group = qq, cc = 0;
-            if (s.cch > 1) { group = qq / s.cch; cc = qq - group * s.cch; }
-            const int rr = (lane * s.inv_w) >> 16;                                      // lane / W (0 when W > 64)
-            const int i = cc * 64 + lane - rr * W;
-            it.row = max(s.r0, row0) + group * s.rpc + rr;
-            const float centre = s.xc0 + (float)(it.row - s.r0) * s.kx;
-            const int lo = s.hw < 1.0e30f ? max(s.c0, (int)ceilf(centre - s.hw)) : s.c0;
-            const int hi = s.hw < 1.0e30f ? min(s.c1, (int)floorf(centre + s.hw)) : s.c1;
-            it.col = lo + i;
-            it.valid = rr < s.rpc && i < W && it.row <= min(s.r1, last_row) && it.col <= hi;
+            const SpanPixel px = span_locate(spans[k], row0, last_row, q - kbase, lane);
+            it.row = px.row; it.col = px.col; it.valid = px.valid;
             return it;
         };
         Item cur = locate(wave);
@@ -818,9 +547,8 @@ raster_bg_k(RasterParams rp, RasterKukaView kv, RasterMobileView mv, int cam, fl
     const int i = blockIdx.x * kRasterBlock + threadIdx.x;
     if (i >= rp.h * rp.w) return;
     const int row = i / rp.w, col = i - row * rp.w;
-    const float sx = (((float)col + 0.5f) / (float)rp.w * 2.0f - 1.0f) * c.tan_half_fov;
-    const float sy = (1.0f - ((float)row + 0.5f) / (float)rp.h * 2.0f) * c.tan_half_fov;
-    float dx, dy, dz;
+    float sx, sy, dx, dy, dz;
+    pixel_centre(c, row, col, rp.h, rp.w, sx, sy);
     pixel_ray(c, sx, sy, dx, dy, dz);
     // nearest static hit: the depth is kept beside the ray so that the per-env pass starts its z-test from it
     float best = 3.0e38f;
@@ -832,33 +560,6 @@ raster_bg_k(RasterParams rp, RasterKukaView kv, RasterMobileView mv, int cam, fl
     }
     rays[i] = make_float4(dx, dy, dz, best);
     bg[i] = win >= 0 ? shade_hit(prims[win], c, dx, dy, dz, best, wcode) : finish_pixel(false, 0.0f, 0.0f, 1.0f, 0.92f, 0.92f, 0.92f);
-}
-
-// pybullet computeViewMatrixFromYawPitchRoll (upAxisIndex = 2): eye = target + Rz(yaw) Ry(roll) Rx(pitch) (0,-d,0),
-// up = R (0,0,1); negative pitch looks down from above.
-Camera make_camera(const double target[3], double dist, double yaw_deg, double pitch_deg, double roll_deg, double fov_deg) {
-    const double d2r = 3.14159265358979323846 / 180.0;
-    const double cy = cos(yaw_deg * d2r), sy = sin(yaw_deg * d2r), cp = cos(pitch_deg * d2r), sp = sin(pitch_deg * d2r);
-    const double cr = cos(roll_deg * d2r), sr = sin(roll_deg * d2r);
-    // R = Rz(yaw) * Ry(roll) * Rx(pitch)
-    const double Rm[3][3] = {{cy * cr, cy * sr * sp - sy * cp, cy * sr * cp + sy * sp},
-                             {sy * cr, sy * sr * sp + cy * cp, sy * sr * cp - cy * sp},
-                             {-sr, cr * sp, cr * cp}};
-    double eye[3], up[3], f[3], r[3], u[3];
-    for (int k = 0; k < 3; k++) { eye[k] = target[k] + Rm[k][1] * (-dist); up[k] = Rm[k][2]; f[k] = target[k] - eye[k]; }
-    double nf = sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
-    for (int k = 0; k < 3; k++) f[k] /= nf;
-    r[0] = f[1] * up[2] - f[2] * up[1]; r[1] = f[2] * up[0] - f[0] * up[2]; r[2] = f[0] * up[1] - f[1] * up[0];
-    double nr = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-    for (int k = 0; k < 3; k++) r[k] /= nr;
-    u[0] = r[1] * f[2] - r[2] * f[1]; u[1] = r[2] * f[0] - r[0] * f[2]; u[2] = r[0] * f[1] - r[1] * f[0];
-    Camera c;
-    c.ex = (float)eye[0]; c.ey = (float)eye[1]; c.ez = (float)eye[2];
-    c.fx = (float)f[0]; c.fy = (float)f[1]; c.fz = (float)f[2];
-    c.rx = (float)r[0]; c.ry = (float)r[1]; c.rz = (float)r[2];
-    c.ux = (float)u[0]; c.uy = (float)u[1]; c.uz = (float)u[2];
-    c.tan_half_fov = (float)tan(fov_deg * d2r / 2);
-    return c;
 }
 
 }  // namespace
@@ -876,17 +577,10 @@ int raster_render(Handle *h, void *d_img) {
     RasterKukaView kv = {};
     RasterMobileView mv = {};
     if (c.env_kind >= SRLHIP_ENV_KUKA_BUTTON) {
-        const double t1[3] = {0.316, -0.2, -0.1}, t2[3] = {0.316, 0.316, -0.105};
-        rp.cam[0] = make_camera(t1, 1.1, 145, -36, 0, 60);        // kuka_button_gym_env.py:94-102
-        rp.cam[1] = make_camera(t2, 1.05, 32, -13, 0, 60);        // :403-409 (multi_view)
+        kuka_cameras(rp.cam);
         kuka_raster_view(h, &kv);
     } else {
-        const double t[3] = {2, c.env_kind == SRLHIP_ENV_MOBILE_1D ? 0.0 : 2.0, 0};
-        rp.cam[0] = make_camera(t, 4.4, 90, -90, 0, 60);          // mobile_robot_env.py:76-84, 1D :33
-        // fpv=True (mobile_robot_env.py:313-332): camera target (robot_x - 0.25, robot_y, 0.15), distance 0.3, yaw = the
-        // env's camera yaw, pitch -17, fov 90; stored relative to the robot, the kernel adds each env's (x, y)
-        const double tf[3] = {-0.25, 0.0, 0.15};
-        rp.cam[1] = make_camera(tf, 0.3, 90, -17, 0, 90);
+        mobile_cameras(c.env_kind == SRLHIP_ENV_MOBILE_1D, rp.cam);
         const MobileState &s = h->mobile;
         mv.x = s.pos_x; mv.y = s.pos_y; mv.tx = s.tgt_x; mv.ty = s.tgt_y; mv.t2x = s.tgt2_x; mv.t2y = s.tgt2_y; mv.cur = s.cur_target;
     }
