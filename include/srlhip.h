@@ -306,6 +306,56 @@ int srlhip_rollout_mlp_policy(srlhip_handle h, int32_t T, const srlhip_mlp_polic
 int srlhip_rollout_mlp_policy_sampled(srlhip_handle h, int32_t T, const srlhip_mlp_policy *pol,
                                       void *obs_TN, float *reward_TN, uint8_t *done_TN, void *act_out_TN);
 
+/* The policy's action as a call of its own: ONE step of the three fused rollouts' action selection, from an observation plane the
+ * caller already holds on the device — the state vectors an SRL encoder made of the rendered frames (image -> encoder -> state ->
+ * policy), where no policy can sit inside the physics kernel.  A T-step rollout on learned states is T x (srlhip_policy_act,
+ * srlhip_step, srlhip_encoder_forward), every call enqueue-only on the handle's stream, no host read in the loop.
+ * Exactly one of `linear` / `mlp` is non-null; the structs are the fused rollouts', unchanged, with obs_dim (D, 1..1024) in the place of
+ * the handle's own observation size (weights [D][A], params P = H D + H + A H + A, obs_mean / obs_std [D]; A = num_actions or
+ * action_dim of the handle).  Device-pointer handles only (cfg.io_device = 1; SRLHIP_ENOTSUP otherwise), ANY env kind, model and
+ * observation mode, raw pixels included: the call reads the handle's action space and its action-stream counters, never the env state.
+ *   obs        float32 [num_envs][D]
+ *   done_prev  uint8 [num_envs], the done plane of the step that produced obs, or NULL at the first step of a rollout; only bit 0 counts
+ *              (bit 1 is cfg.info_bits')
+ *   frozen     uint8 [num_envs], read and written when pol.freeze_after_done (required then): first frozen |= done_prev & 1, then a
+ *              frozen env takes the `None` action of srlhip_linear_policy.freeze_after_done (-1; Kuka continuous: a row of NaNs, bits
+ *              0x7fc00000; MobileRobot continuous: a zero row).  The caller zeroes the plane at the start of a rollout.  Without
+ *              freeze_after_done neither plane is read or written.
+ *   act_out    int32 [num_envs] or float32 [num_envs][A]: the row the caller wants written, e.g. row t of a [T][num_envs] plane.
+ *   score_out  NULL, or float64 [num_envs][A]: the scores as they stood in front of the selection (frozen envs included) — what the
+ *              tests compare bit for bit; a rollout passes NULL.
+ * ARITHMETIC, order-exact (csrc/policy_act.hpp is its one text for device and host, built with -ffp-contract=off: no product is fused
+ * with the sum that takes it; tests/policy_act_ref.py restates it in numpy bit for bit):
+ *   x_d      = o_d, or with normalize (float) min(max(((double)o_d - mean[d]) / std[d], -clip_obs), clip_obs)
+ *   linear   score_a = (double)x_0 W[0][a] + (double)x_1 W[1][a] + ..., d ascending in float64; the sum starts with the d = 0 product
+ *   MLP      pre_j = (double)b1_j + (double)W1[j][0] (double)x_0 + ..., d ascending; h_j = pre_j > 0 ? pre_j : +0.0.
+ *            A virtual row of 16 lanes: lane l owns the units l, l + 16, ... < H; its partial p_l starts from (double)b2_a (lane 0) or
+ *            +0.0 (lanes 1..15) and takes (double)W2[a][j] h_j for its units in ascending order.  The sixteen partials are combined in
+ *            four stages, in each of which every lane adds its partner's value to its own: partner l ^ 1, then l ^ 2, then 7 - l inside
+ *            each half of eight lanes, then 15 - l; score_a is what lane 0 then holds (every lane holds the same bits).
+ *   These are the sums of srlhip_rollout_policy / srlhip_rollout_mlp_policy with the freedom taken out: the fused MobileRobot kernels
+ *   compute exactly this, the fused Kuka kernels may fuse a product with its sum.  Against any other float64 summation of the same
+ *   terms: |difference| <= (2 D + H + 16) 2^-53 S_a,  S_a = |b2_a| + sum_j |W2[a][j]| (|b1_j| + sum_d |W1[j][d] x_d|) — a chain of D + 1
+ *   roundings per unit and at most 13 behind it on this side, at most D + H + 2 on the other, to first order.  (The 2^-46 of
+ *   srlhip_rollout_mlp_policy is this figure at H = 128 and the D <= 3 of a ground-truth observation; at D = 1024 it is 2^-41.9.)
+ *   selection  discrete: the strict argmax, lowest index first; continuous: the row (float)score_a; sample != 0 (MLP and discrete action
+ *            modes only): the inverse-CDF draw of srlhip_rollout_mlp_policy_sampled word for word (m, w_k, c_k, z, a; exp from the
+ *            device math library), with u from the Philox block at the env's CURRENT action-stream counter c, stream 1.
+ * COUNTER: a sampled call leaves c + 1 for EVERY env, frozen or not, and advances it inside the kernel — a captured call draws fresh
+ * numbers at every replay.  One srlhip_policy_act(sample) equals one step of srlhip_rollout_mlp_policy_sampled: K calls from c0 use
+ * the blocks c0 .. c0 + K - 1 that one fused call with T = K uses, and leave c0 + K as it does; the counter is the one
+ * srlhip_rollout(actions = NULL) draws from (what that call adds per step: see above).  As there, the draw does not depend on cfg.rng_mode.
+ * A non-sampled call does not touch the counter.
+ * The result for env e depends on its own row of obs, its parameters, done_prev[e], frozen[e] and its counter alone: not on num_envs,
+ * on e, or on the launch geometry — shards and batch sizes agree bit for bit.
+ * One launch on the handle's stream, no allocation, no synchronisation; capturable under srlhip_graph_begin.  Every parameter block is
+ * read once (a shared block: once per workgroup of four envs).  SRLHIP_EINVAL: both or neither policy, a wrong struct_size, hidden
+ * outside 1..128, reserved != 0, obs_dim outside 1..1024, sample with a linear policy, a null obs / act_out / parameter block, normalize
+ * without mean and std, freeze_after_done without the frozen plane, a pending srlhip_step_async.  SRLHIP_ENOTSUP: a host-pointer
+ * handle; sample on a continuous action mode (the message names "discrete").  A resident persistent kernel parks. */
+int srlhip_policy_act(srlhip_handle h, const srlhip_linear_policy *linear, const srlhip_mlp_policy *mlp, int32_t sample,
+                      const float *obs, int32_t obs_dim, const uint8_t *done_prev, uint8_t *frozen, void *act_out, double *score_out);
+
 /* Raw state access (checkpoint / parity): field ids below; arrays are
  * [num_envs] (or [k][num_envs] for vector fields) of the field's own type.
  * Always HOST pointers. */

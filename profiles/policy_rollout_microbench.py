@@ -28,7 +28,12 @@ reset included, at --envs and at 20 members):
     mlp       srlhip_rollout_mlp_policy over T steps (--deterministic-only: this leg alone, e.g. on a build without the sampled entry point)
     sampled   srlhip_rollout_mlp_policy_sampled over T steps
     cma_per_step / cma_fused   one generation: reset + the per-step loop of CMAESModel.train (BatchedMLP.forward, softmax,
-              torch.multinomial, DeviceVecEnv.step until every member is done, checked every 16 steps) / reset + evaluate_fused"""
+              torch.multinomial, DeviceVecEnv.step until every member is done, checked every 16 steps) / reset + evaluate_fused
+    pixel (--pixel)   learned SRL states (KukaButton, 64x64 frames, state_dim 200, hidden 100; 4096 and 20 envs), T steps each way,
+              alternating: pixel_fused = PixelStateVecEnv.rollout_mlp_policy (T x (srlhip_policy_act, step + rasteriser, encoder), enqueue
+              only) / pixel_per_step = PixelStateVecEnv.step + BatchedMLP.forward + argmax in torch on the same stream with a done.all()
+              read every 16 steps, as cma_es.py does.  Then policy_act alone at 4096 x (D 200, H 100) next to a device-to-device copy
+              of the same parameter bytes, alternating."""
 import argparse
 import json
 import os
@@ -59,8 +64,15 @@ def main():
     ap.add_argument("--sampled", action="store_true")
     ap.add_argument("--deterministic-only", action="store_true")
     ap.add_argument("--no-cma", action="store_true")
+    ap.add_argument("--pixel", action="store_true")
+    ap.add_argument("--pixel-steps", type=int, default=64)
     a = ap.parse_args()
     assert a.envs % 2 == 0
+    if a.pixel:
+        for n in (a.envs, 20):
+            pixel_leg(a, n, a.pixel_steps)
+        act_alone_leg(a, a.envs)
+        return
     if a.sampled:
         sampled_leg(a, "MobileRobotGymEnv-v0", 252, 2, 4, "philox", a.envs)
         sampled_leg(a, "KukaButtonGymEnv-v0", 1002, 3, 6, "philox", a.envs)
@@ -265,6 +277,101 @@ def cma_leg(a, env_id, T, P, H=100):
     out["per_step_over_fused"] = out["cma_per_step_ms"] / out["cma_fused_ms"]
     env.close()
     print(json.dumps(out), flush=True)
+
+
+def _timed(fn, sync):
+    """one call of fn between two host clock reads, the device drained before and after"""
+    import time
+    sync()
+    t0 = time.perf_counter()
+    fn()
+    sync()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def _report(name, n, T, ms, extra=None):
+    ms = sorted(ms)
+    out = {"leg": name, "envs": n, "steps": T, "ms_median": statistics.median(ms), "ms_min": ms[0], "ms_max": ms[-1], "reps": len(ms)}
+    out["us_per_step"] = 1e3 * out["ms_median"] / T
+    out["env_steps_per_s"] = n * T / (out["ms_median"] * 1e-3)
+    out.update(extra or {})
+    print(json.dumps(out), flush=True)
+    return out
+
+
+def pixel_leg(a, n, T, D=200, H=100):
+    from rl_baselines.evolution_strategies.cma_es import BatchedMLP
+    from srlhip.pixel_env import PixelStateVecEnv
+    from state_representation.models import SRLNeuralNetwork
+    torch.manual_seed(0)
+    enc = SRLNeuralNetwork(D, cuda=True, img_shape=(64, 64))
+    env = PixelStateVecEnv("KukaButtonGymEnv-v0", n, enc, seed=0, img_shape=(64, 64))
+    A = env.h.num_actions
+    mlp = BatchedMLP(D, A, H)
+    params = (0.1 * torch.randn((n, mlp.n_params), device=env.device)).contiguous()
+    sync = torch.cuda.synchronize
+
+    def fused():
+        with torch.cuda.stream(env.torch_stream):
+            env.rollout_mlp_policy(T, params, H, freeze_after_done=True)
+
+    def per_step():
+        with torch.cuda.stream(env.torch_stream):
+            done = torch.zeros(n, dtype=torch.bool, device=env.device)
+            obs = env._current
+            for k in range(1, T + 1):
+                acts = torch.argmax(mlp.forward(params, obs), dim=1)
+                actions = torch.where(done, torch.full_like(acts, -1), acts).to(torch.int32).contiguous()
+                obs, _, new_done = env.step(actions)
+                done = done | (new_done != 0)
+                if k % 16 == 0:
+                    bool(done.all())
+
+    with torch.cuda.stream(env.torch_stream):
+        env.reset()
+    for _ in range(a.warmup):
+        fused(); per_step()
+    t_f, t_p = [], []
+    for _ in range(a.reps):                                # alternating: both see the same neighbours on the machine
+        t_f.append(_timed(fused, sync)); t_p.append(_timed(per_step, sync))
+    f = _report("pixel_fused", n, T, t_f)
+    p = _report("pixel_per_step", n, T, t_p)
+    print(json.dumps({"leg": "pixel_ratio", "envs": n, "per_step_over_fused": p["ms_median"] / f["ms_median"]}), flush=True)
+    env.close()
+
+
+def act_alone_leg(a, n, D=200, H=100):
+    from srlhip.pixel_env import PixelStateVecEnv
+    from state_representation.models import SRLNeuralNetwork
+    enc = SRLNeuralNetwork(D, cuda=True, img_shape=(64, 64))
+    env = PixelStateVecEnv("KukaButtonGymEnv-v0", n, enc, seed=0, img_shape=(64, 64))
+    P = env.mlp_param_count(H)
+    params = (0.1 * torch.randn((n, P), device=env.device)).contiguous()
+    twin = torch.empty_like(params)
+    obs = torch.randn((n, D), device=env.device)
+    act = torch.zeros((n,), dtype=torch.int32, device=env.device)
+    K, nbytes = 20, params.numel() * 4
+    sync = torch.cuda.synchronize
+
+    def acts():
+        for _ in range(K):
+            env.h.policy_act(obs.data_ptr(), D, act.data_ptr(), params=params.data_ptr(), hidden=H)
+
+    def copies():
+        for _ in range(K):
+            env.h.copy_async(twin.data_ptr(), params.data_ptr(), nbytes)
+
+    for _ in range(a.warmup):
+        acts(); copies()
+    t_a, t_c = [], []
+    for _ in range(a.reps):
+        t_a.append(_timed(acts, sync) / K); t_c.append(_timed(copies, sync) / K)
+    ma, mc = statistics.median(t_a), statistics.median(t_c)
+    print(json.dumps({"leg": "policy_act_alone", "envs": n, "D": D, "H": H, "param_bytes": nbytes, "ms_median": ma, "ms_min": min(t_a),
+                      "ms_max": max(t_a), "param_GB_per_s": nbytes / (ma * 1e-3) / 1e9, "d2d_copy_ms_median": mc, "d2d_copy_ms_min": min(t_c),
+                      "d2d_copy_ms_max": max(t_c), "d2d_copy_read_GB_per_s": nbytes / (mc * 1e-3) / 1e9, "calls_per_timing": K,
+                      "reps": a.reps}), flush=True)
+    env.close()
 
 
 if __name__ == "__main__":

@@ -862,6 +862,34 @@ int srlhip_rollout_mlp_policy_sampled(srlhip_handle hh, int32_t T, const srlhip_
     return rollout_mlp_policy_entry(hh, "rollout_mlp_policy_sampled", true, T, pol, {obs_TN, reward_TN, done_TN, act_out_TN});
 }
 
+// srlhip_policy_act: the struct checks and messages of the fused rollouts (policy_call_begin, policy_args), none of their refusals
+// by env kind or observation mode — the call never looks at the env state
+int srlhip_policy_act(srlhip_handle hh, const srlhip_linear_policy *linear, const srlhip_mlp_policy *mlp, int32_t sample, const float *obs,
+                      int32_t obs_dim, const uint8_t *done_prev, uint8_t *frozen, void *act_out, double *score_out) {
+    if (!hh) return SRLHIP_EINVAL;
+    Handle *h = reinterpret_cast<Handle *>(hh);
+    const std::string name = "policy_act";
+    if (!linear == !mlp) return h->fail(SRLHIP_EINVAL, name + ": pass exactly one of the linear and the MLP policy");
+    if (linear && linear->struct_size != (int32_t)sizeof(srlhip_linear_policy)) return h->fail(SRLHIP_EINVAL, name + ": srlhip_linear_policy.struct_size mismatch (ABI)");
+    if (mlp && mlp->struct_size != (int32_t)sizeof(srlhip_mlp_policy)) return h->fail(SRLHIP_EINVAL, name + ": srlhip_mlp_policy.struct_size mismatch (ABI)");
+    int rc = policy_call_begin(h, name.c_str(), 1);
+    if (rc) return rc;
+    if (mlp && (mlp->hidden < 1 || mlp->hidden > 128)) return h->fail(SRLHIP_EINVAL, name + ": hidden must be in 1..128");
+    if (mlp && mlp->reserved != 0) return h->fail(SRLHIP_EINVAL, name + ": reserved must be 0");
+    if (obs_dim < 1 || obs_dim > 1024) return h->fail(SRLHIP_EINVAL, name + ": obs_dim must be in 1..1024");
+    if (sample && !mlp) return h->fail(SRLHIP_EINVAL, name + ": only an MLP policy's actions are sampled");
+    const PolicyArgs pa = mlp ? policy_args(*mlp, mlp->params, mlp->hidden) : policy_args(*linear, linear->weights, 0);
+    if (!pa.w) return h->fail(SRLHIP_EINVAL, name + ": null " + (mlp ? "params" : "weights"));
+    if (pa.normalize && (!pa.mean || !pa.std)) return h->fail(SRLHIP_EINVAL, name + ": normalize needs obs_mean and obs_std");
+    if (!obs || !act_out) return h->fail(SRLHIP_EINVAL, name + ": null obs or act_out");
+    if (pa.freeze && !frozen) return h->fail(SRLHIP_EINVAL, name + ": freeze_after_done needs the frozen plane");
+    const srlhip_config &c = h->cfg;
+    if (!c.io_device) return h->fail(SRLHIP_ENOTSUP, name + ": device-pointer handles only (io_device = 1)");
+    if (sample && !c.is_discrete) return h->fail(SRLHIP_ENOTSUP, name + ": only discrete actions are sampled (the reference never samples continuous ones)");
+    if ((rc = set_device(h))) return rc;               // (parks a resident kernel)
+    return policy_act_launch(h, pa, sample != 0, obs_dim, (int)policy_outputs(c), !is_mobile(c.env_kind), obs, done_prev, frozen, act_out, score_out);
+}
+
 int srlhip_get_state(srlhip_handle hh, int32_t field, void *out) {
     if (!hh || !out) return SRLHIP_EINVAL;
     Handle *h = reinterpret_cast<Handle *>(hh);

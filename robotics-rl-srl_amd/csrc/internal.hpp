@@ -84,6 +84,10 @@ int kuka_rollout_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, 
 int kuka_rollout_mlp_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
 int kuka_rollout_mlp_policy_sampled(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
 int kuka_policy_header(Handle *h, double *d_hdr, const PolicyArgs &pol);      // kuka_tree_policy.hip: the one header kernel's launch
+// policy_act.hip: srlhip_policy_act behind its argument checks — one launch on the handle's stream, no allocation, no synchronisation.
+// D = floats per row of obs, A = scores per env; none_nan: a frozen env's continuous row is NaNs (Kuka), not zeros (MobileRobot)
+int policy_act_launch(Handle *h, const PolicyArgs &pol, bool sample, int D, int A, bool none_nan, const float *d_obs, const uint8_t *d_done_prev,
+                      uint8_t *d_frozen, void *d_act, double *d_score);
 int mobile_field(Handle *h, int field, void **dptr, size_t *elem, int *count);
 int mobile_reset_rand_count(const srlhip_config &c);
 int mobile_persist_blocks(Handle *h, int *capacity, uint32_t *eighths);      // persistent stepping (mobile.hip)

@@ -13,7 +13,12 @@ continuous actions get zero rows instead: the reference's MobileRobotGymEnv.step
 --fused-rollout (off by default; the MobileRobot envs, KukaButton / KukaMovingButton / Kuka2Button; ground-truth observations,
 --deterministic or --continuous-actions, no frame stacking): one evaluation is reset + ONE srlhip_rollout_policy launch — the kernel applies each env's own M +- noise * delta to the
 observation it has just produced — and the returns come from the reward / done planes.  Softmax sampling (no --deterministic)
-stays on the per-step path above.  (CMA-ES, whose policy is a 100-unit MLP, has its own fused form: cma_es.py.)"""
+stays on the per-step path above.  (CMA-ES, whose policy is a 100-unit MLP, has its own fused form: cma_es.py.)
+
+A learned SRL model (--srl-model autoencoder, robotic_priors, ...: state_representation/registry.py, SRLType.SRL) runs on both paths:
+makeEnv then builds a PixelStateVecEnv (stepper, rasteriser, encoder on one stream) and the observation is the encoder's state vector.
+With --fused-rollout an evaluation is T x (srlhip_policy_act, step + rasteriser, encoder) enqueued by env.rollout_policy — the same
+action selection as a kernel of its own, no host read in the loop."""
 import pickle
 import time
 
@@ -62,7 +67,7 @@ class ARSModel(object):
         parser.add_argument('--deterministic', action='store_true', default=False,
                             help='do a deterministic approach for the actions on the output of the policy')
         parser.add_argument('--fused-rollout', action='store_true', default=False,
-                            help='evaluate each population with one fused policy rollout launch (ground-truth observations; needs '
+                            help='evaluate each population with one fused policy rollout launch (ground-truth observations or a learned SRL model; needs '
                                  '--deterministic or --continuous-actions and --num-stack 1; not KukaRandButton). The training '
                                  'callback then fires once per evaluation, not once per env step')
         return parser
@@ -82,10 +87,38 @@ class ARSModel(object):
                              "not fused (it stays on the per-step path)")
         if int(getattr(args, "num_stack", 1)) != 1:
             raise ValueError("--fused-rollout needs --num-stack 1: frame stacking is not fused")
-        if getattr(args, "srl_model", "ground_truth") != "ground_truth":
-            raise ValueError("--fused-rollout needs --srl-model ground_truth")
+        if getattr(args, "srl_model", "ground_truth") != "ground_truth" and not ARSModel.learned_srl(args):
+            raise ValueError("--fused-rollout needs --srl-model ground_truth or a learned SRL model (raw_pixels, joints and "
+                             "joints_position are not fused)")
         if ENV_CLASSES[args.env].ENV_KIND not in ARSModel.FUSED_EPISODE_LIMIT:
             raise ValueError("--fused-rollout: {} has no fused policy rollout".format(args.env))
+
+    @staticmethod
+    def learned_srl(args_or_name):
+        """the srl_model is a learned encoder on raw pixels (state_representation/registry.py: SRLType.SRL)"""
+        from state_representation.registry import registered_srl, SRLType
+        name = args_or_name if isinstance(args_or_name, str) else getattr(args_or_name, "srl_model", "ground_truth")
+        return registered_srl.get(name, (None,))[0] is SRLType.SRL
+
+    @staticmethod
+    def make_base_env(args, env_kwargs):
+        """The env under the wrappers: DeviceVecEnv for the env's own state observations; for a learned SRL model a
+        PixelStateVecEnv — stepper, rasteriser and encoder on one stream — with the encoder resolved as HipVecEnv does
+        (srl_model_path / state_dim / random-init) and the frame size from env_kwargs["img_shape"] or args.img_shape."""
+        device_id = getattr(args, "device_id", 0)
+        if not ARSModel.learned_srl(env_kwargs["srl_model"]):
+            return DeviceVecEnv(args.env, args.num_cpu, seed=args.seed, env_kwargs=env_kwargs, device_id=device_id)
+        from srlhip.pixel_env import PixelStateVecEnv
+        from srlhip.vec_env import RNG_MODES, default_rng_mode, resolve_encoder
+        kw = dict(env_kwargs)
+        for name in ("srl_model_path", "state_dim"):
+            if name not in kw and getattr(args, name, None) is not None:
+                kw[name] = getattr(args, name)
+        img_shape = tuple(kw.get("img_shape") or getattr(args, "img_shape", None) or (224, 224))[-2:]
+        n_channels = 6 if (kw.get("multi_view") or kw.get("fpv")) else 3
+        encoder = resolve_encoder(kw, img_shape, n_channels, torch.device("cuda", device_id))
+        return PixelStateVecEnv(args.env, args.num_cpu, encoder, seed=args.seed, img_shape=img_shape, device_id=device_id,
+                                rng_mode=RNG_MODES[default_rng_mode("device")], env_kwargs=kw)
 
     @staticmethod
     def returns_from_planes(reward, done):
@@ -139,8 +172,7 @@ class ARSModel(object):
             args.num_cpu = args.num_population * 2
         env_kwargs = dict(env_kwargs or {})
         env_kwargs.setdefault("srl_model", getattr(args, "srl_model", "ground_truth"))
-        envs = DeviceVecEnv(args.env, args.num_cpu, seed=args.seed, env_kwargs=env_kwargs,
-                            device_id=getattr(args, "device_id", 0))
+        envs = cls.make_base_env(args, env_kwargs)
         envs = DeviceVecFrameStack(envs, getattr(args, "num_stack", 1))
         if getattr(args, "srl_model", "ground_truth") != "raw_pixels" and getattr(args, "algo_type", "v2") == "v2":
             envs = DeviceVecNormalize(envs, norm_obs=True, norm_reward=False)

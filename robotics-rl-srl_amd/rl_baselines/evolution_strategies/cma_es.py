@@ -23,7 +23,11 @@ come from the reward / done planes.  Softmax sampling (no --deterministic) stays
 member's action drawn from the softmax of its scores (cma_es.py:228-232) — in the same one launch (srlhip_rollout_mlp_policy_sampled).
 The action draws then come from each env's own counter-based action stream (Philox stream 1, keyed by seed and env id), not from the
 `torch.multinomial` generator of the per-step path: the two paths sample the same distribution but not the same bits.  (The reference
-draws from the global np.random: no per-env stream could reproduce it either.)"""
+draws from the global np.random: no per-env stream could reproduce it either.)
+
+A learned SRL model (--srl-model autoencoder, ...; SRLType.SRL) runs on every path: makeEnv builds a PixelStateVecEnv under the same
+wrappers (ars.py: make_base_env), and --fused-rollout / --fused-sampling become T x (srlhip_policy_act, step + rasteriser, encoder)
+on the env's stream (env.rollout_mlp_policy).  raw_pixels — the reference's CNN-from-pixels policy — is still not part of it."""
 import math
 import pickle
 import time
@@ -152,7 +156,7 @@ class CMAESModel(object):
         parser.add_argument('--deterministic', action='store_true', default=False,
                             help='do a deterministic approach for the actions on the output of the policy')
         parser.add_argument('--fused-rollout', action='store_true', default=False,
-                            help='evaluate each generation with one fused MLP-policy rollout launch (ground-truth observations; needs '
+                            help='evaluate each generation with one fused MLP-policy rollout launch (ground-truth observations or a learned SRL model; needs '
                                  '--deterministic or --continuous-actions and --num-stack 1; not KukaRandButton). The training '
                                  'callback then fires once per generation, not once per env step')
         parser.add_argument('--fused-sampling', action='store_true', default=False,
@@ -231,7 +235,7 @@ class CMAESModel(object):
         if env_kwargs["srl_model"] == "raw_pixels":
             raise NotImplementedError("CMA-ES on the device stack evaluates state policies (MLP); the reference's CNN-from-pixels "
                                       "policy is not part of it")
-        envs = DeviceVecEnv(args.env, args.num_cpu, seed=args.seed, env_kwargs=env_kwargs, device_id=getattr(args, "device_id", 0))
+        envs = ARSModel.make_base_env(args, env_kwargs)
         envs = DeviceVecFrameStack(envs, getattr(args, "num_stack", 1))
         envs = DeviceVecNormalize(envs, norm_obs=True, norm_reward=False)
         if load_path_normalise is not None:

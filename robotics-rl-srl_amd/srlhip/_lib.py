@@ -37,7 +37,7 @@ _FIELD_SHAPES = {
 EXPORTS = [
     "srlhip_abi_version", "srlhip_default_config", "srlhip_create", "srlhip_destroy", "srlhip_obs_dim",
     "srlhip_obs_bytes", "srlhip_action_dim", "srlhip_num_actions", "srlhip_seed", "srlhip_reset",
-    "srlhip_reset_rand_count", "srlhip_step", "srlhip_step_async", "srlhip_step_wait", "srlhip_step_pending", "srlhip_set_persistent", "srlhip_rollout", "srlhip_rollout_policy", "srlhip_rollout_mlp_policy", "srlhip_rollout_mlp_policy_sampled", "srlhip_get_state", "srlhip_set_state",
+    "srlhip_reset_rand_count", "srlhip_step", "srlhip_step_async", "srlhip_step_wait", "srlhip_step_pending", "srlhip_set_persistent", "srlhip_rollout", "srlhip_rollout_policy", "srlhip_rollout_mlp_policy", "srlhip_rollout_mlp_policy_sampled", "srlhip_policy_act", "srlhip_get_state", "srlhip_set_state",
     "srlhip_device_ptr", "srlhip_render", "srlhip_episode_stats", "srlhip_episode_records", "srlhip_episode_stats_device", "srlhip_sync", "srlhip_copy_async", "srlhip_stream", "srlhip_timing_begin",
     "srlhip_timing_end", "srlhip_last_error", "srlhip_selftest_group_primitives", "srlhip_selftest_rng", "srlhip_kuka_kernel", "srlhip_kuka_default_model", "srlhip_set_kuka_model", "srlhip_kuka_tree_default_model", "srlhip_set_kuka_tree_model",
     "srlhip_graph_begin", "srlhip_graph_end", "srlhip_graph_launch", "srlhip_graph_destroy",
@@ -146,6 +146,7 @@ def load():
     lib.srlhip_rollout_policy.argtypes = [vp, i32, ctypes.POINTER(LinearPolicy), vp, vp, vp, vp]
     lib.srlhip_rollout_mlp_policy.argtypes = [vp, i32, ctypes.POINTER(MlpPolicy), vp, vp, vp, vp]
     lib.srlhip_rollout_mlp_policy_sampled.argtypes = [vp, i32, ctypes.POINTER(MlpPolicy), vp, vp, vp, vp]
+    lib.srlhip_policy_act.argtypes = [vp, ctypes.POINTER(LinearPolicy), ctypes.POINTER(MlpPolicy), i32, vp, i32, vp, vp, vp, vp]
     lib.srlhip_get_state.argtypes = [vp, i32, vp]
     lib.srlhip_set_state.argtypes = [vp, i32, vp]
     lib.srlhip_device_ptr.argtypes = [vp, i32, ctypes.POINTER(vp)]
@@ -398,6 +399,27 @@ class Handle(object):
             shape = ((self.num_envs,) if per_env else ()) + (self.mlp_param_count(int(hidden)),)
         return self._rollout_policy_call("srlhip_rollout_mlp_policy_sampled" if sample else "srlhip_rollout_mlp_policy", T, pol, "params", params, np.float32, shape,
                                          obs_mean, obs_std, want, out)
+
+    def policy_act(self, obs, obs_dim, act_out, weights=None, params=None, hidden=None, per_env=True, freeze_after_done=False,
+                   obs_mean=None, obs_std=None, clip_obs=10.0, done_prev=None, frozen=None, sample=False, score_out=None):
+        """srlhip_policy_act: one launch on the handle's stream that writes every env's action to `act_out` from the float32
+        [num_envs][obs_dim] plane `obs` (include/srlhip.h has the order-exact contract).  Device-pointer handles only; every array
+        argument is a raw device pointer.  `weights` (float64 [(num_envs)][obs_dim][A]): the linear policy; `params` + `hidden`
+        (float32 [(num_envs)][P]): the MLP, sample=True draws its discrete action from the softmax with the env's action stream.
+        done_prev: the done plane of the step that produced obs (None at the first step); frozen: uint8 [num_envs], needed with
+        freeze_after_done; score_out: optional float64 [num_envs][A] plane for the scores.  Only enqueues: capturable between graph_begin / graph_end."""
+        assert (weights is None) != (params is None), "pass weights (linear policy) or params and hidden (MLP)"
+        lin = mlp = None
+        if params is None:
+            pol = lin = self._policy_struct(LinearPolicy, per_env, freeze_after_done, obs_mean, obs_std, clip_obs)
+            pol.weights = weights
+        else:
+            pol = mlp = self._policy_struct(MlpPolicy, per_env, freeze_after_done, obs_mean, obs_std, clip_obs)
+            pol.hidden, pol.reserved, pol.params = int(hidden), 0, params
+        pol.obs_mean, pol.obs_std = obs_mean, obs_std
+        self._check(self._lib.srlhip_policy_act(self._h, None if lin is None else ctypes.byref(lin), None if mlp is None else ctypes.byref(mlp),
+                                                int(bool(sample)), _ptr(obs), int(obs_dim), _ptr(done_prev or None), _ptr(frozen or None),
+                                                _ptr(act_out), _ptr(score_out or None)), "srlhip_policy_act")
 
     def get_state(self, field):
         dtype, k = _FIELD_SHAPES[field]

@@ -1,12 +1,17 @@
 """raw_pixels -> SRL state pipeline on one device (BASELINE configs 4-5): the stepper and the tile
 rasteriser write uint8 images straight into a torch-owned HBM buffer (io_device = 1, zero host copies),
 and the SRL encoder runs one batched forward on it — instead of the reference's one-image-at-a-time
-encoder server behind multiprocessing queues (rl_baselines/utils.py:162-191)."""
+encoder server behind multiprocessing queues (rl_baselines/utils.py:162-191).
+
+rollout_policy / rollout_mlp_policy run a policy on those states without leaving the device: T x (srlhip_policy_act -> step +
+rasteriser -> encoder) enqueued on the handle's stream, DeviceVecEnv's signatures and result dict, so that DeviceVecFrameStack(.., 1),
+DeviceVecNormalize and the ARS / CMA-ES learners sit on this env as they do on DeviceVecEnv."""
 import numpy as np
 import torch
 
 from . import _lib
 from .envs import ENV_CLASSES
+from .gym_compat import Box, Discrete
 
 
 class PixelStateVecEnv(object):
@@ -18,21 +23,35 @@ class PixelStateVecEnv(object):
         cfg.random_target, cfg.multi_view = int(kw.get("random_target", False)), int(bool(kw.get("multi_view", False)) or bool(kw.get("fpv", False)))
         cfg.obs_mode, cfg.img_h, cfg.img_w = _lib.OBS_RAW_PIXELS, img_shape[0], img_shape[1]
         cfg.rng_mode, cfg.auto_reset, cfg.io_device = rng_mode, 1, 1
+        for name in ("is_discrete", "shape_reward", "force_down", "action_repeat"):      # as DeviceVecEnv; absent: the env's defaults
+            if name in kw:
+                setattr(cfg, name, int(kw[name]))
+        if "max_distance" in kw:
+            cfg.max_distance = float(kw["max_distance"])
         self.h = _lib.Handle(cfg)
+        self.cfg, self.env_id = cfg, env_id
         self.encoder, self.num_envs = encoder, num_envs
         self.device = torch.device("cuda", device_id)
         ch = 6 if cfg.multi_view else 3
         self.images = torch.zeros((num_envs, img_shape[0], img_shape[1], ch), dtype=torch.uint8, device=self.device)
         self.rewards = torch.zeros((num_envs,), dtype=torch.float32, device=self.device)
         self.dones = torch.zeros((num_envs,), dtype=torch.uint8, device=self.device)
-        self.actions = torch.zeros((num_envs,), dtype=torch.int32, device=self.device)
+        if cfg.is_discrete:
+            self.actions = torch.zeros((num_envs,), dtype=torch.int32, device=self.device)
+            self.action_space = Discrete(self.h.num_actions)
+        else:
+            self.actions = torch.zeros((num_envs, self.h.action_dim), dtype=torch.float32, device=self.device)
+            self.action_space = Box(low=-1, high=1, shape=(self.h.action_dim,), dtype=np.float32)
+        self.state_dim = int(encoder.state_dim)
+        self.observation_space = Box(low=-np.inf, high=np.inf, shape=(self.state_dim,), dtype=np.float32)
         self.states = torch.zeros((num_envs, encoder.state_dim), dtype=torch.float32, device=self.device)
+        self._current = None              # the float32 states the env holds now (reset / step: self.states; a rollout: its last row)
         # use_graph: replay stepper + rasteriser + encoder of a step from a HIP graph (srlhip_graph_*), keyed by the action
         # source.  Off by default: at 4096 envs the step is GPU-bound and the host already runs ahead of it (697 us eager
         # vs 702 us replayed, profiles/pixel_step_microbench.py); it pays when the host thread is the bottleneck.
         self.use_graph, self._graphs, self._warm = bool(use_graph), {}, {}
         self._stream_ptr = self.h.stream()
-        self._stream = torch.cuda.ExternalStream(self._stream_ptr, device=self.device)
+        self._stream = self.torch_stream = torch.cuda.ExternalStream(self._stream_ptr, device=self.device)
 
     def _encode(self):
         if self.encoder.hip is not None:
@@ -40,9 +59,12 @@ class PixelStateVecEnv(object):
             # order torch's current stream behind it so the caller can consume states / rewards / dones as usual
             states = self.encoder.getStates(self.images, stream=self._stream_ptr, out=self.states)
             torch.cuda.current_stream(self.device).wait_stream(self._stream)
+            self._current = states
             return states
         self.h.sync()                                  # images were written on the stepper's stream
-        return self.encoder.getStates(self.images)
+        states = self.encoder.getStates(self.images)
+        self._current = states
+        return states
 
     def reset(self):
         self._stream.wait_stream(torch.cuda.current_stream(self.device))
@@ -61,6 +83,7 @@ class PixelStateVecEnv(object):
             # stepper + rasteriser + encoder of one VecEnv step replayed from a HIP graph: one launch instead of three
             self.h.graph_launch(g)
             torch.cuda.current_stream(self.device).wait_stream(self._stream)
+            self._current = self.states
             return self.states, self.rewards, self.dones
         # the first call runs eagerly (lazy allocations); at most a handful of distinct action buffers get their own graph
         capture = fused and self.use_graph and self._warm.get(key, 0) >= 1 and len(self._graphs) < 8
@@ -75,9 +98,78 @@ class PixelStateVecEnv(object):
             self._graphs[key] = self.h.graph_end()
             self.h.graph_launch(self._graphs[key])                              # the captured step has not run yet
             torch.cuda.current_stream(self.device).wait_stream(self._stream)
+            self._current = self.states
             return self.states, self.rewards, self.dones
         self._warm[key] = self._warm.get(key, 0) + 1
         return self._encode(), self.rewards, self.dones
+
+    # ---- policy rollouts on the learned states: T x (srlhip_policy_act -> step + rasteriser -> encoder), enqueue-only ----------------
+    def _rollout(self, T, policy, sample, per_env, freeze_after_done, obs_mean, obs_std, clip_obs):
+        """`policy`: the keyword arguments of Handle.policy_act that name the policy (raw device pointers).  The loop starts from the
+        states the env holds (after reset(), step() or an earlier rollout) and every kernel writes straight into row t of the new
+        [T][N]... planes: the action kernel reads row t - 1 of the state and done planes and writes row t of the action plane, the
+        stepper reads that row and writes row t of reward / done and the frame buffer, the encoder writes row t of the state plane.
+        All of it on the handle's stream; no host read, and no synchronisation when the caller is on that stream."""
+        assert self._current is not None, "reset() the env first"
+        n, dev, D = self.num_envs, self.device, self.state_dim
+        assert (obs_mean is None) == (obs_std is None), "obs_mean and obs_std come together"
+        for x in (obs_mean, obs_std):
+            assert x is None or (x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() and tuple(x.shape) == (D,))
+        ordered = torch.cuda.current_stream(dev).cuda_stream == self.torch_stream.cuda_stream
+        if not ordered:
+            torch.cuda.current_stream(dev).synchronize()
+        fused = self.encoder.hip is not None
+        with torch.cuda.stream(self.torch_stream):         # the planes are allocated (and later freed) on the stream that fills them
+            out = {"obs": torch.empty((T, n, D), dtype=torch.float32, device=dev),
+                   "reward": torch.empty((T, n), dtype=torch.float32, device=dev),
+                   "done": torch.empty((T, n), dtype=torch.uint8, device=dev),
+                   "actions": torch.empty((T,) + tuple(self.actions.shape), dtype=self.actions.dtype, device=dev)}
+            frozen = torch.zeros((n,), dtype=torch.uint8, device=dev)
+            prev = self._current if self._current.dtype == torch.float32 else self._current.to(torch.float32)
+            kw = dict(policy, per_env=per_env, freeze_after_done=freeze_after_done, clip_obs=clip_obs, sample=sample,
+                      obs_mean=None if obs_mean is None else obs_mean.data_ptr(), obs_std=None if obs_std is None else obs_std.data_ptr(),
+                      frozen=frozen.data_ptr())
+            images = self.images.data_ptr()
+            for t in range(T):
+                act_t, obs_t = out["actions"][t], out["obs"][t]
+                self.h.policy_act(prev.data_ptr(), D, act_t.data_ptr(), done_prev=out["done"][t - 1].data_ptr() if t else None, **kw)
+                self.h.step(act_t.data_ptr(), out=(images, out["reward"][t].data_ptr(), out["done"][t].data_ptr()))
+                if fused:
+                    self.encoder.getStates(self.images, stream=self._stream_ptr, out=obs_t)
+                else:                                      # no HIP backend (PCA, other model types): the torch forward, ordered on this stream
+                    obs_t.copy_(self.encoder.getStates(self.images))
+                prev = obs_t
+            self._current = prev
+        if not ordered:
+            self.h.sync()
+        return out
+
+    def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0):
+        """DeviceVecEnv.rollout_policy on the learned states: T steps whose actions the linear policy `weights` (float64 CUDA tensor
+        [N][state_dim][A], or [state_dim][A] with per_env=False) picks on the device from the state the encoder has just produced
+        (srlhip_policy_act).  Returns {"obs", "reward", "done", "actions"}: new [T][N]... tensors; "obs" holds the float32 states the
+        policy saw NEXT (row t: the state after step t).  The env's own states / rewards / dones tensors are left as they were."""
+        A = self.h.num_actions if self.cfg.is_discrete else self.h.action_dim
+        shape = ((self.num_envs,) if per_env else ()) + (self.state_dim, A)
+        assert weights.is_cuda and weights.dtype == torch.float64 and weights.is_contiguous() and tuple(weights.shape) == shape, (tuple(weights.shape), shape)
+        return self._rollout(T, {"weights": weights.data_ptr()}, False, per_env, freeze_after_done, obs_mean, obs_std, clip_obs)
+
+    def mlp_param_count(self, hidden):
+        A = self.h.num_actions if self.cfg.is_discrete else self.h.action_dim
+        return hidden * self.state_dim + hidden + A * hidden + A
+
+    def rollout_mlp_policy(self, T, params, hidden, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0,
+                           sample=False):
+        """DeviceVecEnv.rollout_mlp_policy on the learned states.  `params`: float32 CUDA tensor [N][P] (or [P]), P =
+        mlp_param_count(hidden) with D = state_dim; sample=True (discrete actions): the action drawn from the softmax of the scores
+        with each env's own action stream, one block per env and step."""
+        shape = ((self.num_envs,) if per_env else ()) + (self.mlp_param_count(int(hidden)),)
+        assert params.is_cuda and params.dtype == torch.float32 and params.is_contiguous() and tuple(params.shape) == shape, (tuple(params.shape), shape)
+        return self._rollout(T, {"params": params.data_ptr(), "hidden": int(hidden)}, bool(sample), per_env, freeze_after_done,
+                             obs_mean, obs_std, clip_obs)
+
+    def episode_stats(self):
+        return self.h.episode_stats()
 
     def close(self):
         for g in self._graphs.values():

@@ -47,6 +47,14 @@ def default_rng_mode(surface="reference"):
     return mode
 
 
+def resolve_encoder(kw, img_shape, n_channels, device):
+    """The learned SRL model of the env kwargs on `device`: kw["srl_model_path"] loaded (its exp_config.json gives the state
+    dimension), or without a path a random-init network of kw["state_dim"].  One definition for HipVecEnv and the device learners."""
+    from state_representation.models import loadSRLModel
+    return loadSRLModel(kw.get("srl_model_path"), cuda=True, state_dim=kw.get("state_dim"), img_shape=tuple(img_shape),
+                        n_channels=n_channels, device=device)
+
+
 def _env_kind(env_id):
     if env_id not in ENV_CLASSES:
         raise KeyError("{} is not stepped by libsrlhip (supported: {})".format(env_id, sorted(ENV_CLASSES)))
@@ -231,7 +239,6 @@ class HipVecEnv(object):
         replicated onto the others), or a list with one model per shard."""
         import torch
         cfg = self.cfg
-        from state_representation.models import loadSRLModel
         if isinstance(encoder, (list, tuple)):
             if len(encoder) != len(self._shards):
                 raise ValueError("encoder list: one model per shard ({}) expected".format(len(self._shards)))
@@ -243,8 +250,7 @@ class HipVecEnv(object):
             dev = torch.device("cuda", sh.device_id)
             if sh.device_id not in by_device:
                 if encoder is None and not by_device:
-                    by_device[sh.device_id] = loadSRLModel(kw.get("srl_model_path"), cuda=True, state_dim=kw.get("state_dim"),
-                                                           img_shape=(cfg.img_h, cfg.img_w), n_channels=6 if cfg.multi_view else 3, device=dev)
+                    by_device[sh.device_id] = resolve_encoder(kw, (cfg.img_h, cfg.img_w), 6 if cfg.multi_view else 3, dev)
                 else:
                     src = encoder if encoder is not None else next(iter(by_device.values()))
                     src_dev = torch.device(getattr(src, "device", dev))
@@ -475,7 +481,8 @@ class HipVecEnv(object):
         thread per shard: the foreign calls release the GIL) -> the shards' [T][n] planes as one dict of [T][N] planes, global
         env-id order."""
         if self._enc is not None:
-            raise NotImplementedError("fused rollouts with a learned SRL encoder: use srlhip.pixel_env.PixelStateVecEnv")
+            raise NotImplementedError("fused rollouts with a learned SRL encoder: use srlhip.pixel_env.PixelStateVecEnv "
+                                      "(rollout_policy / rollout_mlp_policy)")
         if self._pending:
             self.step_wait()
         if len(self._shards) == 1:
