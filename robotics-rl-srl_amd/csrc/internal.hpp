@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/srlhip.h"
@@ -211,6 +212,19 @@ struct Handle {
         if (e__ != hipSuccess)                                                                     \
             return (h)->fail(SRLHIP_EHIP, std::string(#expr ": ") + hipGetErrorString(e__));       \
     } while (0)
+
+// Run-time configuration -> template arguments: f is a generic lambda that receives the matching value as a std::integral_constant
+// and launches (or names) the instantiation it selects; only the values listed exist in the library.  Returns whether an arm matched
+// — all the way down when f itself returns the bool of a nested dispatch.  A launcher answers false with SRLHIP_ENOTSUP: a value
+// without an arm must not pass for a launch (hipGetLastError() after launching nothing reports success).
+template <int V> using Const = std::integral_constant<int, V>;
+template <class F, class C>
+bool dispatch_arm_matched(F &f, C c) {
+    if constexpr (std::is_void_v<decltype(f(c))>) { f(c); return true; }
+    else return f(c);
+}
+template <int... Vs, class F>
+bool dispatch_int(int v, F &&f) { return (((v == Vs) && dispatch_arm_matched(f, Const<Vs>{})) || ...); }
 
 // a grow-only device buffer: at least `bytes` at *buf afterwards (contents are not kept; the caller orders the free against the stream)
 inline int ensure(Handle *h, void **buf, size_t *cap, size_t bytes) {

@@ -210,6 +210,31 @@ int allow_lds(Handle *h, K kernel) {
     return 0;
 }
 
+// NB of the lane-per-env kernels: Kuka2ButtonGymEnv, or one button
+template <class F>
+void dispatch_buttons(const Handle *h, F &&f) { if (h->cfg.env_kind == SRLHIP_ENV_KUKA_2BUTTON) f(Const<2>{}); else f(Const<1>{}); }
+
+// every reset / rollout instantiation of one button count
+template <int NB, int... MODES>
+int allow_lds_all(Handle *h) {
+    int rc = 0;
+    if ((... || (rc = allow_lds(h, kuka_reset_k<MODES, NB>)))) return rc;
+    (void)(... || (rc = allow_lds(h, kuka_rollout_k<MODES, NB>)));
+    return rc;
+}
+
+// kuka_rollout_k<MODE, NB>, NB from the env kind
+template <int MODE>
+int lane_rollout_launch(Handle *h, const KukaParams &p, dim3 grid, dim3 block, size_t lds_bytes, int T, const void *d_actions, const double *d_noise, float *obs,
+                        float *d_rew, uint8_t *d_done, void *d_act_out) {
+    dispatch_buttons(h, [&](auto nb) {
+        hipLaunchKernelGGL((kuka_rollout_k<MODE, decltype(nb)::value>), grid, block, lds_bytes, h->stream, p, *h->kuka, h->rng, h->stats, T, d_actions, d_noise, obs,
+                           d_rew, d_done, d_act_out);
+    });
+    SRL_HIP_CHECK(h, hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 int kuka_reset_rand_count(const srlhip_config &c) {
@@ -249,13 +274,8 @@ int kuka_alloc(Handle *h) {
         return kuka_tree_settle(h, params_of(h));
     }
     if ((rc = allow_lds(h, kuka_settle_k)) || (rc = allow_lds(h, kuka_starts_k))) return rc;
-#define SRL_ALLOW(NB)                                                                                                     \
-    if ((rc = allow_lds(h, kuka_reset_k<SRLHIP_RNG_HOST, NB>)) || (rc = allow_lds(h, kuka_reset_k<SRLHIP_RNG_PHILOX, NB>)) ||     \
-        (rc = allow_lds(h, kuka_reset_k<SRLHIP_RNG_MT19937, NB>)) || (rc = allow_lds(h, kuka_rollout_k<SRLHIP_RNG_HOST, NB>)) ||  \
-        (rc = allow_lds(h, kuka_rollout_k<SRLHIP_RNG_PHILOX, NB>)) || (rc = allow_lds(h, kuka_rollout_k<SRLHIP_RNG_MT19937, NB>))) \
-        return rc;
-    if (h->cfg.env_kind == SRLHIP_ENV_KUKA_2BUTTON) { SRL_ALLOW(2) } else { SRL_ALLOW(1) }
-#undef SRL_ALLOW
+    dispatch_buttons(h, [&](auto nb) { rc = allow_lds_all<decltype(nb)::value, SRLHIP_RNG_HOST, SRLHIP_RNG_PHILOX, SRLHIP_RNG_MT19937>(h); });
+    if (rc) return rc;
     KukaParams p = params_of(h);
     hipLaunchKernelGGL(kuka_settle_k, dim3(1), dim3(kWave), kLdsBytes, h->stream, p, *s);
     SRL_HIP_CHECK(h, hipGetLastError());
@@ -273,30 +293,16 @@ int kuka_reset(Handle *h, const uint8_t *d_mask, const double *d_host_rand, void
     dim3 grid((h->n + kWave - 1) / kWave), block(kWave);
     const int stride = kuka_reset_rand_count(h->cfg);
     float *obs = static_cast<float *>(d_obs);
-    if (h->kuka->full) {
-        if (h->cfg.rng_mode == SRLHIP_RNG_HOST && !d_host_rand) return h->fail(SRLHIP_EINVAL, "reset: RNG_HOST needs host_rand");
-        return kuka_tree_reset(h, p, d_mask, d_host_rand, stride, obs);
-    }
-    if (h->kuka->custom_model) {
-        if (h->cfg.rng_mode == SRLHIP_RNG_HOST && !d_host_rand) return h->fail(SRLHIP_EINVAL, "reset: RNG_HOST needs host_rand");
-        return kuka_group_reset_table(h, p, d_mask, d_host_rand, stride, obs);
-    }
-    const bool two = h->cfg.env_kind == SRLHIP_ENV_KUKA_2BUTTON;
-#define SRL_RESET(MODE)                                                                                                          \
-    if (two) hipLaunchKernelGGL((kuka_reset_k<MODE, 2>), grid, block, kLdsBytes, h->stream, p, *h->kuka, h->rng, h->stats, d_mask, d_host_rand, stride, obs); \
-    else hipLaunchKernelGGL((kuka_reset_k<MODE, 1>), grid, block, kLdsBytes, h->stream, p, *h->kuka, h->rng, h->stats, d_mask, d_host_rand, stride, obs);
-    switch (h->cfg.rng_mode) {
-        case SRLHIP_RNG_HOST:
-            if (!d_host_rand) return h->fail(SRLHIP_EINVAL, "reset: RNG_HOST needs host_rand");
-            SRL_RESET(SRLHIP_RNG_HOST)
-            break;
-        case SRLHIP_RNG_PHILOX:
-            SRL_RESET(SRLHIP_RNG_PHILOX)
-            break;
-        default:
-            SRL_RESET(SRLHIP_RNG_MT19937)
-    }
-#undef SRL_RESET
+    if (h->cfg.rng_mode == SRLHIP_RNG_HOST && !d_host_rand) return h->fail(SRLHIP_EINVAL, "reset: RNG_HOST needs host_rand");
+    if (h->kuka->full) return kuka_tree_reset(h, p, d_mask, d_host_rand, stride, obs);
+    if (h->kuka->custom_model) return kuka_group_reset_table(h, p, d_mask, d_host_rand, stride, obs);
+    const bool hit = dispatch_int<SRLHIP_RNG_HOST, SRLHIP_RNG_PHILOX, SRLHIP_RNG_MT19937>(h->cfg.rng_mode, [&](auto mode) {
+        dispatch_buttons(h, [&](auto nb) {
+            hipLaunchKernelGGL((kuka_reset_k<decltype(mode)::value, decltype(nb)::value>), grid, block, kLdsBytes, h->stream, p, *h->kuka, h->rng, h->stats, d_mask,
+                               d_host_rand, stride, obs);
+        });
+    });
+    if (!hit) return h->fail(SRLHIP_ENOTSUP, "reset: no instantiation for this RNG mode");
     SRL_HIP_CHECK(h, hipGetLastError());
     return 0;
 }
@@ -361,23 +367,11 @@ int kuka_rollout(Handle *h, int T, const void *d_actions, void *d_obs, float *d_
     static const int forced_lds_kb = [] { const char *v = getenv("SRLHIP_KUKA_LDS_KB"); return v ? atoi(v) : 0; }();
     const size_t lds_bytes = forced_lds_kb > 0 && (size_t)forced_lds_kb * 1024 >= kLdsBytes && forced_lds_kb <= 160 ? (size_t)forced_lds_kb * 1024 : kLdsBytes;
     float *obs = static_cast<float *>(d_obs);
-    const bool two = h->cfg.env_kind == SRLHIP_ENV_KUKA_2BUTTON;
-#define SRL_ROLLOUT(MODE)                                                                                                        \
-    if (two) hipLaunchKernelGGL((kuka_rollout_k<MODE, 2>), grid, block, lds_bytes, h->stream, p, *h->kuka, h->rng, h->stats, T, d_actions, (const double *)nullptr, obs, d_rew, d_done, d_act_out); \
-    else hipLaunchKernelGGL((kuka_rollout_k<MODE, 1>), grid, block, lds_bytes, h->stream, p, *h->kuka, h->rng, h->stats, T, d_actions, (const double *)nullptr, obs, d_rew, d_done, d_act_out);
-    switch (h->cfg.rng_mode) {
-        case SRLHIP_RNG_PHILOX:
-            SRL_ROLLOUT(SRLHIP_RNG_PHILOX)
-            break;
-        case SRLHIP_RNG_MT19937:
-            SRL_ROLLOUT(SRLHIP_RNG_MT19937)
-            break;
-        default:
-            return h->fail(SRLHIP_EINVAL, "rollout: needs a device RNG mode (PHILOX or MT19937)");
-    }
-#undef SRL_ROLLOUT
-    SRL_HIP_CHECK(h, hipGetLastError());
-    return 0;
+    int rc = 0;
+    const bool hit = dispatch_int<SRLHIP_RNG_PHILOX, SRLHIP_RNG_MT19937>(h->cfg.rng_mode, [&](auto mode) {
+        rc = lane_rollout_launch<decltype(mode)::value>(h, p, grid, block, lds_bytes, T, d_actions, nullptr, obs, d_rew, d_done, d_act_out);
+    });
+    return hit ? rc : h->fail(SRLHIP_EINVAL, "rollout: needs a device RNG mode (PHILOX or MT19937)");
 }
 
 int kuka_step(Handle *h, const void *d_actions, const double *d_noise, void *d_obs, float *d_rew, uint8_t *d_done) {
@@ -385,14 +379,7 @@ int kuka_step(Handle *h, const void *d_actions, const double *d_noise, void *d_o
     KukaParams p = params_of(h);
     if (use_group_kernel(h)) return kuka_group_launch(h, p, 1, d_actions, d_noise, static_cast<float *>(d_obs), d_rew, d_done, nullptr);
     dim3 grid((h->n + kWave - 1) / kWave), block(kWave);
-    if (h->cfg.env_kind == SRLHIP_ENV_KUKA_2BUTTON)
-        hipLaunchKernelGGL((kuka_rollout_k<SRLHIP_RNG_HOST, 2>), grid, block, kLdsBytes, h->stream, p, *h->kuka, h->rng, h->stats, 1,
-                           d_actions, d_noise, static_cast<float *>(d_obs), d_rew, d_done, (void *)nullptr);
-    else
-        hipLaunchKernelGGL((kuka_rollout_k<SRLHIP_RNG_HOST, 1>), grid, block, kLdsBytes, h->stream, p, *h->kuka, h->rng, h->stats, 1,
-                           d_actions, d_noise, static_cast<float *>(d_obs), d_rew, d_done, (void *)nullptr);
-    SRL_HIP_CHECK(h, hipGetLastError());
-    return 0;
+    return lane_rollout_launch<SRLHIP_RNG_HOST>(h, p, grid, block, kLdsBytes, 1, d_actions, d_noise, static_cast<float *>(d_obs), d_rew, d_done, nullptr);
 }
 
 int kuka_persist_blocks(Handle *h, int *capacity) { if (capacity) *capacity = 0; return h->kuka && h->kuka->full ? kuka_tree_persist_blocks(h, capacity) : 0; }

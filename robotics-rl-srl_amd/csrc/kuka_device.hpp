@@ -93,6 +93,13 @@ inline KukaParams params_of(const Handle *h) {
 }
 
 
+// RNG mode -> template argument for the Kuka launches.  The compiler lays kernels out in the order in which it instantiates them, and the
+// arms of a dispatch_int are instantiated last to first: the lists are written so that the code objects keep the layout they have
+// always had (rollouts PHILOX, MT19937, HOST; resets HOST, PHILOX, MT19937) and stay comparable byte for byte across host-only changes.
+template <class F> bool dispatch_rollout_rng(int mode, F &&f) { return dispatch_int<SRLHIP_RNG_HOST, SRLHIP_RNG_MT19937, SRLHIP_RNG_PHILOX>(mode, f); }
+template <class F> bool dispatch_rollout_device_rng(int mode, F &&f) { return dispatch_int<SRLHIP_RNG_MT19937, SRLHIP_RNG_PHILOX>(mode, f); }
+template <class F> bool dispatch_reset_rng(int mode, F &&f) { return dispatch_int<SRLHIP_RNG_MT19937, SRLHIP_RNG_PHILOX, SRLHIP_RNG_HOST>(mode, f); }
+
 // lane-group kernels: launchers (kuka_group.hip: baked model; kuka_group_cm.hip: runtime model table)
 constexpr int kGroupBlock = 64;
 constexpr int kGroupEnvs = kGroupBlock / 16;
@@ -102,7 +109,8 @@ int kuka_group_launch_table(Handle *h, const KukaParams &p, int T, const void *d
                             uint8_t *d_done, void *d_act_out);
 int kuka_group_reset_table(Handle *h, const KukaParams &p, const uint8_t *d_mask, const double *d_host_rand, int stride, float *obs);
 int kuka_group_settle_table(Handle *h, const KukaParams &p);
-// full-model lane-group kernels (kuka_tree.hip)
+// full-model lane-group kernels (kuka_tree.hip); s: what kuka_tree_launch selected (kuka_tree_select.hpp)
+struct TreeSelect;
 // persistent stepping: 1 when this handle's configuration has a persistent instantiation and its grid is co-resident on the device
 int kuka_tree_persist_blocks(Handle *h, int *capacity);       // > 0: the number of real workgroups; 0: not supported.  capacity: workgroups of that kernel the device holds at once
 int kuka_tree_persist_launch(Handle *h, const KukaParams &p, const void *d_actions, float *obs, float *d_rew, uint8_t *d_done, const PersistArgs &pa);
@@ -110,10 +118,10 @@ int kuka_tree_launch(Handle *h, const KukaParams &p, int T, const void *d_action
                      uint8_t *d_done, void *d_act_out);
 int kuka_tree_reset(Handle *h, const KukaParams &p, const uint8_t *d_mask, const double *d_host_rand, int stride, float *obs);
 // two wavefronts per SIMD (default from 65536 envs, SRLHIP_KUKA_OCC forces either): kuka_tree_occ.hip
-int kuka_tree_occ_launch(Handle *h, const KukaParams &p, int T, const void *d_actions, const double *d_noise, float *obs, float *d_rew,
+int kuka_tree_occ_launch(Handle *h, const KukaParams &p, const TreeSelect &s, int T, const void *d_actions, const double *d_noise, float *obs, float *d_rew,
                          uint8_t *d_done, void *d_act_out);
 // KukaRandButtonGymEnv (free bodies): kuka_tree_rb.hip
-int kuka_tree_rb_launch(Handle *h, const KukaParams &p, int T, const void *d_actions, const double *d_noise, float *obs, float *d_rew,
+int kuka_tree_rb_launch(Handle *h, const KukaParams &p, const TreeSelect &s, int T, const void *d_actions, const double *d_noise, float *obs, float *d_rew,
                         uint8_t *d_done, void *d_act_out);
 int kuka_tree_rb_reset(Handle *h, const KukaParams &p, const uint8_t *d_mask, const double *d_host_rand, int stride, float *obs);
 int kuka_tree_settle(Handle *h, const KukaParams &p);     // settled state + start-state table of the installed tree model

@@ -4,6 +4,9 @@
 namespace srl {
 using namespace kuka;
 
-SRL_GROUP_LAUNCHER(kuka_group_launch_baked, false)
+int kuka_group_launch_baked(Handle *h, const KukaParams &p, int T, const void *d_actions, const double *d_noise, float *obs, float *d_rew,
+                            uint8_t *d_done, void *d_act_out) {
+    return group_rollout_launch<false>(h, p, T, d_actions, d_noise, obs, d_rew, d_done, d_act_out);
+}
 
 }  // namespace srl

@@ -126,20 +126,20 @@ __global__ void __launch_bounds__(64) kuka_group_probe_k(const double *q7, doubl
 
 }  // namespace
 
-SRL_GROUP_LAUNCHER(kuka_group_launch_table, true)
+int kuka_group_launch_table(Handle *h, const KukaParams &p, int T, const void *d_actions, const double *d_noise, float *obs, float *d_rew,
+                            uint8_t *d_done, void *d_act_out) {
+    return group_rollout_launch<true>(h, p, T, d_actions, d_noise, obs, d_rew, d_done, d_act_out);
+}
 
 int kuka_group_reset_table(Handle *h, const KukaParams &p, const uint8_t *d_mask, const double *d_host_rand, int stride, float *obs) {
     dim3 ggrid((h->n + kGroupEnvs - 1) / kGroupEnvs), gblock(kGroupBlock);
-    const bool joints = !h->cfg.is_discrete && h->cfg.action_joints;
-#define SRL_GRESET(MODE)                                                                                                                       \
-    if (joints) hipLaunchKernelGGL((kuka_group_reset_k<MODE, true>), ggrid, gblock, 0, h->stream, p, *h->kuka, h->rng, h->stats, d_mask, d_host_rand, stride, obs); \
-    else hipLaunchKernelGGL((kuka_group_reset_k<MODE, false>), ggrid, gblock, 0, h->stream, p, *h->kuka, h->rng, h->stats, d_mask, d_host_rand, stride, obs)
-    switch (h->cfg.rng_mode) {
-        case SRLHIP_RNG_HOST: SRL_GRESET(SRLHIP_RNG_HOST); break;
-        case SRLHIP_RNG_PHILOX: SRL_GRESET(SRLHIP_RNG_PHILOX); break;
-        default: SRL_GRESET(SRLHIP_RNG_MT19937);
-    }
-#undef SRL_GRESET
+    const bool hit = dispatch_reset_rng(h->cfg.rng_mode, [&](auto mode) {
+        return dispatch_int<0, 1>(!h->cfg.is_discrete && h->cfg.action_joints ? 1 : 0, [&](auto joints) {
+            hipLaunchKernelGGL((kuka_group_reset_k<decltype(mode)::value, decltype(joints)::value != 0>), ggrid, gblock, 0, h->stream, p, *h->kuka, h->rng,
+                               h->stats, d_mask, d_host_rand, stride, obs);
+        });
+    });
+    if (!hit) return h->fail(SRLHIP_ENOTSUP, "reset: no instantiation for this RNG mode");
     SRL_HIP_CHECK(h, hipGetLastError());
     return 0;
 }

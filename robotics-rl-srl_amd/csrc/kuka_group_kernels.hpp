@@ -136,27 +136,23 @@ kuka_group_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, in
 }
 
 
+// one launcher for both translation units (kuka_group_launch_baked / kuka_group_launch_table): CM is the unit's compile-time model switch
+template <bool CM>
+int group_rollout_launch(Handle *h, const KukaParams &p, int T, const void *d_actions, const double *d_noise, float *obs, float *d_rew, uint8_t *d_done,
+                         void *d_act_out) {
+    dim3 grid((h->n + kGroupEnvs - 1) / kGroupEnvs), block(kGroupBlock);
+    const bool hit = dispatch_rollout_rng(h->cfg.rng_mode, [&](auto mode) {
+        return dispatch_int<0, 1>(!h->cfg.is_discrete && h->cfg.action_joints ? 1 : 0, [&](auto joints) {
+            return dispatch_int<0, 1>(d_actions ? 1 : 0, [&](auto given) {
+                hipLaunchKernelGGL((kuka_group_rollout_k<decltype(mode)::value, decltype(joints)::value != 0, decltype(given)::value != 0, CM>), grid, block, 0,
+                                   h->stream, p, *h->kuka, h->rng, h->stats, T, d_actions, d_noise, obs, d_rew, d_done, d_act_out);
+            });
+        });
+    });
+    if (!hit) return h->fail(SRLHIP_ENOTSUP, "rollout: no instantiation for this RNG mode");
+    SRL_HIP_CHECK(h, hipGetLastError());
+    return 0;
+}
+
 }  // namespace
-
-// one launcher body for both translation units: CM is the unit's compile-time model switch
-#define SRL_GROUP_LAUNCHER(NAME, CM)                                                                                                 \
-    int NAME(Handle *h, const KukaParams &p, int T, const void *d_actions, const double *d_noise, float *obs, float *d_rew,         \
-             uint8_t *d_done, void *d_act_out) {                                                                                     \
-        dim3 grid((h->n + kGroupEnvs - 1) / kGroupEnvs), block(kGroupBlock);                                                         \
-        const bool joints = !h->cfg.is_discrete && h->cfg.action_joints;                                                             \
-        switch (h->cfg.rng_mode) {                                                                                                   \
-            case SRLHIP_RNG_PHILOX: SRL_GROUP_MODE(SRLHIP_RNG_PHILOX, CM) break;                                                     \
-            case SRLHIP_RNG_MT19937: SRL_GROUP_MODE(SRLHIP_RNG_MT19937, CM) break;                                                   \
-            default: SRL_GROUP_MODE(SRLHIP_RNG_HOST, CM)                                                                             \
-        }                                                                                                                            \
-        SRL_HIP_CHECK(h, hipGetLastError());                                                                                         \
-        return 0;                                                                                                                    \
-    }
-#define SRL_GROUP_GO(MODE, J, G, CM) hipLaunchKernelGGL((kuka_group_rollout_k<MODE, J, G, CM>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, T, d_actions, d_noise, obs, d_rew, d_done, d_act_out)
-#define SRL_GROUP_MODE(MODE, CM)                                                            \
-    if (joints && d_actions) SRL_GROUP_GO(MODE, true, true, CM);                            \
-    else if (joints) SRL_GROUP_GO(MODE, true, false, CM);                                   \
-    else if (d_actions) SRL_GROUP_GO(MODE, false, true, CM);                                \
-    else SRL_GROUP_GO(MODE, false, false, CM);
-
 }  // namespace srl

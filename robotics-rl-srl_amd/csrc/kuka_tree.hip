@@ -69,143 +69,90 @@ __global__ void __launch_bounds__(kGroupBlock) kuka_tree_refresh_k(KukaParams p,
 
 }  // namespace
 
-#define SRL_TREE_GO(MODE, J, G, NB) hipLaunchKernelGGL((kuka_tree_rollout_k<MODE, J, G, NB>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, T, d_actions, d_noise, obs, d_rew, d_done, d_act_out, G ? sig : PersistArgs{})
-// (Kuka2ButtonGymEnv takes discrete actions only: no joints-mode instantiation of the two-button kernels)
-#define SRL_TREE_MODE(MODE)                                         \
-    if (two && d_actions) SRL_TREE_GO(MODE, false, true, 2);        \
-    else if (two) SRL_TREE_GO(MODE, false, false, 2);               \
-    else if (joints && d_actions) SRL_TREE_GO(MODE, true, true, 1); \
-    else if (joints) SRL_TREE_GO(MODE, true, false, 1);             \
-    else if (d_actions) SRL_TREE_GO(MODE, false, true, 1);          \
-    else SRL_TREE_GO(MODE, false, false, 1);
+// (the host copy of the installed table is part of every Handle; the value means something on full-model handles only, and only they come here)
+static double solver_detail_of(const Handle *h) { return reinterpret_cast<const TreeModel *>(h->kuka_tmodel_host)->solver_detail; }
+
+// Which kernel: kuka_tree_select.hpp (tree_select_launch).  Two overrides, read here: SRLHIP_KUKA_SPEC=0 keeps the generic instantiation
+// where the configuration-specialised one applies (tests compare the two), once per process; SRLHIP_KUKA_OCC=0|1 forces the one- or the
+// two-wavefront variant (tests run both on small batches), at every call.
+// (Why the two-wavefront variant is the default only from 65536 envs up: kuka_tree_occ.hip.  Round 5: where the specialised
+//  one-wavefront instantiation applies it is the faster one at every size measured — 65536 envs 1.73e8 against 1.66e8, 131072 1.74e8
+//  against 1.72e8 env-steps/s, profiles/r05_nsweep_kuka.jsonl — so the default takes the variant only where that one does not apply.)
 int kuka_tree_launch(Handle *h, const KukaParams &p, int T, const void *d_actions, const double *d_noise, float *obs, float *d_rew,
                      uint8_t *d_done, void *d_act_out) {
-    if (h->cfg.env_kind == SRLHIP_ENV_KUKA_RAND) return kuka_tree_rb_launch(h, p, T, d_actions, d_noise, obs, d_rew, d_done, d_act_out);   // free bodies: kuka_tree_rb.hip
-    // the reference's default KukaButtonGymEnv configuration on a device RNG mode: the instantiation with that configuration folded in
-    // (kuka_tree_kernels.hpp, SPEC = 1); SRLHIP_KUKA_SPEC=0 keeps the generic instantiation (tests compare the two)
-    const srlhip_config &c = h->cfg;
-    static const bool spec_enabled = [] { const char *v = getenv("SRLHIP_KUKA_SPEC"); return !v || atoi(v) != 0; }();
-    const bool spec = spec_enabled && reinterpret_cast<const TreeModel *>(h->kuka_tmodel_host)->solver_detail == 0.0 && c.env_kind == SRLHIP_ENV_KUKA_BUTTON && (c.rng_mode == SRLHIP_RNG_PHILOX || c.rng_mode == SRLHIP_RNG_MT19937) && c.is_discrete && !c.action_joints && !c.random_target &&
-                      c.force_down && !c.shape_reward && c.action_repeat == 1 && c.auto_reset &&
-                      (c.obs_mode == SRLHIP_OBS_GROUND_TRUTH || (c.obs_mode == SRLHIP_OBS_RAW_PIXELS && !obs));      // raw_pixels: the rasteriser draws, the stepper writes no observation
-    {
-        // Very large batches run the two-wavefronts-per-SIMD variant (kuka_tree_occ.hip: one-button envs, Cartesian actions).
-        // Measured after the contact-sweep work (profiles/r04_occ_nsweep_final.jsonl, one -> two wavefronts, env-steps/s x 1e8):
-        // 16384 envs 1.62 -> 1.37, 32768 1.63 -> 1.56, 65536 1.65 -> 1.67, 131072 1.66 -> 1.73 (before that work the variant won from
-        // 32768: profiles/r04_occ_nsweep.jsonl).  The sweep is a dependent f64 chain that one wavefront already issues at 6.2 of
-        // the SIMD's 4.1 cycles per op (profiles/r04_f64_issue_rate.txt), so a second wavefront can hide little, its register diet
-        // (256 instead of 512) costs ~1 KB/lane of scratch, and its four envs take turns in the contact path.  Hence the threshold.
-        // SRLHIP_KUKA_OCC=0|1 forces either variant (tests run both on small batches).
-        const char *force = getenv("SRLHIP_KUKA_OCC");
-        const bool one_button = h->cfg.env_kind == SRLHIP_ENV_KUKA_BUTTON || h->cfg.env_kind == SRLHIP_ENV_KUKA_MOVING;
-        const bool cartesian = h->cfg.is_discrete || !h->cfg.action_joints;
-        // (round 5: where the configuration-specialised one-wavefront instantiation applies it is the faster one at every size measured
-        //  — 65536 envs 1.73e8 against 1.66e8, 131072 1.74e8 against 1.72e8, profiles/r05_nsweep_kuka.jsonl — so the default dispatch takes
-        //  the two-wavefront variant only for configurations that instantiation does not cover)
-        const bool occ = force ? force[0] == '1' : (h->n >= 65536 && !spec);
-        if (occ && one_button && cartesian) return kuka_tree_occ_launch(h, p, T, d_actions, d_noise, obs, d_rew, d_done, d_act_out);
-    }
-    dim3 grid(contiguous_grid((h->n + kGroupEnvs - 1) / kGroupEnvs)), block(kGroupBlock);      // a multiple of 8: the rollout kernel maps blocks to envs XCD by XCD
-    const bool joints = !h->cfg.is_discrete && h->cfg.action_joints, two = h->cfg.env_kind == SRLHIP_ENV_KUKA_2BUTTON;
-    // a single-step launch with the caller's actions on a handle whose host side armed the early completion signal (api.hip): this
-    // kernel reports the step's outputs per eighth of the grid before it ends
-    PersistArgs sig{};
-    if (h->step_signal.done && T == 1 && d_actions) {
-        sig = h->step_signal; h->step_signal_armed = true;
-        h->signal_eighths = contiguous_eighths((h->n + kGroupEnvs - 1) / kGroupEnvs);
-    }
-    if (spec) {
-#define SRL_TREE_SPEC(MODE, G) hipLaunchKernelGGL((kuka_tree_rollout_k<MODE, false, G, 1, 0, 1>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, T, d_actions, d_noise, obs, d_rew, d_done, d_act_out, G ? sig : PersistArgs{})
-        if (c.rng_mode == SRLHIP_RNG_PHILOX) { if (d_actions) SRL_TREE_SPEC(SRLHIP_RNG_PHILOX, true); else SRL_TREE_SPEC(SRLHIP_RNG_PHILOX, false); }
-        else { if (d_actions) SRL_TREE_SPEC(SRLHIP_RNG_MT19937, true); else SRL_TREE_SPEC(SRLHIP_RNG_MT19937, false); }     // (the reference's own streams: HipVecEnv's default)
-#undef SRL_TREE_SPEC
-        SRL_HIP_CHECK(h, hipGetLastError());
-        return 0;
-    }
-    switch (h->cfg.rng_mode) {
-        case SRLHIP_RNG_PHILOX: SRL_TREE_MODE(SRLHIP_RNG_PHILOX) break;
-        case SRLHIP_RNG_MT19937: SRL_TREE_MODE(SRLHIP_RNG_MT19937) break;
-        default: SRL_TREE_MODE(SRLHIP_RNG_HOST)
-    }
-    SRL_HIP_CHECK(h, hipGetLastError());
-    return 0;
+    static const bool spec_allowed = [] { const char *v = getenv("SRLHIP_KUKA_SPEC"); return !v || atoi(v) != 0; }();
+    const char *force = getenv("SRLHIP_KUKA_OCC");
+    const TreeSelect s = tree_select_launch(h->cfg, h->n, d_actions != nullptr, T, obs != nullptr, solver_detail_of(h), h->step_signal.done != nullptr,
+                                            force ? (force[0] == '1' ? 1 : 0) : -1, spec_allowed);
+    if (s.family == TREE_RB) return kuka_tree_rb_launch(h, p, s, T, d_actions, d_noise, obs, d_rew, d_done, d_act_out);      // free bodies: kuka_tree_rb.hip
+    if (s.family == TREE_OCC) return kuka_tree_occ_launch(h, p, s, T, d_actions, d_noise, obs, d_rew, d_done, d_act_out);
+    const TreeIo io = {T, d_actions, d_noise, obs, d_rew, d_done, d_act_out};
+    int rc = 0;
+    bool hit;
+    if (s.family == TREE_SPEC)      // (MT19937: the reference's own streams, HipVecEnv's default)
+        hit = dispatch_rollout_device_rng(s.mode, [&](auto mode) {
+            return dispatch_int<0, 1>(s.given, [&](auto given) { rc = tree_rollout_launch<0, 1>(h, p, mode, Const<0>{}, given, Const<1>{}, s.arm_signal, io); });
+        });
+    else
+        hit = dispatch_rollout_rng(s.mode, [&](auto mode) {
+            return dispatch_tree_arm(s.joints, s.nb, [&](auto joints, auto nb) {
+                return dispatch_int<0, 1>(s.given, [&](auto given) { rc = tree_rollout_launch(h, p, mode, joints, given, nb, s.arm_signal, io); });
+            });
+        });
+    return hit ? rc : h->fail(SRLHIP_ENOTSUP, "rollout: no instantiation for this Kuka configuration");
 }
 
 // ---- persistent stepping (step_signal.hpp; srlhip_set_persistent) -------------------------------------------------------------------
-// Persistent instantiations exist for KukaButtonGymEnv, KukaMovingButtonGymEnv and Kuka2ButtonGymEnv on a device RNG mode: the
-// configuration-specialised kernel where kuka_tree_launch would pick it (reference ctor defaults, default solver details), the generic
-// one otherwise (random_target, shaped reward, continuous Cartesian or joint-space actions, the joints observation modes, other
-// solver details).  The grid must be CO-RESIDENT: a workgroup that waits for the host in a loop never makes room for one that has not
-// started.
-static int persist_kind(const Handle *h) {          // 0: none, 1: SPEC, 2: generic Cartesian, 3: generic joint-space actions, 4: Kuka2Button
-    const srlhip_config &c = h->cfg;
-    if (!h->kuka || c.kuka_model != SRLHIP_KUKA_MODEL_FULL || c.env_kind == SRLHIP_ENV_KUKA_RAND ||      // (KukaRandButton: kuka_tree_rb.hip, kinds 5, 6)
-        !(c.rng_mode == SRLHIP_RNG_PHILOX || c.rng_mode == SRLHIP_RNG_MT19937) || c.obs_mode == SRLHIP_OBS_RAW_PIXELS)
-        return 0;
-    if (c.env_kind == SRLHIP_ENV_KUKA_2BUTTON) return c.is_discrete ? 4 : 0;          // (Kuka2ButtonGymEnv takes discrete actions only)
-    const bool spec = reinterpret_cast<const TreeModel *>(h->kuka_tmodel_host)->solver_detail == 0.0 && c.env_kind == SRLHIP_ENV_KUKA_BUTTON && c.is_discrete &&
-                      !c.action_joints && !c.random_target && c.force_down && !c.shape_reward && c.action_repeat == 1 && c.auto_reset && c.obs_mode == SRLHIP_OBS_GROUND_TRUTH;
-    if (spec) return 1;
-    return (!c.is_discrete && c.action_joints) ? 3 : 2;
-}
-static const void *persist_fn(const Handle *h, int kind) {
-    const bool ph = h->cfg.rng_mode == SRLHIP_RNG_PHILOX;
-    switch (kind) {
-        case 1: return ph ? reinterpret_cast<const void *>(kuka_tree_rollout_k<SRLHIP_RNG_PHILOX, false, true, 1, 0, 1, 1>) : reinterpret_cast<const void *>(kuka_tree_rollout_k<SRLHIP_RNG_MT19937, false, true, 1, 0, 1, 1>);
-        case 2: return ph ? reinterpret_cast<const void *>(kuka_tree_rollout_k<SRLHIP_RNG_PHILOX, false, true, 1, 0, 0, 1>) : reinterpret_cast<const void *>(kuka_tree_rollout_k<SRLHIP_RNG_MT19937, false, true, 1, 0, 0, 1>);
-        case 3: return ph ? reinterpret_cast<const void *>(kuka_tree_rollout_k<SRLHIP_RNG_PHILOX, true, true, 1, 0, 0, 1>) : reinterpret_cast<const void *>(kuka_tree_rollout_k<SRLHIP_RNG_MT19937, true, true, 1, 0, 0, 1>);
-        case 4: return ph ? reinterpret_cast<const void *>(kuka_tree_rollout_k<SRLHIP_RNG_PHILOX, false, true, 2, 0, 0, 1>) : reinterpret_cast<const void *>(kuka_tree_rollout_k<SRLHIP_RNG_MT19937, false, true, 2, 0, 0, 1>);
-    }
-    return nullptr;
+// Which resident kernel, if any: kuka_tree_select.hpp (tree_select_persist).  The grid must be CO-RESIDENT: a workgroup that waits for
+// the host in a loop never makes room for one that has not started.  So the kernel whose occupancy decides whether the grid fits and the
+// kernel that is launched must be the same one: both come out of this one dispatch on the selected tuple: specialised, generic Cartesian,
+// generic joint-space actions, Kuka2Button — f(mode, joints, nb, spec).
+template <class F>
+static bool dispatch_persist(const Handle *h, F &&f) {
+    if (!h->kuka) return false;
+    const TreeSelect s = tree_select_persist(h->cfg, solver_detail_of(h));
+    if (s.family == TREE_NONE) return false;
+    const auto go = [&](auto joints, auto nb, auto spec) { return dispatch_rollout_device_rng(s.mode, [&](auto mode) { f(mode, joints, nb, spec); }); };
+    if (s.family == TREE_SPEC) return go(Const<0>{}, Const<1>{}, Const<1>{});
+    if (s.nb == 1 && !s.joints) return go(Const<0>{}, Const<1>{}, Const<0>{});
+    if (s.nb == 1 && s.joints) return go(Const<1>{}, Const<1>{}, Const<0>{});
+    if (s.nb == 2 && !s.joints) return go(Const<0>{}, Const<2>{}, Const<0>{});
+    return false;
 }
 int kuka_tree_persist_blocks(Handle *h, int *capacity) {
     if (capacity) *capacity = 0;
-    const int kind = persist_kind(h);
-    if (!kind) return 0;
+    const void *fn = nullptr;
+    dispatch_persist(h, [&](auto mode, auto joints, auto nb, auto spec) {
+        fn = reinterpret_cast<const void *>(kuka_tree_rollout_k<decltype(mode)::value, decltype(joints)::value != 0, true, decltype(nb)::value, 0, decltype(spec)::value, 1>);
+    });
+    if (!fn) return 0;
     const int real = (h->n + kGroupEnvs - 1) / kGroupEnvs, grid = contiguous_grid(real);
     int per_cu = 0;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, h->cfg.device_id) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persist_fn(h, kind), kGroupBlock, 0) != hipSuccess) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kGroupBlock, 0) != hipSuccess) return 0;
     if (capacity) *capacity = per_cu * prop.multiProcessorCount;       // workgroups of this kernel the device holds at once
     return (long long)per_cu * prop.multiProcessorCount >= grid ? real : 0;
 }
 int kuka_tree_persist_launch(Handle *h, const KukaParams &p, const void *d_actions, float *obs, float *d_rew, uint8_t *d_done, const PersistArgs &pa) {
-    dim3 grid(contiguous_grid((h->n + kGroupEnvs - 1) / kGroupEnvs)), block(kGroupBlock);
-    const double *no_noise = nullptr;
-    void *no_act = nullptr;
-    const bool ph = h->cfg.rng_mode == SRLHIP_RNG_PHILOX;
-#define SRL_TREE_PERSIST(MODE, J, SPEC) hipLaunchKernelGGL((kuka_tree_rollout_k<MODE, J, true, 1, 0, SPEC, 1>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, 0, d_actions, no_noise, obs, d_rew, d_done, no_act, pa)
-#define SRL_TREE_PERSIST2(MODE) hipLaunchKernelGGL((kuka_tree_rollout_k<MODE, false, true, 2, 0, 0, 1>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, 0, d_actions, no_noise, obs, d_rew, d_done, no_act, pa)
-    switch (persist_kind(h)) {
-        case 1: if (ph) SRL_TREE_PERSIST(SRLHIP_RNG_PHILOX, false, 1); else SRL_TREE_PERSIST(SRLHIP_RNG_MT19937, false, 1); break;
-        case 2: if (ph) SRL_TREE_PERSIST(SRLHIP_RNG_PHILOX, false, 0); else SRL_TREE_PERSIST(SRLHIP_RNG_MT19937, false, 0); break;
-        case 3: if (ph) SRL_TREE_PERSIST(SRLHIP_RNG_PHILOX, true, 0); else SRL_TREE_PERSIST(SRLHIP_RNG_MT19937, true, 0); break;
-        case 4: if (ph) SRL_TREE_PERSIST2(SRLHIP_RNG_PHILOX); else SRL_TREE_PERSIST2(SRLHIP_RNG_MT19937); break;
-        default: return h->fail(SRLHIP_ENOTSUP, "persistent stepping: no instantiation for this configuration");
-    }
-#undef SRL_TREE_PERSIST
-#undef SRL_TREE_PERSIST2
-    SRL_HIP_CHECK(h, hipGetLastError());
-    return 0;
+    const TreeIo io = {0, d_actions, nullptr, obs, d_rew, d_done, nullptr};
+    int rc = 0;
+    const bool hit = dispatch_persist(h, [&](auto mode, auto joints, auto nb, auto spec) {
+        rc = tree_rollout_launch<0, decltype(spec)::value, 1>(h, p, mode, joints, Const<1>{}, nb, false, io, pa);
+    });
+    return hit ? rc : h->fail(SRLHIP_ENOTSUP, "persistent stepping: no instantiation for this configuration");
 }
 
 int kuka_tree_reset(Handle *h, const KukaParams &p, const uint8_t *d_mask, const double *d_host_rand, int stride, float *obs) {
     if (h->cfg.env_kind == SRLHIP_ENV_KUKA_RAND) return kuka_tree_rb_reset(h, p, d_mask, d_host_rand, stride, obs);
-    dim3 grid((h->n + kGroupEnvs - 1) / kGroupEnvs), block(kGroupBlock);
-    const bool joints = !h->cfg.is_discrete && h->cfg.action_joints, two = h->cfg.env_kind == SRLHIP_ENV_KUKA_2BUTTON;
-#define SRL_TRESET(MODE)                                                                                                                       \
-    if (two) hipLaunchKernelGGL((kuka_tree_reset_k<MODE, false, 2>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, d_mask, d_host_rand, stride, obs); \
-    else if (joints) hipLaunchKernelGGL((kuka_tree_reset_k<MODE, true, 1>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, d_mask, d_host_rand, stride, obs); \
-    else hipLaunchKernelGGL((kuka_tree_reset_k<MODE, false, 1>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, d_mask, d_host_rand, stride, obs)
-    switch (h->cfg.rng_mode) {
-        case SRLHIP_RNG_HOST: SRL_TRESET(SRLHIP_RNG_HOST); break;
-        case SRLHIP_RNG_PHILOX: SRL_TRESET(SRLHIP_RNG_PHILOX); break;
-        default: SRL_TRESET(SRLHIP_RNG_MT19937);
-    }
-#undef SRL_TRESET
-    SRL_HIP_CHECK(h, hipGetLastError());
-    return 0;
+    const bool two = h->cfg.env_kind == SRLHIP_ENV_KUKA_2BUTTON;
+    int rc = 0;
+    const bool hit = dispatch_reset_rng(h->cfg.rng_mode, [&](auto mode) {
+        return dispatch_tree_arm(!two && tree_joint_actions(h->cfg), two ? 2 : 1, [&](auto joints, auto nb) {
+            rc = tree_reset_launch<0>(h, p, mode, joints, nb, d_mask, d_host_rand, stride, obs);
+        });
+    });
+    return hit ? rc : h->fail(SRLHIP_ENOTSUP, "reset: no instantiation for this Kuka configuration");
 }
 
 int kuka_tree_settle(Handle *h, const KukaParams &p) {

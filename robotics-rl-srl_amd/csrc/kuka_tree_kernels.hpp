@@ -5,6 +5,7 @@
 #pragma once
 #include "kuka_device.hpp"
 #include "kuka_tree.hpp"
+#include "kuka_tree_select.hpp"
 
 namespace srl {
 using namespace kuka;
@@ -95,7 +96,7 @@ __device__ __forceinline__ void tstore_body(const KukaState &s, int64_t n, int e
 // action_repeat 1, sparse reward, auto-reset: kuka_button_gym_env.py:93-98 ctor defaults) AND the model table's default solver details
 // (solver_detail = 0) as compile-time constants — the run-time
 // configuration tests of the env logic and of the step's branches fold away (the host selects it only for a handle with exactly
-// this configuration, kuka_tree.hip: spec_config_of).
+// this configuration, kuka_tree_select.hpp: tree_spec_config).
 // PERSIST = 1 (srlhip_set_persistent; GIVEN actions; the protocol is step_signal.hpp's): the loop does not count to T — before every step
 // the wavefront waits for the host's next sequence number, reads its actions from the SAME mapped row every step, writes its outputs
 // straight to the host's mapped planes (on a placement where that is not valid: to a staging copy that the last wavefront of its eighth
@@ -680,60 +681,77 @@ kuka_tree_reset_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, const
     }
 }
 
-// srlhip_rollout_policy (POLICY = 1, kuka_tree_policy.hip) / srlhip_rollout_mlp_policy (POLICY = 2, kuka_tree_mlp.hip): the launch both
-// share — {PHILOX, MT19937} x {Cartesian one button, joint-space actions one button, Cartesian two buttons}, generic configuration
-// (SPEC = 0), launching form.  Every batch size runs this one-wavefront-per-SIMD kernel (the two-wavefront variant of kuka_tree_occ.hip
-// has no policy form).  Instantiating it instantiates the six kernels: once per POLICY, each in its own translation unit.
-// The guard restates what srlhip_rollout_policy / srlhip_rollout_mlp_policy have refused by name before they come here (api.hip:
-// rollout_policy): through the ABI it never fires, so where a caller's own refusal stands relative to it cannot be observed.
-template <int POLICY>
-int kuka_tree_policy_launch(Handle *h, const char *name, int T, const PolicyArgs &pol, double *d_hdr, float *obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
-    const srlhip_config &c = h->cfg;
-    if (!h->kuka || !h->kuka->full || c.env_kind == SRLHIP_ENV_KUKA_RAND || c.obs_mode != SRLHIP_OBS_GROUND_TRUTH || !c.auto_reset ||
-        (c.rng_mode != SRLHIP_RNG_PHILOX && c.rng_mode != SRLHIP_RNG_MT19937))
-        return h->fail(SRLHIP_ENOTSUP, std::string(name) + ": no policy instantiation for this Kuka configuration");
-    const KukaParams p = params_of(h);
-    int rc = kuka_policy_header(h, d_hdr, pol);
-    if (rc) return rc;
-    dim3 grid(contiguous_grid((h->n + kGroupEnvs - 1) / kGroupEnvs)), block(kGroupBlock);      // as kuka_tree_launch: blocks map to envs XCD by XCD
-    const bool joints = !c.is_discrete && c.action_joints, two = c.env_kind == SRLHIP_ENV_KUKA_2BUTTON;
-    const void *d_w = pol.w;
-    const double *hdr = d_hdr;
-#define SRL_TREE_POL(MODE, J, NB) hipLaunchKernelGGL((kuka_tree_rollout_k<MODE, J, false, NB, 0, 0, 0, POLICY>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, T, d_w, hdr, obs, d_rew, d_done, d_act_out, PersistArgs{})
-#define SRL_TREE_POL_MODE(MODE)                       \
-    if (two) SRL_TREE_POL(MODE, false, 2);            \
-    else if (joints) SRL_TREE_POL(MODE, true, 1);     \
-    else SRL_TREE_POL(MODE, false, 1);
-    if (c.rng_mode == SRLHIP_RNG_PHILOX) { SRL_TREE_POL_MODE(SRLHIP_RNG_PHILOX) } else { SRL_TREE_POL_MODE(SRLHIP_RNG_MT19937) }
-#undef SRL_TREE_POL_MODE
-#undef SRL_TREE_POL
+// ---- launches: the ONE place per kernel template where its template arguments meet a launch ---------------------------------------
+// (a new instantiation is a new arm in the dispatch of the translation unit that is to hold it; templates, so that only a unit that
+//  calls one instantiates its kernels)
+
+// the (JOINTS, NB) pairs the kernels exist for: Cartesian two buttons (Kuka2ButtonGymEnv takes discrete actions only), joint-space one
+// button (compiled out with JOINT_ARM = false), Cartesian one button.  f(joints, nb)
+template <bool JOINT_ARM = true, class F>
+bool dispatch_tree_arm(int joints, int nb, F &&f) {
+    if (nb == 2 && !joints) { f(Const<0>{}, Const<2>{}); return true; }
+    if constexpr (JOINT_ARM) if (nb == 1 && joints) { f(Const<1>{}, Const<1>{}); return true; }
+    if (nb == 1 && !joints) { f(Const<0>{}, Const<1>{}); return true; }
+    return false;
+}
+
+// what a rollout launch passes through to kuka_tree_rollout_k
+struct TreeIo { int T; const void *actions; const double *noise; float *obs, *rew; uint8_t *done; void *act_out; };
+
+// kuka_tree_rollout_k<MODE, JOINTS, GIVEN, NB, RB, SPEC, PERSIST, POLICY>: grid (a multiple of 8 blocks: the kernel maps blocks to envs
+// XCD by XCD), the early completion signal, launch, error check.  arm_signal (kuka_tree_select.hpp): a single-step launch with the
+// caller's actions on a handle whose host side armed the signal (api.hip) — the kernel reports the step's outputs per eighth of the grid
+// before it ends.  pa: the resident kernel's control block (PERSIST = 1), nothing otherwise.
+template <int RB = 0, int SPEC = 0, int PERSIST = 0, int POLICY = 0, int MODE, int JOINTS, int GIVEN, int NB>
+int tree_rollout_launch(Handle *h, const KukaParams &p, Const<MODE>, Const<JOINTS>, Const<GIVEN>, Const<NB>, bool arm_signal, const TreeIo &io,
+                        PersistArgs pa = PersistArgs{}) {
+    const int real = (h->n + kGroupEnvs - 1) / kGroupEnvs;
+    dim3 grid(contiguous_grid(real)), block(kGroupBlock);
+    if (arm_signal) {
+        pa = h->step_signal; h->step_signal_armed = true;
+        h->signal_eighths = contiguous_eighths(real);
+    }
+    hipLaunchKernelGGL((kuka_tree_rollout_k<MODE, JOINTS != 0, GIVEN != 0, NB, RB, SPEC, PERSIST, POLICY>), grid, block, 0, h->stream, p, *h->kuka, h->rng,
+                       h->stats, io.T, io.actions, io.noise, io.obs, io.rew, io.done, io.act_out, pa);
     SRL_HIP_CHECK(h, hipGetLastError());
     return 0;
 }
 
-// srlhip_rollout_mlp_policy_sampled (POLICY = 3, kuka_tree_mlp_sample.hip): the same launch over {PHILOX, MT19937} x {Cartesian one
-// button, two buttons} — four kernels, discrete actions only (the entry point has refused the continuous modes by name).  A template
-// like its sibling, so that only the translation unit that calls it instantiates them.
+// kuka_tree_reset_k<MODE, JOINTS, NB, RB>
+template <int RB, int MODE, int JOINTS, int NB>
+int tree_reset_launch(Handle *h, const KukaParams &p, Const<MODE>, Const<JOINTS>, Const<NB>, const uint8_t *d_mask, const double *d_host_rand, int stride, float *obs) {
+    dim3 grid((h->n + kGroupEnvs - 1) / kGroupEnvs), block(kGroupBlock);
+    hipLaunchKernelGGL((kuka_tree_reset_k<MODE, JOINTS != 0, NB, RB>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, d_mask, d_host_rand, stride, obs);
+    SRL_HIP_CHECK(h, hipGetLastError());
+    return 0;
+}
+
+// srlhip_rollout_policy (POLICY = 1, kuka_tree_policy.hip) / srlhip_rollout_mlp_policy (POLICY = 2, kuka_tree_mlp.hip) /
+// srlhip_rollout_mlp_policy_sampled (POLICY = 3, kuka_tree_mlp_sample.hip): the launch all three share — {PHILOX, MT19937} x {Cartesian
+// one button, joint-space actions one button, Cartesian two buttons}, generic configuration (SPEC = 0), launching form; POLICY = 3
+// samples discrete actions only and has no joint-space arm (four kernels instead of six).  Every batch size runs this
+// one-wavefront-per-SIMD kernel (the two-wavefront variant of kuka_tree_occ.hip has no policy form).  Instantiating it instantiates the
+// kernels: once per POLICY, each in its own translation unit.
+// The guard restates what the entry points have refused by name before they come here (api.hip: rollout_policy): through the ABI it
+// never fires, so where a caller's own refusal stands relative to it cannot be observed.
 template <int POLICY>
-int kuka_tree_sampled_launch(Handle *h, const char *name, int T, const PolicyArgs &pol, double *d_hdr, float *obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
+int kuka_tree_policy_launch(Handle *h, const char *name, int T, const PolicyArgs &pol, double *d_hdr, float *obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
     const srlhip_config &c = h->cfg;
-    if (!h->kuka || !h->kuka->full || c.env_kind == SRLHIP_ENV_KUKA_RAND || c.obs_mode != SRLHIP_OBS_GROUND_TRUTH || !c.auto_reset || !c.is_discrete ||
-        (c.rng_mode != SRLHIP_RNG_PHILOX && c.rng_mode != SRLHIP_RNG_MT19937))
-        return h->fail(SRLHIP_ENOTSUP, std::string(name) + ": no policy instantiation for this Kuka configuration");
+    const auto refuse = [&] { return h->fail(SRLHIP_ENOTSUP, std::string(name) + ": no policy instantiation for this Kuka configuration"); };
+    if (!h->kuka || !h->kuka->full || c.env_kind == SRLHIP_ENV_KUKA_RAND || c.obs_mode != SRLHIP_OBS_GROUND_TRUTH || !c.auto_reset ||
+        (POLICY == 3 && !c.is_discrete) || !tree_device_rng(c))
+        return refuse();
     const KukaParams p = params_of(h);
     int rc = kuka_policy_header(h, d_hdr, pol);
     if (rc) return rc;
-    dim3 grid(contiguous_grid((h->n + kGroupEnvs - 1) / kGroupEnvs)), block(kGroupBlock);      // as kuka_tree_policy_launch
     const bool two = c.env_kind == SRLHIP_ENV_KUKA_2BUTTON;
-    const void *d_w = pol.w;
-    const double *hdr = d_hdr;
-    static_assert(POLICY == 3, "the sampling policy form");
-#define SRL_TREE_SMP(MODE, NB) hipLaunchKernelGGL((kuka_tree_rollout_k<MODE, false, false, NB, 0, 0, 0, POLICY>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, T, d_w, hdr, obs, d_rew, d_done, d_act_out, PersistArgs{})
-    if (c.rng_mode == SRLHIP_RNG_PHILOX) { if (two) SRL_TREE_SMP(SRLHIP_RNG_PHILOX, 2); else SRL_TREE_SMP(SRLHIP_RNG_PHILOX, 1); }
-    else { if (two) SRL_TREE_SMP(SRLHIP_RNG_MT19937, 2); else SRL_TREE_SMP(SRLHIP_RNG_MT19937, 1); }
-#undef SRL_TREE_SMP
-    SRL_HIP_CHECK(h, hipGetLastError());
-    return 0;
+    const TreeIo io = {T, pol.w, d_hdr, obs, d_rew, d_done, d_act_out};
+    const bool hit = dispatch_rollout_device_rng(c.rng_mode, [&](auto mode) {
+        return dispatch_tree_arm<POLICY != 3>(!two && tree_joint_actions(c), two ? 2 : 1, [&](auto joints, auto nb) {
+            rc = tree_rollout_launch<0, 0, 0, POLICY>(h, p, mode, joints, Const<0>{}, nb, false, io);
+        });
+    });
+    return hit ? rc : refuse();
 }
 
 }  // namespace

@@ -121,16 +121,17 @@ kuka_tree_rollout_occ_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st,
 
 }  // namespace
 
-#define SRL_TREE_OCC_GO(MODE, G) hipLaunchKernelGGL((kuka_tree_rollout_occ_k<MODE, G>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, T, d_actions, d_noise, obs, d_rew, d_done, d_act_out)
-int kuka_tree_occ_launch(Handle *h, const KukaParams &p, int T, const void *d_actions, const double *d_noise, float *obs, float *d_rew,
+int kuka_tree_occ_launch(Handle *h, const KukaParams &p, const TreeSelect &s, int T, const void *d_actions, const double *d_noise, float *obs, float *d_rew,
                          uint8_t *d_done, void *d_act_out) {
     const int envs_per_block = kOccBlock / grp::GL;
     dim3 grid((h->n + envs_per_block - 1) / envs_per_block), block(kOccBlock);
-    switch (h->cfg.rng_mode) {
-        case SRLHIP_RNG_PHILOX: if (d_actions) SRL_TREE_OCC_GO(SRLHIP_RNG_PHILOX, true); else SRL_TREE_OCC_GO(SRLHIP_RNG_PHILOX, false); break;
-        case SRLHIP_RNG_MT19937: if (d_actions) SRL_TREE_OCC_GO(SRLHIP_RNG_MT19937, true); else SRL_TREE_OCC_GO(SRLHIP_RNG_MT19937, false); break;
-        default: if (d_actions) SRL_TREE_OCC_GO(SRLHIP_RNG_HOST, true); else SRL_TREE_OCC_GO(SRLHIP_RNG_HOST, false);
-    }
+    const bool hit = dispatch_rollout_rng(s.mode, [&](auto mode) {
+        return dispatch_int<0, 1>(s.given, [&](auto given) {
+            hipLaunchKernelGGL((kuka_tree_rollout_occ_k<decltype(mode)::value, decltype(given)::value != 0>), grid, block, 0, h->stream, p, *h->kuka, h->rng,
+                               h->stats, T, d_actions, d_noise, obs, d_rew, d_done, d_act_out);
+        });
+    });
+    if (!hit) return h->fail(SRLHIP_ENOTSUP, "rollout: no instantiation for this Kuka configuration");
     SRL_HIP_CHECK(h, hipGetLastError());
     return 0;
 }

@@ -7,44 +7,26 @@
 namespace srl {
 using namespace kuka;
 
-#define SRL_TREE_RB_GO(MODE, J, G) hipLaunchKernelGGL((kuka_tree_rollout_k<MODE, J, G, 1, 1>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, T, d_actions, d_noise, obs, d_rew, d_done, d_act_out, G ? sig : PersistArgs{})
-#define SRL_TREE_RB_MODE(MODE)                                      \
-    if (joints && d_actions) SRL_TREE_RB_GO(MODE, true, true);      \
-    else if (joints) SRL_TREE_RB_GO(MODE, true, false);             \
-    else if (d_actions) SRL_TREE_RB_GO(MODE, false, true);          \
-    else SRL_TREE_RB_GO(MODE, false, false);
-int kuka_tree_rb_launch(Handle *h, const KukaParams &p, int T, const void *d_actions, const double *d_noise, float *obs, float *d_rew,
+int kuka_tree_rb_launch(Handle *h, const KukaParams &p, const TreeSelect &s, int T, const void *d_actions, const double *d_noise, float *obs, float *d_rew,
                         uint8_t *d_done, void *d_act_out) {
-    dim3 grid(contiguous_grid((h->n + kGroupEnvs - 1) / kGroupEnvs)), block(kGroupBlock);      // a multiple of 8: the rollout kernel maps blocks to envs XCD by XCD
-    const bool joints = !h->cfg.is_discrete && h->cfg.action_joints;
-    PersistArgs sig{};                          // the early completion signal of a single-step launch (kuka_tree.hip, api.hip)
-    if (h->step_signal.done && T == 1 && d_actions) {
-        sig = h->step_signal; h->step_signal_armed = true;
-        h->signal_eighths = contiguous_eighths((h->n + kGroupEnvs - 1) / kGroupEnvs);
-    }
-    switch (h->cfg.rng_mode) {
-        case SRLHIP_RNG_PHILOX: SRL_TREE_RB_MODE(SRLHIP_RNG_PHILOX) break;
-        case SRLHIP_RNG_MT19937: SRL_TREE_RB_MODE(SRLHIP_RNG_MT19937) break;
-        default: SRL_TREE_RB_MODE(SRLHIP_RNG_HOST)
-    }
-    SRL_HIP_CHECK(h, hipGetLastError());
-    return 0;
+    const TreeIo io = {T, d_actions, d_noise, obs, d_rew, d_done, d_act_out};
+    int rc = 0;
+    const bool hit = dispatch_rollout_rng(s.mode, [&](auto mode) {
+        return dispatch_int<0, 1>(s.joints, [&](auto joints) {
+            return dispatch_int<0, 1>(s.given, [&](auto given) { rc = tree_rollout_launch<1>(h, p, mode, joints, given, Const<1>{}, s.arm_signal, io); });
+        });
+    });
+    return hit ? rc : h->fail(SRLHIP_ENOTSUP, "rollout: no instantiation for this Kuka configuration");
 }
 
 int kuka_tree_rb_reset(Handle *h, const KukaParams &p, const uint8_t *d_mask, const double *d_host_rand, int stride, float *obs) {
-    dim3 grid((h->n + kGroupEnvs - 1) / kGroupEnvs), block(kGroupBlock);
-    const bool joints = !h->cfg.is_discrete && h->cfg.action_joints;
-#define SRL_TRESET_RB(MODE)                                                                                                                    \
-    if (joints) hipLaunchKernelGGL((kuka_tree_reset_k<MODE, true, 1, 1>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, d_mask, d_host_rand, stride, obs); \
-    else hipLaunchKernelGGL((kuka_tree_reset_k<MODE, false, 1, 1>), grid, block, 0, h->stream, p, *h->kuka, h->rng, h->stats, d_mask, d_host_rand, stride, obs)
-    switch (h->cfg.rng_mode) {
-        case SRLHIP_RNG_HOST: SRL_TRESET_RB(SRLHIP_RNG_HOST); break;
-        case SRLHIP_RNG_PHILOX: SRL_TRESET_RB(SRLHIP_RNG_PHILOX); break;
-        default: SRL_TRESET_RB(SRLHIP_RNG_MT19937);
-    }
-#undef SRL_TRESET_RB
-    SRL_HIP_CHECK(h, hipGetLastError());
-    return 0;
+    int rc = 0;
+    const bool hit = dispatch_reset_rng(h->cfg.rng_mode, [&](auto mode) {
+        return dispatch_int<0, 1>(tree_joint_actions(h->cfg) ? 1 : 0, [&](auto joints) {
+            rc = tree_reset_launch<1>(h, p, mode, joints, Const<1>{}, d_mask, d_host_rand, stride, obs);
+        });
+    });
+    return hit ? rc : h->fail(SRLHIP_ENOTSUP, "reset: no instantiation for this Kuka configuration");
 }
 
 }  // namespace srl

@@ -962,11 +962,8 @@ int alloc_state(Handle *h, MobileState &s) {
     return rc;
 }
 
-// Run-time configuration -> template arguments: f is a generic lambda that receives std::integral_constants and launches (or names)
-// the instantiation they select.  Only the combinations a caller dispatches on exist in the library.
-template <int V> using Const = std::integral_constant<int, V>;
-template <int... Vs, class F>
-void dispatch_int(int v, F &&f) { (void)(((v == Vs) && (f(Const<Vs>{}), true)) || ...); }
+// Run-time configuration -> template arguments (internal.hpp: Const / dispatch_int).  Only the combinations a caller dispatches on
+// exist in the library.
 template <class F>
 void dispatch_device_rng(int rng_mode, F &&f) { dispatch_int<SRLHIP_RNG_PHILOX, SRLHIP_RNG_MT19937>(rng_mode, f); }
 template <class F>

@@ -575,10 +575,10 @@ def test_ragged_env_counts_with_mt19937_streams(n):
     h.close()
 
 
-@pytest.mark.parametrize("mode", ["continuous_philox_agent", "joints_mt19937", "host_rng_masked_resets"])
+@pytest.mark.parametrize("mode", ["continuous_philox_agent", "joints_philox_agent", "joints_mt19937", "host_rng_masked_resets"])
 def test_rand_button_env_other_action_modes_and_ragged_batches(mode):
     """KukaRandButtonGymEnv's free bodies under the other kernel instantiations: continuous Cartesian actions sampled on the device
-    (Philox agent), joint-space actions with the reference-exact MT19937 streams, and the host-RNG harness with masked resets — all on
+    (Philox agent; Cartesian and, briefly, joint-space), joint-space actions with the reference-exact MT19937 streams, and the host-RNG harness with masked resets — all on
     batches that do not fill the last wavefront (its spare lane groups shadow the last env, bodies included)."""
     cfg = _lib.default_config(_lib.ENV_KUKA_RAND)
     T = 700
@@ -594,6 +594,18 @@ def test_rand_button_env_other_action_modes_and_ragged_batches(mode):
             ora = kuka_clib.rollout(11 + np.arange(n), T, actions=None, is_discrete=False, random_target=True, rng_mode=kuka_clib.RNG_PHILOX, trace=False)
             kuka_clib.body_trace_off()
             assert np.array_equal(ora["actions"], out["actions"])
+        elif mode == "joints_philox_agent":
+            # joint-space actions sampled on the device: the one free-body instantiation no other case launches.  One full wavefront
+            # plus a tail group that shadows env 4, a grid rounded up to 8 with six padding blocks; three steps exercise the dispatch
+            n, T = 5, 3
+            cfg.num_envs, cfg.seed0, cfg.is_discrete, cfg.action_joints, cfg.rng_mode = n, 41, 0, 1, _lib.RNG_PHILOX
+            h = _lib.Handle(cfg)
+            obs0 = h.reset()
+            out = h.rollout(T)
+            ob = kuka_clib.body_trace(n)
+            ora = kuka_clib.rollout(41 + np.arange(n), T, actions=None, is_discrete=False, action_joints=True, rng_mode=kuka_clib.RNG_PHILOX, trace=False)
+            kuka_clib.body_trace_off()
+            assert out["actions"].shape == (T, n, 7) and np.array_equal(ora["actions"], out["actions"])
         elif mode == "joints_mt19937":
             n = 5
             cfg.num_envs, cfg.seed0, cfg.is_discrete, cfg.action_joints = n, 31, 0, 1

@@ -65,17 +65,48 @@ def test_ee_target_matches_reference_none_steps(golden_dir):
 
 
 # ---- 2. draw accounting --------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("joints", [0, 1])
-def test_none_rows_draw_nothing(joints):
+# The lumped forms launch the RNG_HOST arms of the lumped-gripper kernels, which nothing else does: the lane-per-env kernel (one and two
+# buttons: reset and the single-step launch), the lane-group kernel of the baked model, and the one of a runtime model table (reset and
+# rollout; the table installed is the baked model's own) — n = 5, T = 3: a tail group of the wavefront shadows env 4.
+LUMPED_FORMS = [pytest.param(j, f, id="{}-{}".format(j, f), marks=pytest.mark.lumped_kuka)
+                for f in ("lumped_lane", "lumped_group", "lumped_table") for j in (0, 1)] + \
+               [pytest.param(0, "lumped_two", id="0-lumped_two", marks=pytest.mark.lumped_kuka)]
+
+
+@pytest.mark.parametrize("joints,form", [pytest.param(0, "full", id="0"), pytest.param(1, "full", id="1")] + LUMPED_FORMS)
+def test_none_rows_draw_nothing(joints, form, monkeypatch):
     from oracle import gym_seeding
-    n, T, adim = 64, 520, 7 if joints else 3
-    acts, none = none_actions(T, n, adim, 31 + joints)
-    a = make(n=n, auto_reset=0, seed0=200, action_joints=joints)
-    b = make(n=n, auto_reset=0, rng_mode=_lib.RNG_HOST, action_joints=joints)
+    adim = 7 if joints else 3
+    kind, kw, lead = _lib.ENV_KUKA_BUTTON, {}, 0
+    if form == "full":
+        n, T = 64, 520
+        acts, none = none_actions(T, n, adim, 31 + joints)
+    else:
+        n, T = 5, 3
+        acts = np.random.RandomState(31 + joints).uniform(-1, 1, size=(T, n, adim)).astype(np.float32)
+        none = np.zeros((T, n), bool)
+        none[0] = True
+        none[1, 2] = True
+        acts[none] = np.nan
+        kw = dict(kuka_model=_lib.KUKA_MODEL_LUMPED)
+        monkeypatch.setenv("SRLHIP_KUKA_KERNEL", "lane" if form in ("lumped_lane", "lumped_two") else "group")
+        if form == "lumped_two":
+            kind, lead = _lib.ENV_KUKA_2BUTTON, 2          # kuka_2button_gym_env.py:55-70: two uniform draws in front of the init actions
+    a = make(kind, n=n, auto_reset=0, seed0=200, action_joints=joints, **kw)
+    b = make(kind, n=n, auto_reset=0, rng_mode=_lib.RNG_HOST, action_joints=joints, **kw)
+    if form == "lumped_table":
+        from oracle import kuka_clib
+        from srlhip import kuka_model
+        for h in (a, b):
+            h.set_kuka_model(kuka_model.to_table(kuka_clib.get_model()))
+    if form != "full":
+        assert a.kuka_kernel() == b.kuka_kernel() == ("lane" if form in ("lumped_lane", "lumped_two") else "group")
     rngs = [gym_seeding.np_random(200 + i)[0] for i in range(n)]
     rand = np.zeros((n, b.reset_rand_count))
+    assert b.reset_rand_count == lead + 5
     for i, r in enumerate(rngs):
-        rand[i, :5] = [float(r.normal((7,) if joints else (3,))[0]) for _ in range(5)]
+        rand[i, :lead] = [r.uniform(-1, 1) for _ in range(lead)]
+        rand[i, lead:lead + 5] = [float(r.normal((7,) if joints else (3,))[0]) for _ in range(5)]
     assert np.array_equal(a.reset(), b.reset(host_rand=rand))
     std = NOISE_STD_JOINTS if joints else NOISE_STD_CONTINUOUS
     for t in range(T):
@@ -195,21 +226,31 @@ def test_occ_kernel_agrees(env_kind, monkeypatch):
     assert np.abs(qs[0] - qs[1]).max() <= 1e-11
 
 
+# The short forms launch the lane-group instantiations that no other test does — actions drawn on the device (GIVEN = false), and the
+# kernels of a runtime model table (CM = true; the table installed is the baked model's own, so the lane kernel stays the reference) —
+# on n = 5, T = 3: one full wavefront plus a tail group that shadows env 4.
 @pytest.mark.lumped_kuka
-@pytest.mark.parametrize("joints", [0, 1])
-def test_lumped_lane_and_group_kernels_agree(joints, monkeypatch):
-    n, T, adim = 128, 300, 7 if joints else 3
-    acts, _ = none_actions(T, n, adim, 9)
+@pytest.mark.parametrize("joints,form", [pytest.param(0, "given", id="0"), pytest.param(1, "given", id="1")] +
+                         [pytest.param(j, f, id="{}-{}".format(j, f)) for j in (0, 1) for f in ("drawn", "table_given", "table_drawn")])
+def test_lumped_lane_and_group_kernels_agree(joints, form, monkeypatch):
+    from srlhip import kuka_model
+    n, T, adim = (128, 300, 7 if joints else 3) if form == "given" else (5, 3, 7 if joints else 3)
+    acts = none_actions(T, n, adim, 9)[0] if form == "given" else np.random.RandomState(9).uniform(-1, 1, size=(T, n, adim)).astype(np.float32)
     outs, qs = [], []
     for kernel in ("lane", "group"):
         monkeypatch.setenv("SRLHIP_KUKA_KERNEL", kernel)
         h = make(n=n, seed0=4, action_joints=joints, kuka_model=_lib.KUKA_MODEL_LUMPED)
+        if kernel == "group" and form.startswith("table"):
+            from oracle import kuka_clib
+            h.set_kuka_model(kuka_model.to_table(kuka_clib.get_model()))
         assert h.kuka_kernel() == kernel
         h.reset()
-        outs.append(h.rollout(T, actions=acts))
+        outs.append(h.rollout(T, actions=None if form.endswith("drawn") else acts))
         qs.append(h.get_state(_lib.F_KUKA_Q))
         h.close()
     assert np.array_equal(outs[0]["done"], outs[1]["done"]) and np.array_equal(outs[0]["reward"], outs[1]["reward"])
+    if form.endswith("drawn"):
+        assert np.array_equal(outs[0]["actions"], outs[1]["actions"])
     assert np.abs(qs[0] - qs[1]).max() <= 1e-11
 
 

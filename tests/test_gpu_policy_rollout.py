@@ -247,6 +247,7 @@ KUKA_CASES = [
     ("KUKA_2BUTTON", 1, 0, "MT19937", 7, 64, 1, 0, 0, 0),
     ("KUKA_BUTTON", 1, 0, "PHILOX", 16, 1100, 1, 0, 1, 1),
     ("KUKA_BUTTON", 0, 0, "MT19937", 7, 1100, 1, 0, 1, 0),          # continuous freeze: the all-NaN `None` rows
+    ("KUKA_2BUTTON", 1, 0, "PHILOX", 5, 3, 1, 0, 0, 0),             # the linear policy's two-button kernel on the Philox streams: no other case launches it
 ]
 
 
