@@ -52,6 +52,7 @@
 
 #include "../../include/srlhip.h"
 #include "encoder_general.hpp"
+#include "internal.hpp"
 
 #ifndef ENC_X
 #define ENC_X 0          // experiment builds (profiles/probes/encoder_experiments.sh); 0 = the product
@@ -73,10 +74,8 @@ constexpr unsigned kMaskByte = (unsigned)srlenc::kMaskI8 << 24;   // the validit
 constexpr int kIntNegInf = -2147483647 - 1;   // max-pool padding on combined int32 sums (|sum| <= 9.4e8)
 constexpr int kS2 = 36;                 // layers 2/3:      K = 9 taps x 64 channels = 576
 constexpr int kB2Ahead = 6;             // layer-2 B fragments are requested this many k-steps before their MFMAs
-constexpr float kWeightTop = 16384.f;   // packer: largest |weight| of a layer after its power-of-two pre-scale
 constexpr float kF16Max = 65504.f;
 constexpr float kNegInf = -3.0e38f;     // max-pool padding on raw (pre-ReLU) accumulators
-constexpr float kMean[3] = {0.485f, 0.456f, 0.406f}, kStd[3] = {0.229f, 0.224f, 0.225f};
 
 // ---- LDS map (bytes) -------------------------------------------------------------------------------
 constexpr int kMaxGroups = 4;                    // wave groups along M: 2 (4 waves, one per SIMD) or 4 (8 waves, two per SIMD)
@@ -95,10 +94,6 @@ constexpr int LDS_TOTAL = RAW + kImg * kImg * 3;
 constexpr int PART = A2H;                        // [groups-1][2][8][64] f32 layer-3 partial sums of K parts 1.. (A2 is dead by then)
 static_assert(IN_BYTES % 16 == 0 && A2_PLANE % 16 == 0 && A3_PLANE % 16 == 0, "LDS planes must stay 16-byte aligned");
 static_assert(LDS_TOTAL <= 160 * 1024, "encoder LDS map exceeds one CU");
-
-constexpr size_t kPack1Bytes = 2 * kS1 * 64 * 32, kPack2Bytes = 2 * kS2 * 64 * 32;
-constexpr size_t kPack1iBytes = 2 * kS1i * kDigits * 64 * 16;      // [n-half][k-step][digit][lane][16 i8]
-constexpr int kDefaultGroups = 2;
 
 struct EncParams {
     const uint8_t *images;      // [n][64][64][3]
@@ -880,137 +875,22 @@ __global__ __launch_bounds__(128 * MG, 1) void encoder_fwd_k(EncParams P) {
 #undef ENC_STAMP
 
 // ---------------------------------------------------------------------------------------------- host side
-using srlenc::pack_layer3x3;
-using srlenc::pick_scale;
-using srlenc::split_f16;
-double layer1_weight(const float *w, const float *b, int o, int k) {
-    const int ky = k / 32, kx = (k % 32) / 4, c4 = k % 4;
-    double v = 0.0;
-    if (kx < 7) {
-        if (c4 < 3) {
-            v = (double)w[((o * 3 + c4) * 7 + kx) * 7 + ky] / (255.0 * (double)kStd[c4]);
-        } else {
-            for (int c = 0; c < 3; c++) v -= (double)w[((o * 3 + c) * 7 + kx) * 7 + ky] * (double)kMean[c] / (double)kStd[c];
-            if (ky == 3 && kx == 3) v += (double)b[o];
-        }
-    }
-    return v;
-}
-
-// conv1_w [64][3][7][7] (torch OIHW, BatchNorm folded), conv1_b [64].  The network sees the frame with its two
-// spatial axes swapped (models.py:185-188), so the tap at frame offset (ky, kx) is torch's w[o][c][kx][ky].
-float pack_layer1(const float *w, const float *b, _Float16 *out) {
-    double wmax = 0.0;
-    for (int o = 0; o < 64; o++)
-        for (int k = 0; k < 16 * kS1; k++) wmax = fmax(wmax, fabs(layer1_weight(w, b, o, k)));
-    const float scale = pick_scale(wmax);
-    for (int nh = 0; nh < 2; nh++)
-        for (int s = 0; s < kS1; s++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int e = 0; e < 8; e++) {
-                    const int o = 32 * nh + (lane & 31), k = 16 * s + 8 * (lane >> 5) + e;
-                    _Float16 *dst = out + ((size_t)(nh * kS1 + s) * 64 + lane) * 16;
-                    split_f16((float)(layer1_weight(w, b, o, k) * (double)scale), dst[e], dst[8 + e]);
-                }
-    return scale;
-}
+// Shapes, packers, the float block's layout and the choice of instantiation: encoder_pack.hpp (plain C++, checked on the CPU).
+static_assert(kS1 == srlenc::layer1_steps(3) && kS2 == srlenc::kSteps3x3, "the kernel's k-steps are the packers'");
 }  // namespace
 
-namespace srlenc {
-// int8 layer 1 (3-channel frames): the folded taps around p - 128.  k = ky * 32 + slot * 4 + c4; ONE of the eight pixel slots of a kernel
-// row carries zero weights — slot 0 in the fused kernel (the fragment of output pixel j starts at input pixel 2 j - 4, 16-byte aligned
-// quads), slot 7 in the layered kernels (the fragment starts at the window column of tap 0); c4 < 3: w / (255 std_c) (multiplies
-// p - 128); c4 = 3, the validity mask (byte value 127 inside the frame, 0 outside): [sum_c w_c (128 / 255 - mean_c) / std_c — zero
-// padding stays exact in NORMALISED space — plus the folded BN bias on the centre tap] / 127.
-static double layer1_weight_i8(const float *w, const float *b, int zero_slot, int o, int k) {
-    constexpr float kMean[3] = {0.485f, 0.456f, 0.406f}, kStd[3] = {0.229f, 0.224f, 0.225f};
-    const int ky = k / 32, slot = (k % 32) / 4, c4 = k % 4, kx = zero_slot == 0 ? slot - 1 : slot;
-    double v = 0.0;
-    if (slot != zero_slot) {
-        if (c4 < 3) {
-            v = (double)w[((o * 3 + c4) * 7 + kx) * 7 + ky] / (255.0 * (double)kStd[c4]);
-        } else {
-            for (int c = 0; c < 3; c++) v += (double)w[((o * 3 + c) * 7 + kx) * 7 + ky] * (128.0 / 255.0 - (double)kMean[c]) / (double)kStd[c];
-            if (ky == 3 && kx == 3) v += (double)b[o];
-            v /= (double)kMaskI8;
-        }
-    }
-    return v;
-}
-// out: [n-half][k-step][digit][lane][16 i8], digit 0 = most significant; inv256[o] = 256 / scale_o, scale_o = the largest power of two
-// with max_k |w| scale_o <= kWeightTopI8: weight = (65536 d0 + 256 d1 + d2) / scale_o with balanced digits in [-128, 127].
-void pack_layer1_i8(const float *w, const float *b, int zero_slot, int8_t *out, float *inv256) {
-    for (int o = 0; o < 64; o++) {
-        double wmax = 0.0;
-        for (int k = 0; k < 32 * kI8Steps; k++) wmax = fmax(wmax, fabs(layer1_weight_i8(w, b, zero_slot, o, k)));
-        int e = 0;
-        if (wmax > 0.0 && std::isfinite(wmax)) {
-            frexp((double)kWeightTopI8 / wmax, &e);      // kWeightTopI8 / wmax = f * 2^e, f in [0.5, 1)
-            e = e - 1 > 60 ? 60 : (e - 1 < -60 ? -60 : e - 1);
-        }
-        const double scale = ldexp(1.0, e);
-        inv256[o] = (float)(256.0 / scale);
-        const int nh = o >> 5;
-        for (int k = 0; k < 32 * kI8Steps; k++) {
-            long long z = llround(layer1_weight_i8(w, b, zero_slot, o, k) * scale);
-            if (z > kWeightTopI8) z = kWeightTopI8;
-            if (z < -kWeightTopI8) z = -kWeightTopI8;
-            int dg[kI8Digits];
-            for (int d = kI8Digits - 1; d >= 0; d--) {          // least significant first
-                long long r = ((z + 128) % 256 + 256) % 256 - 128;
-                dg[d] = (int)r;
-                z = (z - r) / 256;
-            }
-            const int s = k / 32, hh = (k % 32) / 16, el = k % 16, lane = hh * 32 + (o & 31);
-            for (int d = 0; d < kI8Digits; d++)
-                out[((size_t)((nh * kI8Steps + s) * kI8Digits + d) * 64 + lane) * 16 + el] = (int8_t)dg[d];
-        }
-    }
-}
-
-void split_f16(float v, _Float16 &hi, _Float16 &lo) {
-    hi = (_Float16)v;
-    lo = (_Float16)(v - (float)hi);
-}
-// largest power of two that keeps max|w| * scale <= kWeightTop (lo parts then sit well inside f16's normal range)
-float pick_scale(double wmax) {
-    if (!(wmax > 0.0) || !std::isfinite(wmax)) return 1.f;
-    int e;
-    frexp((double)kWeightTop / wmax, &e);          // kWeightTop / wmax = f * 2^e, f in [0.5, 1)
-    e = e - 1 > 40 ? 40 : (e - 1 < -40 ? -40 : e - 1);
-    return (float)ldexp(1.0, e);
-}
-// conv_w [64][64][3][3] (torch OIHW, BatchNorm folded): k = (ky * 3 + kx) * 64 + c
-float pack_layer3x3(const float *w, _Float16 *out) {
-    double wmax = 0.0;
-    for (int i = 0; i < 64 * 64 * 9; i++) wmax = fmax(wmax, fabs((double)w[i]));
-    const float scale = pick_scale(wmax);
-    for (int nh = 0; nh < 2; nh++)
-        for (int s = 0; s < kS2; s++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int e = 0; e < 8; e++) {
-                    const int o = 32 * nh + (lane & 31), k = 16 * s + 8 * (lane >> 5) + e;
-                    const int tap = k / 64, c = k % 64, ky = tap / 3, kx = tap % 3;
-                    _Float16 *dst = out + ((size_t)(nh * kS2 + s) * 64 + lane) * 16;
-                    split_f16(w[((o * 64 + c) * 3 + kx) * 3 + ky] * scale, dst[e], dst[8 + e]);
-                }
-    return scale;
-}
-
-}  // namespace srlenc
-
 struct srlhip_encoder {
-    int device_id, state_dim;
-    char *d_pack;          // b1 | b2 | b3
-    float *d_f32;          // inv_scale[3] pad bias2[64] bias3[64] fcw[state_dim][64] fcb[state_dim]
-    int *d_status;
-    int num_cus;
-    int groups;            // wave groups along M: 2 = 4 waves per workgroup, 4 = 8 waves
-    int l1_i8;             // layer 1 on the int8 matrix pipe (default with groups == 2); SRLHIP_ENCODER_L1=f16 keeps the split-f16 form
-    char *d_pack_i8;       // int8 layer-1 digits
-    float *d_inv1c;        // [64] per-channel 256 / scale
-    srlenc::General *general;   // non-null: the layered path of encoder_general.hip serves this handle (any shape but 64x64x3)
-    int img_h, img_w, n_channels;
+    int device_id = 0, state_dim = 0;
+    char *d_pack = nullptr;          // b1 | b2 | b3
+    float *d_f32 = nullptr;          // srlenc::kF32*: inv_scale[3] pad bias2[64] bias3[64] fcw[state_dim][64] fcb[state_dim]
+    int *d_status = nullptr;
+    int num_cus = 0;
+    int groups = 2;                  // wave groups along M: 2 = 4 waves per workgroup, 4 = 8 waves
+    int l1_i8 = 0;                   // layer 1 on the int8 matrix pipe (default with groups == 2); SRLHIP_ENCODER_L1=f16 keeps the split-f16 form
+    char *d_pack_i8 = nullptr;       // int8 layer-1 digits
+    float *d_inv1c = nullptr;        // [64] per-channel 256 / scale
+    srlenc::General *general = nullptr;   // non-null: the layered path of encoder_general.hip serves this handle (any shape but 64x64x3)
+    int img_h = 0, img_w = 0, n_channels = 0;
     std::string err;
     int fail(int code, const std::string &m) { err = m; return code; }
 };
@@ -1022,43 +902,127 @@ bool fused_shape(int img_h, int img_w, int n_channels) {
     const char *g = getenv("SRLHIP_ENCODER_GENERAL");          // test knob: run 64x64x3 through the layered path too
     return img_h == kImg && img_w == kImg && n_channels == 3 && !(g && atoi(g) == 1);
 }
-bool supported_shape(int img_h, int img_w, int n_channels) { return srlenc::geometry(img_h, img_w, n_channels).ok; }
+
+// The (MG, I8) instantiations of encoder_fwd_k, written once: f(Const<MG>, Const<I8>) for entry v of srlenc::kFusedVariants; returns
+// f's SRLHIP code, SRLHIP_ENOTSUP for a v outside the table.  (The arms last first: the compiler emits the kernels in the reverse of the
+// order it meets them here, and table order is the order they have always had in the code object.)
+template <class F>
+int fused_dispatch(int v, F &&f) {
+    int rc = SRLHIP_ENOTSUP;
+    srl::dispatch_int<2, 1, 0>(v, [&](auto V) {
+        constexpr srlenc::FusedVariant k = srlenc::kFusedVariants[decltype(V)::value];
+        rc = f(srl::Const<k.groups>{}, srl::Const<k.l1_i8>{});
+    });
+    return rc;
+}
+
+EncParams fused_params(const srlhip_encoder *e, const uint8_t *images_dev, int n, float *states_dev, long long *prof) {
+    EncParams p;
+    p.images = images_dev; p.n = n;
+    p.b1 = e->d_pack; p.b2 = p.b1 + srlenc::layer1_bytes(3); p.b3 = p.b2 + srlenc::kPack3x3Bytes;
+    p.b1i = e->d_pack_i8; p.inv1c = e->d_inv1c;
+    p.inv_scale = e->d_f32 + srlenc::kF32InvScale; p.bias2 = e->d_f32 + srlenc::kF32Bias2; p.bias3 = e->d_f32 + srlenc::kF32Bias3;
+    p.fcw = e->d_f32 + srlenc::kF32Fcw; p.fcb = e->d_f32 + srlenc::f32_fcb(e->state_dim);
+    p.state_dim = e->state_dim; p.out = states_dev; p.status = e->d_status; p.prof = prof;
+    return p;
+}
+
+// one workgroup per CU (at most one per frame) of the handle's instantiation; prof: the stamp buffer of the PROF form
+template <bool PROF>
+int fused_launch(const srlhip_encoder *e, const uint8_t *images_dev, int n, float *states_dev, long long *prof, hipStream_t stream) {
+    const EncParams p = fused_params(e, images_dev, n, states_dev, prof);
+    const int grid = n < e->num_cus ? n : e->num_cus;
+    return fused_dispatch(srlenc::fused_variant(e->groups, e->l1_i8 != 0), [&](auto MG, auto I8) {
+        hipLaunchKernelGGL((encoder_fwd_k<PROF, decltype(MG)::value, decltype(I8)::value != 0>), dim3(grid), dim3(128 * decltype(MG)::value), LDS_TOTAL, stream, p);
+        return SRLHIP_OK;
+    });
+}
+
+// the fused 64x64x3 path of srlhip_encoder_create: pack, upload, allow every instantiation its LDS, read the two experiment knobs
+int fused_create(srlhip_encoder *e, const float *conv1_w, const float *conv1_b, const float *conv2_w, const float *conv2_b, const float *conv3_w,
+                 const float *conv3_b, const float *fc_w, const float *fc_b, std::string &err) {
+    if (!conv1_w || !conv1_b || !conv2_w || !conv3_w) { err = "srlhip_encoder_create: null weight pointer"; return SRLHIP_EINVAL; }
+    const int device_id = e->device_id, state_dim = e->state_dim;
+    std::vector<char> pack(srlenc::kPackFusedBytes);
+    float scales[3];
+    srlenc::pack_fused(conv1_w, conv1_b, conv2_w, conv3_w, pack.data(), scales);
+    std::vector<int8_t> pack_i8(srlenc::kPackI8Bytes);
+    float inv1c[64];
+    srlenc::pack_layer1_i8(conv1_w, conv1_b, 0, pack_i8.data(), inv1c);
+    const size_t nf = srlenc::f32_count(state_dim);
+    std::vector<float> f(nf);
+    for (int i = 0; i < 3; i++) f[srlenc::kF32InvScale + i] = 1.f / scales[i];      // powers of two: exact
+    memcpy(f.data() + srlenc::kF32Bias2, conv2_b, 64 * sizeof(float));
+    memcpy(f.data() + srlenc::kF32Bias3, conv3_b, 64 * sizeof(float));
+    memcpy(f.data() + srlenc::kF32Fcw, fc_w, (size_t)state_dim * kCh * sizeof(float));
+    memcpy(f.data() + srlenc::f32_fcb(state_dim), fc_b, state_dim * sizeof(float));
+    ENC_HIP(err, hipSetDevice(device_id));
+    hipDeviceProp_t prop;
+    ENC_HIP(err, hipGetDeviceProperties(&prop, device_id));
+    e->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    ENC_HIP(err, hipMalloc(reinterpret_cast<void **>(&e->d_pack), pack.size()));
+    ENC_HIP(err, hipMalloc(reinterpret_cast<void **>(&e->d_f32), nf * sizeof(float)));
+    ENC_HIP(err, hipMalloc(reinterpret_cast<void **>(&e->d_status), sizeof(int)));
+    ENC_HIP(err, hipMemcpy(e->d_pack, pack.data(), pack.size(), hipMemcpyHostToDevice));
+    ENC_HIP(err, hipMemcpy(e->d_f32, f.data(), nf * sizeof(float), hipMemcpyHostToDevice));
+    ENC_HIP(err, hipMemset(e->d_status, 0, sizeof(int)));
+    ENC_HIP(err, hipMalloc(reinterpret_cast<void **>(&e->d_pack_i8), pack_i8.size()));
+    ENC_HIP(err, hipMalloc(reinterpret_cast<void **>(&e->d_inv1c), sizeof inv1c));
+    ENC_HIP(err, hipMemcpy(e->d_pack_i8, pack_i8.data(), pack_i8.size(), hipMemcpyHostToDevice));
+    ENC_HIP(err, hipMemcpy(e->d_inv1c, inv1c, sizeof inv1c, hipMemcpyHostToDevice));
+    for (int v = 0; v < 3; v++) {
+        const int rc = fused_dispatch(v, [&](auto MG, auto I8) {
+            ENC_HIP(err, hipFuncSetAttribute(reinterpret_cast<const void *>(encoder_fwd_k<false, decltype(MG)::value, decltype(I8)::value != 0>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL));
+            ENC_HIP(err, hipFuncSetAttribute(reinterpret_cast<const void *>(encoder_fwd_k<true, decltype(MG)::value, decltype(I8)::value != 0>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL));
+            return SRLHIP_OK;
+        });
+        if (rc != SRLHIP_OK) return rc;
+    }
+    const char *w = getenv("SRLHIP_ENCODER_WAVES");       // experiment knob: 4 (one wave per SIMD) or 8 (two)
+    const char *l1 = getenv("SRLHIP_ENCODER_L1");         // experiment knob: f16 = the split-f16 layer 1 of rounds 2-5
+    e->groups = srlenc::fused_groups(w ? atoi(w) : 0);
+    e->l1_i8 = srlenc::fused_l1_i8(e->groups, l1 && strcmp(l1, "f16") == 0);
+    return SRLHIP_OK;
+}
+
+// freed on every way out of srlhip_encoder_phase_cycles
+struct ProfWords {
+    long long *d = nullptr;
+    ~ProfWords() { if (d) (void)hipFree(d); }
+};
 }  // namespace
 
 extern "C" {
 
-size_t srlhip_encoder_pack_bytes(void) { return kPack1Bytes + 2 * kPack2Bytes; }
+size_t srlhip_encoder_pack_bytes(void) { return srlenc::kPackFusedBytes; }
 
-size_t srlhip_encoder_pack_i8_bytes(void) { return kPack1iBytes; }
+size_t srlhip_encoder_pack_i8_bytes(void) { return srlenc::kPackI8Bytes; }
 
 int srlhip_encoder_pack_i8(const float *conv1_w, const float *conv1_b, int32_t zero_slot, void *out, size_t out_bytes, float *inv_scale64) {
-    if (!conv1_w || !conv1_b || !out || !inv_scale64 || out_bytes < kPack1iBytes || (zero_slot != 0 && zero_slot != 7)) return SRLHIP_EINVAL;
+    if (!conv1_w || !conv1_b || !out || !inv_scale64 || out_bytes < srlenc::kPackI8Bytes || (zero_slot != 0 && zero_slot != 7)) return SRLHIP_EINVAL;
     srlenc::pack_layer1_i8(conv1_w, conv1_b, zero_slot, static_cast<int8_t *>(out), inv_scale64);
     return SRLHIP_OK;
 }
 
 int srlhip_encoder_pack(const float *conv1_w, const float *conv1_b, const float *conv2_w, const float *conv3_w,
                         void *out, size_t out_bytes, float *scales3) {
-    if (!conv1_w || !conv1_b || !conv2_w || !conv3_w || !out || !scales3 || out_bytes < srlhip_encoder_pack_bytes())
-        return SRLHIP_EINVAL;
-    char *p = static_cast<char *>(out);
-    scales3[0] = pack_layer1(conv1_w, conv1_b, reinterpret_cast<_Float16 *>(p));
-    scales3[1] = pack_layer3x3(conv2_w, reinterpret_cast<_Float16 *>(p + kPack1Bytes));
-    scales3[2] = pack_layer3x3(conv3_w, reinterpret_cast<_Float16 *>(p + kPack1Bytes + kPack2Bytes));
+    if (!conv1_w || !conv1_b || !conv2_w || !conv3_w || !out || !scales3 || out_bytes < srlenc::kPackFusedBytes) return SRLHIP_EINVAL;
+    srlenc::pack_fused(conv1_w, conv1_b, conv2_w, conv3_w, static_cast<char *>(out), scales3);
     return SRLHIP_OK;
 }
 
 int srlhip_encoder_pack_first_layer(int32_t n_channels, const float *conv1_w, const float *conv1_b, void *out, size_t out_bytes, float *scale) {
     if (!scale) return SRLHIP_EINVAL;
-    *scale = srlenc::pack_layer1_general(conv1_w, conv1_b, n_channels, out, out_bytes);
-    return *scale > 0.f ? SRLHIP_OK : SRLHIP_EINVAL;
+    *scale = 0.f;
+    if (!conv1_w || !conv1_b || !out || (n_channels != 3 && n_channels != 6) || out_bytes < srlenc::layer1_bytes(n_channels)) return SRLHIP_EINVAL;
+    *scale = srlenc::pack_layer1_f16(conv1_w, conv1_b, n_channels, static_cast<_Float16 *>(out));
+    return SRLHIP_OK;
 }
 
-int srlhip_encoder_supported(int32_t img_h, int32_t img_w, int32_t n_channels) { return supported_shape(img_h, img_w, n_channels) ? 1 : 0; }
+int srlhip_encoder_supported(int32_t img_h, int32_t img_w, int32_t n_channels) { return srlenc::geometry(img_h, img_w, n_channels).ok ? 1 : 0; }
 
 int32_t srlhip_encoder_feature_count(int32_t img_h, int32_t img_w, int32_t n_channels) {
-    const srlenc::Geometry g = srlenc::geometry(img_h, img_w, n_channels);
-    return g.ok ? 64 * g.Hp[2] * g.Wp[2] : 0;
+    return srlenc::feature_count(srlenc::geometry(img_h, img_w, n_channels));
 }
 
 int srlhip_encoder_create(int32_t device_id, int32_t img_h, int32_t img_w, int32_t n_channels, int32_t state_dim,
@@ -1067,78 +1031,19 @@ int srlhip_encoder_create(int32_t device_id, int32_t img_h, int32_t img_w, int32
                           srlhip_encoder_handle *out) {
     if (!out) return SRLHIP_EINVAL;
     *out = nullptr;
-    if (!supported_shape(img_h, img_w, n_channels) || state_dim < 1 || !conv2_b || !conv3_b || !fc_w || !fc_b) {
+    const srlenc::Geometry geo = srlenc::geometry(img_h, img_w, n_channels);
+    if (!geo.ok || state_dim < 1 || !conv2_b || !conv3_b || !fc_w || !fc_b) {
         g_enc_create_error = "srlhip_encoder_create: CustomCNN frames are 8..1024 pixels a side with 3 or 6 channels, state_dim >= 1";
         return SRLHIP_ENOTSUP;
     }
-    if (!fused_shape(img_h, img_w, n_channels)) {
-        srlhip_encoder *e = new (std::nothrow) srlhip_encoder();
-        if (!e) return SRLHIP_ENOMEM;
-        e->device_id = device_id; e->state_dim = state_dim; e->d_pack = nullptr; e->d_f32 = nullptr; e->d_status = nullptr; e->general = nullptr;
-        e->img_h = img_h; e->img_w = img_w; e->n_channels = n_channels; e->d_pack_i8 = nullptr; e->d_inv1c = nullptr; e->l1_i8 = 0;
-        const int rc = srlenc::general_create(device_id, srlenc::geometry(img_h, img_w, n_channels), state_dim, conv1_w, conv1_b, conv2_w, conv2_b,
-                                              conv3_w, conv3_b, fc_w, fc_b, &e->general, g_enc_create_error);
-        if (rc != SRLHIP_OK) { delete e; return rc; }
-        *out = e;
-        return SRLHIP_OK;
-    }
-    std::vector<char> pack(srlhip_encoder_pack_bytes());
-    float scales[3];
-    if (srlhip_encoder_pack(conv1_w, conv1_b, conv2_w, conv3_w, pack.data(), pack.size(), scales) != SRLHIP_OK) {
-        g_enc_create_error = "srlhip_encoder_create: null weight pointer";
-        return SRLHIP_EINVAL;
-    }
     srlhip_encoder *e = new (std::nothrow) srlhip_encoder();
     if (!e) return SRLHIP_ENOMEM;
-    e->device_id = device_id; e->state_dim = state_dim; e->d_pack = nullptr; e->d_f32 = nullptr; e->d_status = nullptr; e->general = nullptr;
-    e->img_h = img_h; e->img_w = img_w; e->n_channels = n_channels; e->d_pack_i8 = nullptr; e->d_inv1c = nullptr; e->l1_i8 = 0;
-    std::vector<int8_t> pack_i8(kPack1iBytes);
-    float inv1c[64];
-    srlenc::pack_layer1_i8(conv1_w, conv1_b, 0, pack_i8.data(), inv1c);
-#define ENC_CHECK(expr)                                                                              \
-    do {                                                                                             \
-        hipError_t e__ = (expr);                                                                     \
-        if (e__ != hipSuccess) {                                                                     \
-            g_enc_create_error = std::string(#expr ": ") + hipGetErrorString(e__);                   \
-            srlhip_encoder_destroy(e);                                                               \
-            return SRLHIP_EHIP;                                                                      \
-        }                                                                                            \
-    } while (0)
-    ENC_CHECK(hipSetDevice(device_id));
-    hipDeviceProp_t prop;
-    ENC_CHECK(hipGetDeviceProperties(&prop, device_id));
-    e->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    const size_t nf = 132 + (size_t)state_dim * (1 + kCh);
-    std::vector<float> f(nf);
-    for (int i = 0; i < 3; i++) f[i] = 1.f / scales[i];      // powers of two: exact
-    f[3] = 0.f;
-    memcpy(f.data() + 4, conv2_b, 64 * sizeof(float));
-    memcpy(f.data() + 68, conv3_b, 64 * sizeof(float));
-    memcpy(f.data() + 132, fc_w, (size_t)state_dim * kCh * sizeof(float));        // 16-byte aligned rows (float4 loads)
-    memcpy(f.data() + 132 + (size_t)state_dim * kCh, fc_b, state_dim * sizeof(float));
-    ENC_CHECK(hipMalloc(reinterpret_cast<void **>(&e->d_pack), pack.size()));
-    ENC_CHECK(hipMalloc(reinterpret_cast<void **>(&e->d_f32), nf * sizeof(float)));
-    ENC_CHECK(hipMalloc(reinterpret_cast<void **>(&e->d_status), sizeof(int)));
-    ENC_CHECK(hipMemcpy(e->d_pack, pack.data(), pack.size(), hipMemcpyHostToDevice));
-    ENC_CHECK(hipMemcpy(e->d_f32, f.data(), nf * sizeof(float), hipMemcpyHostToDevice));
-    ENC_CHECK(hipMemset(e->d_status, 0, sizeof(int)));
-    ENC_CHECK(hipMalloc(reinterpret_cast<void **>(&e->d_pack_i8), kPack1iBytes));
-    ENC_CHECK(hipMalloc(reinterpret_cast<void **>(&e->d_inv1c), sizeof inv1c));
-    ENC_CHECK(hipMemcpy(e->d_pack_i8, pack_i8.data(), kPack1iBytes, hipMemcpyHostToDevice));
-    ENC_CHECK(hipMemcpy(e->d_inv1c, inv1c, sizeof inv1c, hipMemcpyHostToDevice));
-    ENC_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(encoder_fwd_k<false, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL));
-    ENC_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(encoder_fwd_k<true, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL));
-    ENC_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(encoder_fwd_k<false, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL));
-    ENC_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(encoder_fwd_k<true, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL));
-    ENC_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(encoder_fwd_k<false, 4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL));
-    ENC_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(encoder_fwd_k<true, 4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL));
-    {
-        const char *w = getenv("SRLHIP_ENCODER_WAVES");       // experiment knob: 4 (one wave per SIMD) or 8 (two)
-        e->groups = (w && atoi(w) == 4) ? 2 : (w && atoi(w) == 8) ? 4 : kDefaultGroups;
-        const char *l1 = getenv("SRLHIP_ENCODER_L1");         // experiment knob: f16 = the split-f16 layer 1 of rounds 2-5
-        e->l1_i8 = e->groups == 2 && !(l1 && strcmp(l1, "f16") == 0);
-    }
-#undef ENC_CHECK
+    e->device_id = device_id; e->state_dim = state_dim; e->img_h = img_h; e->img_w = img_w; e->n_channels = n_channels;
+    const int rc = fused_shape(img_h, img_w, n_channels)
+                       ? fused_create(e, conv1_w, conv1_b, conv2_w, conv2_b, conv3_w, conv3_b, fc_w, fc_b, g_enc_create_error)
+                       : srlenc::general_create(device_id, geo, state_dim, conv1_w, conv1_b, conv2_w, conv2_b, conv3_w, conv3_b, fc_w, fc_b, &e->general,
+                                                g_enc_create_error);
+    if (rc != SRLHIP_OK) { srlhip_encoder_destroy(e); return rc; }      // whatever the path had built so far
     *out = e;
     return SRLHIP_OK;
 }
@@ -1151,17 +1056,8 @@ int srlhip_encoder_forward(srlhip_encoder_handle e, const uint8_t *images_dev, i
     hipError_t rc = hipSetDevice(e->device_id);
     if (rc != hipSuccess) return e->fail(SRLHIP_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(rc));
     if (e->general) return srlenc::general_forward(e->general, images_dev, n, states_dev, static_cast<hipStream_t>(hip_stream), e->err);
-    EncParams p;
-    p.images = images_dev; p.n = n;
-    p.b1 = e->d_pack; p.b2 = e->d_pack + kPack1Bytes; p.b3 = e->d_pack + kPack1Bytes + kPack2Bytes;
-    p.inv_scale = e->d_f32; p.bias2 = e->d_f32 + 4; p.bias3 = e->d_f32 + 68; p.fcw = e->d_f32 + 132;
-    p.fcb = e->d_f32 + 132 + (size_t)e->state_dim * kCh;
-    p.state_dim = e->state_dim; p.out = states_dev; p.status = e->d_status; p.prof = nullptr;
-    p.b1i = e->d_pack_i8; p.inv1c = e->d_inv1c;
-    const int grid = n < e->num_cus ? n : e->num_cus;
-    if (e->groups == 2 && e->l1_i8) hipLaunchKernelGGL((encoder_fwd_k<false, 2, true>), dim3(grid), dim3(256), LDS_TOTAL, static_cast<hipStream_t>(hip_stream), p);
-    else if (e->groups == 2) hipLaunchKernelGGL((encoder_fwd_k<false, 2, false>), dim3(grid), dim3(256), LDS_TOTAL, static_cast<hipStream_t>(hip_stream), p);
-    else hipLaunchKernelGGL((encoder_fwd_k<false, 4, false>), dim3(grid), dim3(512), LDS_TOTAL, static_cast<hipStream_t>(hip_stream), p);
+    const int launched = fused_launch<false>(e, images_dev, n, states_dev, nullptr, static_cast<hipStream_t>(hip_stream));
+    if (launched != SRLHIP_OK) return e->fail(launched, "encoder_fwd_k launch: no such instantiation");
     rc = hipGetLastError();
     if (rc != hipSuccess) return e->fail(SRLHIP_EHIP, std::string("encoder_fwd_k launch: ") + hipGetErrorString(rc));
     return SRLHIP_OK;
@@ -1172,34 +1068,19 @@ int srlhip_encoder_phase_cycles(srlhip_encoder_handle e, const uint8_t *images_d
     if (!e || !cycles9) return SRLHIP_EINVAL;
     if (n < 1 || !images_dev || !states_dev) return e->fail(SRLHIP_EINVAL, "srlhip_encoder_phase_cycles: need n >= 1 and both buffers");
     if (e->general) return e->fail(SRLHIP_ENOTSUP, "srlhip_encoder_phase_cycles: the phase stamps belong to the fused 64x64x3 kernel");
-#define ENC_RC(expr)                                                                                  \
-    do {                                                                                              \
-        hipError_t e__ = (expr);                                                                      \
-        if (e__ != hipSuccess) return e->fail(SRLHIP_EHIP, std::string(#expr ": ") + hipGetErrorString(e__)); \
-    } while (0)
-    ENC_RC(hipSetDevice(e->device_id));
+    ENC_HIP(e->err, hipSetDevice(e->device_id));
     const size_t words = (size_t)kProfFrames * kProfStamps * kProfWaves;
-    long long *d_prof = nullptr;
-    ENC_RC(hipMalloc(reinterpret_cast<void **>(&d_prof), words * sizeof(long long)));
-    ENC_RC(hipMemset(d_prof, 0, words * sizeof(long long)));
-    EncParams p;
-    p.images = images_dev; p.n = n;
-    p.b1 = e->d_pack; p.b2 = e->d_pack + kPack1Bytes; p.b3 = e->d_pack + kPack1Bytes + kPack2Bytes;
-    p.inv_scale = e->d_f32; p.bias2 = e->d_f32 + 4; p.bias3 = e->d_f32 + 68; p.fcw = e->d_f32 + 132;
-    p.fcb = e->d_f32 + 132 + (size_t)e->state_dim * kCh;
-    p.state_dim = e->state_dim; p.out = states_dev; p.status = e->d_status; p.prof = d_prof;
-    p.b1i = e->d_pack_i8; p.inv1c = e->d_inv1c;
-    const int grid = n < e->num_cus ? n : e->num_cus;
-    if (e->groups == 2 && e->l1_i8) hipLaunchKernelGGL((encoder_fwd_k<true, 2, true>), dim3(grid), dim3(256), LDS_TOTAL, nullptr, p);
-    else if (e->groups == 2) hipLaunchKernelGGL((encoder_fwd_k<true, 2, false>), dim3(grid), dim3(256), LDS_TOTAL, nullptr, p);
-    else hipLaunchKernelGGL((encoder_fwd_k<true, 4, false>), dim3(grid), dim3(512), LDS_TOTAL, nullptr, p);
-    ENC_RC(hipGetLastError());
+    ProfWords prof;
+    ENC_HIP(e->err, hipMalloc(reinterpret_cast<void **>(&prof.d), words * sizeof(long long)));
+    ENC_HIP(e->err, hipMemset(prof.d, 0, words * sizeof(long long)));
+    const int launched = fused_launch<true>(e, images_dev, n, states_dev, prof.d, nullptr);
+    if (launched != SRLHIP_OK) return e->fail(launched, "encoder_fwd_k launch: no such instantiation");
+    ENC_HIP(e->err, hipGetLastError());
     std::vector<long long> host(words);
-    ENC_RC(hipMemcpy(host.data(), d_prof, words * sizeof(long long), hipMemcpyDeviceToHost));
-    (void)hipFree(d_prof);
-#undef ENC_RC
+    ENC_HIP(e->err, hipMemcpy(host.data(), prof.d, words * sizeof(long long), hipMemcpyDeviceToHost));
     // segment k = stamp k -> stamp k+1 (the last one wraps to the next frame's stamp 0), slowest wave, averaged over
     // the frames workgroup 0 processed
+    const int grid = n < e->num_cus ? n : e->num_cus;
     const int frames = (n + grid - 1) / grid < kProfFrames ? (n - 1) / grid + 1 : kProfFrames;
     for (int k = 0; k < kProfStamps; k++) cycles9[k] = 0;
     int counted = 0;

@@ -27,30 +27,12 @@
 #include <new>
 #include <vector>
 
-#include "../../include/srlhip.h"
-
 #ifndef EG_X
 #define EG_X 0          // experiment builds (profiles/probes/encoder_general_experiments.sh): 1 = layers 2-3 without their MFMAs, 2 = without
 #endif                  // the pooling / band stores, 3 = without the window loads; 4 / 5 / 6 = layer 1 without its MFMAs / pooling and
                         // stores / pixel unpack.  Results are wrong by construction; 0 = the product.
 
 namespace srlenc {
-
-Geometry geometry(int img_h, int img_w, int n_channels) {
-    Geometry g;
-    g.H = img_h; g.W = img_w; g.C = n_channels;
-    int h = img_h, w = img_w;
-    const int k[3] = {7, 3, 3}, s[3] = {2, 1, 2}, pad[3] = {3, 1, 1}, ppad[3] = {1, 0, 0};
-    g.ok = (n_channels == 3 || n_channels == 6) && img_h >= 8 && img_w >= 8 && img_h <= 1024 && img_w <= 1024;
-    for (int l = 0; l < 3; l++) {
-        g.Hc[l] = (h + 2 * pad[l] - k[l]) / s[l] + 1; g.Wc[l] = (w + 2 * pad[l] - k[l]) / s[l] + 1;
-        g.Hp[l] = g.Hc[l] + 2 * ppad[l] >= 3 ? (g.Hc[l] + 2 * ppad[l] - 3) / 2 + 1 : 0;
-        g.Wp[l] = g.Wc[l] + 2 * ppad[l] >= 3 ? (g.Wc[l] + 2 * ppad[l] - 3) / 2 + 1 : 0;
-        if (g.Hp[l] < 1 || g.Wp[l] < 1) g.ok = false;
-        h = g.Hp[l]; w = g.Wp[l];
-    }
-    return g;
-}
 
 namespace {
 
@@ -63,7 +45,6 @@ typedef int i32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int PX = 144;                 // LDS pixel pitch of a 64-channel f16 plane (128 B + 16 B skew)
 constexpr float kF16Max = 65504.f, kNegInf = -3.0e38f;
-constexpr float kMean[3] = {0.485f, 0.456f, 0.406f}, kStd[3] = {0.229f, 0.224f, 0.225f};
 constexpr int kNC1 = 70, kNC2 = 34, kNC3 = 65;          // staged input columns of a 32-column convolution tile
 constexpr int kNC3Narrow = 33;                           // layer 3 when its map has at most 16 columns (224x224 frames: 14)
 constexpr int kLdsSlack3 = 2 * 32 * PX;                  // the masked columns of a narrow tile still read (finite garbage) behind the window
@@ -505,57 +486,35 @@ __global__ __launch_bounds__(256) void enc_fc_k(const float *feat, const float *
     }
 }
 
-// layer 1, normalisation folded: staged pixel = (c_0 .. c_{C-1}, mask [, 0]); k = (ky * 8 + kx) * CPIX + c with kx = 7 a zero slot.
-// The mask channel carries -sum_c w * mean_c / std_c per tap (zero padding stays exact in NORMALISED space) and the folded bias
-// on the centre tap.  The frame's axes are swapped with respect to torch's, so the tap at frame offset (ky, kx) is w[o][c][kx][ky].
-double layer1_weight(const float *w, const float *b, int C, int cpix, int o, int k) {
-    const int ky = k / (8 * cpix), kx = (k / cpix) % 8, c = k % cpix;
-    if (kx >= 7) return 0.0;
-    if (c < C) return (double)w[((o * C + c) * 7 + kx) * 7 + ky] / (255.0 * (double)kStd[c % 3]);
-    if (c > C) return 0.0;
-    double v = 0.0;
-    for (int cc = 0; cc < C; cc++) v -= (double)w[((o * C + cc) * 7 + kx) * 7 + ky] * (double)kMean[cc % 3] / (double)kStd[cc % 3];
-    if (ky == 3 && kx == 3) v += (double)b[o];
-    return v;
-}
-float pack_layer1(const float *w, const float *b, int C, _Float16 *out) {
-    const int cpix = C == 3 ? 4 : 8, ks = 7 * 8 * cpix / 16;
-    double wmax = 0.0;
-    for (int o = 0; o < 64; o++)
-        for (int k = 0; k < 16 * ks; k++) wmax = fmax(wmax, fabs(layer1_weight(w, b, C, cpix, o, k)));
-    const float scale = pick_scale(wmax);
-    for (int nh = 0; nh < 2; nh++)
-        for (int s = 0; s < ks; s++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int e = 0; e < 8; e++) {
-                    const int o = 32 * nh + (lane & 31), k = 16 * s + 8 * (lane >> 5) + e;
-                    _Float16 *dst = out + ((size_t)(nh * ks + s) * 64 + lane) * 16;
-                    split_f16((float)(layer1_weight(w, b, C, cpix, o, k) * (double)scale), dst[e], dst[8 + e]);
-                }
-    return scale;
-}
+// ---------------------------------------------------------------------------------------------- host side
+// Dynamic LDS of every launch form, in bytes: the value hipFuncSetAttribute allows is the value the launch asks for.  A pair's LDS is its
+// input window, or the pooled band of r rows x 15 columns (256 bytes per pixel) that replaces it before the stores.
+constexpr int lds_bytes(int window, int r) { return window > r * 15 * 256 ? window : r * 15 * 256; }
+constexpr int kLds1 = (int)layer1_bytes(3) + 2 * lds_bytes((2 * (2 * kR1) + 7) * kNC1 * 8, kR1);       // 3 channels: weights + two pairs
+constexpr int kLds1I8 = (int)kPackI8Bytes + 2 * lds_bytes((2 * (2 * kR1) + 7) * kNC1 * 4, kR1);        // ... as int8 digits and pixels
+constexpr int kLds1Allowed = 96 * 1024;                                                                // what both of them are allowed
+constexpr int kLds1x6 = lds_bytes((2 * (2 * kR1x6) + 7) * kNC1 * 16, kR1x6);                           // 6 channels: weights in registers
+constexpr int kLds2 = 2 * (kR2 * 2 + 3) * kNC2 * PX, kLds3 = 2 * (2 * (2 * kR3) + 3) * kNC3 * PX;      // hi + lo planes of the window
+constexpr int kLds3Narrow = 2 * (2 * (2 * kR3) + 3) * kNC3Narrow * PX + kLdsSlack3;
+static_assert(kLds1 <= kLds1Allowed && kLds1I8 <= kLds1Allowed, "the layer-1 launches ask for no more LDS than their attribute allows");
+static_assert(kLds1x6 <= 64 * 1024, "the 6-channel layer 1 sets no attribute: it stays under the default limit");
+
+constexpr size_t kF32Bias3G = 64, kF32FcbG = 128;      // d_f32 of the layered path: bias2[64] bias3[64] fcb[state_dim] fcw[state_dim][F]
 
 }  // namespace
 
-float pack_layer1_general(const float *w, const float *b, int n_channels, void *out, size_t out_bytes) {
-    if (!w || !b || !out || (n_channels != 3 && n_channels != 6)) return 0.f;
-    const size_t need = (size_t)2 * (n_channels == 3 ? 14 : 28) * 2048;
-    if (out_bytes < need) return 0.f;
-    return pack_layer1(w, b, n_channels, static_cast<_Float16 *>(out));
-}
-
 struct General {
-    int device_id, state_dim, F;
-    Geometry g;
-    char *d_pack;          // layer 1 | layer 2 | layer 3 B fragments
-    char *d_pack_i8;       // 3-channel frames: layer 1 as int8 digits (pack_layer1_i8, zero slot 7), then [64] float 256 / scale
-    bool l1_i8;            // layer 1 runs on the int8 pipe (3 channels, SRLHIP_ENCODER_L1=i8: the measured alternative, slower here)
-    size_t pack1_bytes;
-    float *d_f32;          // bias2[64] bias3[64] fcb[state_dim] fcw[state_dim][F]
-    float inv_scale[3];
-    int *d_status;
-    char *d_act;           // scratch for `cap` frames: a1 hi | a1 lo | a2 hi | a2 lo | features
-    int cap;
+    int device_id = 0, state_dim = 0, F = 0;
+    Geometry g = {};
+    char *d_pack = nullptr;          // layer 1 | layer 2 | layer 3 B fragments
+    char *d_pack_i8 = nullptr;       // 3-channel frames: layer 1 as int8 digits (pack_layer1_i8, zero slot 7), then [64] float 256 / scale
+    bool l1_i8 = false;              // layer 1 runs on the int8 pipe (3 channels, SRLHIP_ENCODER_L1=i8: the measured alternative, slower here)
+    size_t pack1_bytes = 0;
+    float *d_f32 = nullptr;          // bias2[64] bias3[64] fcb[state_dim] fcw[state_dim][F]
+    float inv_scale[3] = {};
+    int *d_status = nullptr;
+    char *d_act = nullptr;           // scratch for `cap` frames: a1 hi | a1 lo | a2 hi | a2 lo | features
+    int cap = 0;
 };
 
 int *general_status(General *g) { return g->d_status; }
@@ -576,8 +535,8 @@ int general_create(int device_id, const Geometry &geo, int state_dim, const floa
                    General **out, std::string &err) {
     General *g = new (std::nothrow) General();
     if (!g) return SRLHIP_ENOMEM;
-    g->device_id = device_id; g->state_dim = state_dim; g->g = geo; g->d_pack = nullptr; g->d_f32 = nullptr; g->d_status = nullptr;
-    g->d_act = nullptr; g->cap = 0; g->d_pack_i8 = nullptr;
+    *out = g;
+    g->device_id = device_id; g->state_dim = state_dim; g->g = geo;
     {
         // The int8 form of layer 1 is NOT the default here (it is in the fused 64x64x3 kernel): left to the compiler's scheduler its six
         // digit accumulators per row pair + the 80 recombined sums + hoisted fragment loads spill (88 registers at the 256 of two
@@ -586,62 +545,39 @@ int general_create(int device_id, const Geometry &geo, int state_dim, const floa
         const char *l1 = getenv("SRLHIP_ENCODER_L1");
         g->l1_i8 = geo.C == 3 && l1 && strcmp(l1, "i8") == 0;
     }
-    const int F = 64 * geo.Hp[2] * geo.Wp[2];
+    const int F = feature_count(geo);
     g->F = F;
-    const int ks1 = geo.C == 3 ? 14 : 28;
-    g->pack1_bytes = (size_t)2 * ks1 * 64 * 32;
+    g->pack1_bytes = layer1_bytes(geo.C);
     std::vector<char> pack(g->pack1_bytes + 2 * kPack3x3Bytes);
-    const float s1 = pack_layer1(conv1_w, conv1_b, geo.C, reinterpret_cast<_Float16 *>(pack.data()));
+    const float s1 = pack_layer1_f16(conv1_w, conv1_b, geo.C, reinterpret_cast<_Float16 *>(pack.data()));
     const float s2 = pack_layer3x3(conv2_w, reinterpret_cast<_Float16 *>(pack.data() + g->pack1_bytes));
     const float s3 = pack_layer3x3(conv3_w, reinterpret_cast<_Float16 *>(pack.data() + g->pack1_bytes + kPack3x3Bytes));
     g->inv_scale[0] = 1.f / s1; g->inv_scale[1] = 1.f / s2; g->inv_scale[2] = 1.f / s3;      // powers of two: exact
-    std::vector<float> f(128 + (size_t)state_dim * (1 + F));
+    std::vector<float> f(kF32FcbG + (size_t)state_dim * (1 + F));
     memcpy(f.data(), conv2_b, 64 * sizeof(float));
-    memcpy(f.data() + 64, conv3_b, 64 * sizeof(float));
-    memcpy(f.data() + 128, fc_b, state_dim * sizeof(float));
-    // features are [frame row p][frame column q][channel]; torch flattens the transposed map as (channel, q, p)
-    const int Hp = geo.Hp[2], Wp = geo.Wp[2];
-    for (int s = 0; s < state_dim; s++)
-        for (int p = 0; p < Hp; p++)
-            for (int q = 0; q < Wp; q++)
-                for (int c = 0; c < 64; c++)
-                    f[128 + state_dim + (size_t)s * F + (p * Wp + q) * 64 + c] = fc_w[(size_t)s * F + (size_t)c * Wp * Hp + q * Hp + p];
-#define GEN_CHECK(expr)                                                              \
-    do {                                                                             \
-        hipError_t e__ = (expr);                                                     \
-        if (e__ != hipSuccess) {                                                     \
-            err = std::string(#expr ": ") + hipGetErrorString(e__);                  \
-            general_destroy(g);                                                      \
-            return SRLHIP_EHIP;                                                      \
-        }                                                                            \
-    } while (0)
-    GEN_CHECK(hipSetDevice(device_id));
-    GEN_CHECK(hipMalloc(reinterpret_cast<void **>(&g->d_pack), pack.size()));
-    GEN_CHECK(hipMalloc(reinterpret_cast<void **>(&g->d_f32), f.size() * sizeof(float)));
-    GEN_CHECK(hipMalloc(reinterpret_cast<void **>(&g->d_status), sizeof(int)));
-    GEN_CHECK(hipMemcpy(g->d_pack, pack.data(), pack.size(), hipMemcpyHostToDevice));
-    GEN_CHECK(hipMemcpy(g->d_f32, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
-    GEN_CHECK(hipMemset(g->d_status, 0, sizeof(int)));
+    memcpy(f.data() + kF32Bias3G, conv3_b, 64 * sizeof(float));
+    memcpy(f.data() + kF32FcbG, fc_b, state_dim * sizeof(float));
+    reorder_fc(fc_w, state_dim, geo.Hp[2], geo.Wp[2], f.data() + kF32FcbG + state_dim);
+    ENC_HIP(err, hipSetDevice(device_id));
+    ENC_HIP(err, hipMalloc(reinterpret_cast<void **>(&g->d_pack), pack.size()));
+    ENC_HIP(err, hipMalloc(reinterpret_cast<void **>(&g->d_f32), f.size() * sizeof(float)));
+    ENC_HIP(err, hipMalloc(reinterpret_cast<void **>(&g->d_status), sizeof(int)));
+    ENC_HIP(err, hipMemcpy(g->d_pack, pack.data(), pack.size(), hipMemcpyHostToDevice));
+    ENC_HIP(err, hipMemcpy(g->d_f32, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
+    ENC_HIP(err, hipMemset(g->d_status, 0, sizeof(int)));
     if (geo.C == 3) {
         std::vector<char> p8(kPackI8Bytes + 64 * sizeof(float));
         pack_layer1_i8(conv1_w, conv1_b, 7, reinterpret_cast<int8_t *>(p8.data()), reinterpret_cast<float *>(p8.data() + kPackI8Bytes));
-        GEN_CHECK(hipMalloc(reinterpret_cast<void **>(&g->d_pack_i8), p8.size()));
-        GEN_CHECK(hipMemcpy(g->d_pack_i8, p8.data(), p8.size(), hipMemcpyHostToDevice));
-        GEN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(enc_layer_k<1, 4, kR1, kNC1, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        ENC_HIP(err, hipMalloc(reinterpret_cast<void **>(&g->d_pack_i8), p8.size()));
+        ENC_HIP(err, hipMemcpy(g->d_pack_i8, p8.data(), p8.size(), hipMemcpyHostToDevice));
+        ENC_HIP(err, hipFuncSetAttribute(reinterpret_cast<const void *>(enc_layer_k<1, 4, kR1, kNC1, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds1Allowed));
     }
-    constexpr int lds2 = 2 * (kR2 * 2 + 3) * kNC2 * PX, lds3 = 2 * (2 * (2 * kR3) + 3) * kNC3 * PX;
-    GEN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(enc_layer_k<2, 4, kR2, kNC2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds2));
-    GEN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(enc_layer_k<1, 4, kR1, kNC1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    GEN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(enc_layer_k<3, 4, kR3, kNC3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds3));
-    GEN_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(enc_layer_k<3, 4, kR3, kNC3Narrow>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  2 * (2 * (2 * kR3) + 3) * kNC3Narrow * PX + kLdsSlack3));
-#undef GEN_CHECK
-    *out = g;
+    ENC_HIP(err, hipFuncSetAttribute(reinterpret_cast<const void *>(enc_layer_k<2, 4, kR2, kNC2>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds2));
+    ENC_HIP(err, hipFuncSetAttribute(reinterpret_cast<const void *>(enc_layer_k<1, 4, kR1, kNC1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds1Allowed));
+    ENC_HIP(err, hipFuncSetAttribute(reinterpret_cast<const void *>(enc_layer_k<3, 4, kR3, kNC3>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds3));
+    ENC_HIP(err, hipFuncSetAttribute(reinterpret_cast<const void *>(enc_layer_k<3, 4, kR3, kNC3Narrow>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds3Narrow));
     return SRLHIP_OK;
 }
-
-// dynamic LDS of a layer kernel: the input window, or the pooled band that replaces it before the stores
-static int lds_bytes(int window, int r, bool f32) { const int band = r * 15 * (f32 ? 256 : 256); return window > band ? window : band; }
 
 // layers 2-3: bands a workgroup walks — as many as leave >= 4096 workgroups
 static int bands_per_wg(int nbands, int nsegs, int frames) {
@@ -682,36 +618,30 @@ int general_forward(General *g, const uint8_t *images_dev, int n, float *states_
         dim3 grid1((p.Wp + 14) / 15, (p.nbands + p.bands_per_wg - 1) / p.bands_per_wg, nn);
         if (geo.C == 3 && g->l1_i8) {
             // 3 channels, int8 layer 1: digits in LDS, four wavefronts per workgroup (two column segments), bands of kR1 pooled rows
-            constexpr int win = (2 * (2 * kR1) + 7) * kNC1 * 4, band = kR1 * 15 * 256;
             p.pack = g->d_pack_i8; p.inv1c = reinterpret_cast<const float *>(g->d_pack_i8 + kPackI8Bytes);
-            hipLaunchKernelGGL((enc_layer_k<1, 4, kR1, kNC1, true, true>), dim3((grid1.x + 1) / 2, grid1.y, nn), dim3(256),
-                               (int)kPackI8Bytes + 2 * (win > band ? win : band), stream, p);
+            hipLaunchKernelGGL((enc_layer_k<1, 4, kR1, kNC1, true, true>), dim3((grid1.x + 1) / 2, grid1.y, nn), dim3(256), kLds1I8, stream, p);
         } else if (geo.C == 3) {
             // 3 channels: weights in LDS, four wavefronts per workgroup (two column segments), bands of kR1 pooled rows
-            constexpr int win = (2 * (2 * kR1) + 7) * kNC1 * 8, band = kR1 * 15 * 256;
-            hipLaunchKernelGGL((enc_layer_k<1, 4, kR1, kNC1, true>), dim3((grid1.x + 1) / 2, grid1.y, nn), dim3(256),
-                               2 * 14 * 2048 + 2 * (win > band ? win : band), stream, p);
+            hipLaunchKernelGGL((enc_layer_k<1, 4, kR1, kNC1, true>), dim3((grid1.x + 1) / 2, grid1.y, nn), dim3(256), kLds1, stream, p);
         } else {
-            hipLaunchKernelGGL((enc_layer_k<1, 8, kR1x6, kNC1>), grid1, dim3(128), lds_bytes((2 * (2 * kR1x6) + 7) * kNC1 * 16, kR1x6, false), stream, p);
+            hipLaunchKernelGGL((enc_layer_k<1, 8, kR1x6, kNC1>), grid1, dim3(128), kLds1x6, stream, p);
         }
         // layer 2
         p.img = nullptr; p.in_hi = a1h + a1 * base; p.in_lo = a1l + a1 * base; p.out_hi = a2h + a2 * base; p.out_lo = a2l + a2 * base;
         p.pack = pack2; p.bias = g->d_f32; p.inv_scale = g->inv_scale[1];
         p.Hin = geo.Hp[0]; p.Win = geo.Wp[0]; p.Hc = geo.Hc[1]; p.Wc = geo.Wc[1]; p.Hp = geo.Hp[1]; p.Wp = geo.Wp[1];
         p.nbands = (p.Hp + kR2 - 1) / kR2; p.bands_per_wg = bands_per_wg(p.nbands, (p.Wp + 14) / 15, nn);
-        hipLaunchKernelGGL((enc_layer_k<2, 4, kR2, kNC2>), dim3((p.Wp + 14) / 15, (p.nbands + p.bands_per_wg - 1) / p.bands_per_wg, nn), dim3(128), 2 * (kR2 * 2 + 3) * kNC2 * PX, stream, p);
+        hipLaunchKernelGGL((enc_layer_k<2, 4, kR2, kNC2>), dim3((p.Wp + 14) / 15, (p.nbands + p.bands_per_wg - 1) / p.bands_per_wg, nn), dim3(128), kLds2, stream, p);
         // layer 3
         p.in_hi = a2h + a2 * base; p.in_lo = a2l + a2 * base; p.out_hi = nullptr; p.out_lo = nullptr; p.out_f32 = feat + (size_t)g->F * base;
-        p.pack = pack3; p.bias = g->d_f32 + 64; p.inv_scale = g->inv_scale[2];
+        p.pack = pack3; p.bias = g->d_f32 + kF32Bias3G; p.inv_scale = g->inv_scale[2];
         p.Hin = geo.Hp[1]; p.Win = geo.Wp[1]; p.Hc = geo.Hc[2]; p.Wc = geo.Wc[2]; p.Hp = geo.Hp[2]; p.Wp = geo.Wp[2];
         p.nbands = (p.Hp + kR3 - 1) / kR3; p.bands_per_wg = bands_per_wg(p.nbands, (p.Wp + 14) / 15, nn);
         if (p.Wc <= 16)
-            hipLaunchKernelGGL((enc_layer_k<3, 4, kR3, kNC3Narrow>), dim3(1, (p.nbands + p.bands_per_wg - 1) / p.bands_per_wg, nn), dim3(128),
-                               2 * (2 * (2 * kR3) + 3) * kNC3Narrow * PX + kLdsSlack3, stream, p);
+            hipLaunchKernelGGL((enc_layer_k<3, 4, kR3, kNC3Narrow>), dim3(1, (p.nbands + p.bands_per_wg - 1) / p.bands_per_wg, nn), dim3(128), kLds3Narrow, stream, p);
         else
-            hipLaunchKernelGGL((enc_layer_k<3, 4, kR3, kNC3>), dim3((p.Wp + 14) / 15, (p.nbands + p.bands_per_wg - 1) / p.bands_per_wg, nn), dim3(128),
-                               2 * (2 * (2 * kR3) + 3) * kNC3 * PX, stream, p);
-        hipLaunchKernelGGL(enc_fc_k, dim3(nn), dim3(256), 0, stream, feat + (size_t)g->F * base, g->d_f32 + 128 + g->state_dim, g->d_f32 + 128,
+            hipLaunchKernelGGL((enc_layer_k<3, 4, kR3, kNC3>), dim3((p.Wp + 14) / 15, (p.nbands + p.bands_per_wg - 1) / p.bands_per_wg, nn), dim3(128), kLds3, stream, p);
+        hipLaunchKernelGGL(enc_fc_k, dim3(nn), dim3(256), 0, stream, feat + (size_t)g->F * base, g->d_f32 + kF32FcbG + g->state_dim, g->d_f32 + kF32FcbG,
                            states_dev + (size_t)base * g->state_dim, g->F, g->state_dim);
     }
     const hipError_t rc = hipGetLastError();

@@ -1,4 +1,4 @@
-"""Host-only checks of the layered encoder's shape logic (csrc/encoder_general.hip::geometry, through the C-ABI): which
+"""Host-only checks of the layered encoder's shape logic (csrc/encoder_pack.hpp::geometry, through the C-ABI): which
 frame shapes the HIP encoder covers and how many inputs its fully connected layer has, against PyTorch's own shape
 arithmetic for the same CustomCNN (state_representation/models.py; reference: models.py:178-193)."""
 import pytest
@@ -29,7 +29,7 @@ def test_uncovered_shapes():
 
 @pytest.mark.parametrize("ch", [3, 6])
 def test_layered_layer1_pack_is_the_normalised_convolution(ch):
-    """The layered path's layer-1 B image (srlhip_encoder_pack_first_layer, csrc/encoder_general.hip) decoded with numpy and applied
+    """The layered path's layer-1 B image (srlhip_encoder_pack_first_layer, csrc/encoder_pack.hpp) decoded with numpy and applied
     to a padded (channels, mask[, 0]) uint8 frame the way the kernel indexes it — k = (ky * 8 + kx) * cpix + c, stride 2,
     3-pixel ring with mask 0 — equals the BatchNorm-folded conv1 of the torch model on the reference's preprocessing
     (scale to [0, 1], ImageNet mean / std per 3-channel group, H/W swapped): checks the folding, the mask channel that keeps

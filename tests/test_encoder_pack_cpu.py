@@ -108,7 +108,7 @@ def test_pack_decodes_to_the_network():
 
 
 def test_int8_layer1_pack_decodes_to_the_network():
-    """Round 6: layer 1 of the fused kernel runs on the int8 matrix pipe (csrc/encoder.hip, pack_layer1_i8).  The digit image is
+    """Round 6: layer 1 of the fused kernel runs on the int8 matrix pipe (csrc/encoder_pack.hpp, pack_layer1_i8).  The digit image is
     decoded with numpy — balanced base-256 digits, per-channel power-of-two scales, slot 0 of every kernel row empty, mask tap around
     p - 128 — and the kernel's INTEGER data flow is emulated exactly (int64 sums of (p - 128) x digit, recombined as
     256 a2 + a1 + floor(a0 / 256)): followed by the float64 walk through layers 2 / 3 / FC it has to match PyTorch."""
