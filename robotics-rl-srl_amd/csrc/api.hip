@@ -18,8 +18,6 @@ namespace {
 thread_local std::string g_create_error;
 constexpr int kBlock = 256;
 
-bool is_mobile(int kind) { return kind >= SRLHIP_ENV_MOBILE && kind <= SRLHIP_ENV_MOBILE_LINE; }
-
 // RandomState.seed(digits) for the selected envs, one lane per env.
 __global__ void mt_seed_k(Mt19937View v, int n, const uint8_t *mask, const uint32_t *digits, const int32_t *len) {
     int e = blockIdx.x * kBlock + threadIdx.x;
@@ -38,30 +36,27 @@ __global__ void key_seed_k(RngState r, int n, const uint8_t *mask, const uint32_
     r.ctr[e] = 0; r.act_ctr[e] = 0;
 }
 
-int ensure_pinned(Handle *h, void **buf, size_t *cap, size_t bytes) {
-    if (*cap >= bytes) return 0;
-    if (*buf) (void)hipHostFree(*buf);
-    *buf = nullptr; *cap = 0;
+int ensure_pinned(Handle *h, PinBuf &b, size_t bytes) {
+    if (b.cap >= bytes) return 0;
+    if (b.p) (void)hipHostFree(b.p);
+    b = PinBuf{};
     // mapped: kernels may address it directly (zero-copy step); coherent (fine-grained): what a RESIDENT kernel writes and releases at
     // system scope is visible to the host while the kernel is still running (persistent stepping; + 16: its copy works in dwords)
-    SRL_HIP_CHECK(h, hipHostMalloc(buf, bytes + 16, hipHostMallocMapped | hipHostMallocCoherent));
-    *cap = bytes;
+    SRL_HIP_CHECK(h, hipHostMalloc(&b.p, bytes + 16, hipHostMallocMapped | hipHostMallocCoherent));
+    b.cap = bytes;
     return 0;
 }
-int stage_in(Handle *h, void **buf, size_t *cap, const void *host, size_t bytes) {
-    int rc = ensure(h, buf, cap, bytes);
+int stage_in(Handle *h, DevBuf &b, const void *host, size_t bytes) {
+    int rc = ensure(h, b, bytes);
     if (rc) return rc;
-    SRL_HIP_CHECK(h, hipMemcpyAsync(*buf, host, bytes, hipMemcpyHostToDevice, h->stream));
+    SRL_HIP_CHECK(h, hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, h->stream));
     return 0;
 }
 
-size_t action_bytes(const Handle *h) {
-    return (size_t)h->n * (h->cfg.is_discrete ? sizeof(int32_t) : sizeof(float) * action_dim_of(h->cfg));
-}
-size_t obs_bytes_per_env(const Handle *h) {
-    if (h->cfg.obs_mode == SRLHIP_OBS_RAW_PIXELS)
-        return (size_t)h->cfg.img_h * h->cfg.img_w * (h->cfg.multi_view ? 6 : 3);
-    return sizeof(float) * obs_dim_of(h->cfg);
+// the handle's step buffers (api_rules.hpp); SRLHIP_ZERO_COPY=0: bounce buffers even where the zero-copy step applies (read once)
+StepLayout step_layout(const Handle *h) {
+    static const bool zc_enabled = [] { const char *v = getenv("SRLHIP_ZERO_COPY"); return !v || atoi(v) != 0; }();
+    return srl::step_layout(h->cfg, (size_t)h->n, zc_enabled);
 }
 
 // ---- persistent stepping: host side of the protocol (step_signal.hpp) -------------------------------------------------------------------
@@ -117,19 +112,16 @@ int persist_launch(Handle *h, uint32_t start_seq) {
     SRL_HIP_CHECK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->persist_relay + kWordCount), 0, kWordStepCount - kWordCount, h->stream));
     void *dctl = nullptr, *din = nullptr, *dout = nullptr;
     SRL_HIP_CHECK(h, hipHostGetDevicePointer(&dctl, h->persist_host, 0));
-    SRL_HIP_CHECK(h, hipHostGetDevicePointer(&din, h->pin_in, 0));
-    SRL_HIP_CHECK(h, hipHostGetDevicePointer(&dout, h->pin_out, 0));
+    SRL_HIP_CHECK(h, hipHostGetDevicePointer(&din, h->pin[PIN_IN].p, 0));
+    SRL_HIP_CHECK(h, hipHostGetDevicePointer(&dout, h->pin[PIN_OUT].p, 0));
     PersistArgs pa = signal_args(SignalKind::resident, dctl, h->persist_relay);
     pa.start_seq = start_seq;
     { const char *v = getenv("SRLHIP_PERSIST_STAGED"); pa.force_staged = v && atoi(v) != 0; }
     pa.spin_limit = h->persist_park_us / 2 + 1;        // one poll of workgroup 0: one 8-byte PCIe read + s_sleep 8, ~2 us
-    const size_t n = (size_t)h->n, ob = obs_bytes_per_env(h) * n, out_rew = (ob + 15) & ~(size_t)15, out_done = out_rew + 4 * n;
+    const StepLayout L = step_layout(h);
     pa.stage = static_cast<const uint32_t *>(h->persist_stage); pa.host_out = static_cast<uint32_t *>(dout);
-    pa.rew_dw = (uint32_t)(out_rew / 4); pa.done_dw = (uint32_t)(out_done / 4);
-    uint8_t *o = static_cast<uint8_t *>(h->persist_stage), *ho = static_cast<uint8_t *>(dout);
-    // (the Kuka kernels take the staging copy and switch to the host's planes themselves; the MobileRobot kernel writes the host's planes)
-    int rc = is_mobile(h->cfg.env_kind) ? mobile_persist_start(h, din, reinterpret_cast<float *>(ho), reinterpret_cast<float *>(ho + out_rew), ho + out_done, pa)
-                                        : kuka_persist_start(h, din, reinterpret_cast<float *>(o), reinterpret_cast<float *>(o + out_rew), o + out_done, pa);
+    pa.rew_dw = (uint32_t)(L.out_rew / 4); pa.done_dw = (uint32_t)(L.out_done / 4);
+    int rc = env_ops(h).persist_start(h, din, pa);
     if (rc) return rc;
     h->persist_running = true;
     return 0;
@@ -153,19 +145,19 @@ int seed_impl(Handle *h, const uint8_t *mask, const int64_t *seeds) {
     int rc;
     const uint8_t *d_mask = nullptr;
     if (mask) {
-        if ((rc = stage_in(h, &h->st_mask, &h->st_mask_sz, mask, n))) return rc;
-        d_mask = static_cast<const uint8_t *>(h->st_mask);
+        if ((rc = stage_in(h, h->st[ST_MASK], mask, n))) return rc;
+        d_mask = static_cast<const uint8_t *>(h->st[ST_MASK].p);
     }
     dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-    if ((rc = stage_in(h, &h->st_rand, &h->st_rand_sz, lohi.data(), lohi.size() * 4))) return rc;
+    if ((rc = stage_in(h, h->st[ST_RAND], lohi.data(), lohi.size() * 4))) return rc;
     hipLaunchKernelGGL(key_seed_k, grid, block, 0, h->stream, h->rng, n, d_mask,
-                       static_cast<const uint32_t *>(h->st_rand));
+                       static_cast<const uint32_t *>(h->st[ST_RAND].p));
     SRL_HIP_CHECK(h, hipGetLastError());
     SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));   // host vectors die at return
     if (h->cfg.rng_mode == SRLHIP_RNG_MT19937) {
-        if ((rc = stage_in(h, &h->st_rand, &h->st_rand_sz, digits.data(), digits.size() * 4))) return rc;
-        if ((rc = stage_in(h, &h->st_noise, &h->st_noise_sz, len.data(), len.size() * 4))) return rc;
-        SRL_HIP_CHECK(h, mt_seed_launch(h->rng.mt, n, d_mask, static_cast<const uint32_t *>(h->st_rand), static_cast<const int32_t *>(h->st_noise), h->stream));
+        if ((rc = stage_in(h, h->st[ST_RAND], digits.data(), digits.size() * 4))) return rc;
+        if ((rc = stage_in(h, h->st[ST_NOISE], len.data(), len.size() * 4))) return rc;
+        SRL_HIP_CHECK(h, mt_seed_launch(h->rng.mt, n, d_mask, static_cast<const uint32_t *>(h->st[ST_RAND].p), static_cast<const int32_t *>(h->st[ST_NOISE].p), h->stream));
         SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));
     }
     return 0;
@@ -180,28 +172,6 @@ __global__ void episode_stats_k(EpisodeStats st, int n, float *ret, int32_t *len
     if (fin) fin[e] = st.n_finished[e];
 }
 
-// Host-pointer calls validate what the kernels cannot afford to: the full-model Kuka kernels are compiled with -fno-honor-nans, so a NaN
-// or an infinity in a continuous action or in host-drawn noise would propagate through the step unchecked (the reference's
-// np.clip / pybullet would raise or saturate).  Device-pointer callers own their buffers' contents.
-bool all_finite_f32(const float *p, size_t count) { for (size_t i = 0; i < count; i++) if (!std::isfinite(p[i])) return false; return true; }
-bool all_finite_f64(const double *p, size_t count) { for (size_t i = 0; i < count; i++) if (!std::isfinite(p[i])) return false; return true; }
-// Continuous actions of a Kuka handle, rows of `dim`: every row all finite, or all NaN (the reference's `None`, include/srlhip.h).
-// One pass; a partly NaN row and any infinity fail.
-bool kuka_rows_ok(const float *p, size_t rows, int dim) {
-    for (size_t r = 0; r < rows; r++, p += dim) {
-        int fin = 0, nan = 0;
-        for (int j = 0; j < dim; j++) { fin += std::isfinite(p[j]) ? 1 : 0; nan += std::isnan(p[j]) ? 1 : 0; }
-        if (fin != dim && nan != dim) return false;
-    }
-    return true;
-}
-// the host-pointer check of a continuous action plane: MobileRobot takes finite values only (its step has no `None` branch for
-// continuous actions: `action[0]` on None raises), Kuka finite or NaN rows
-bool continuous_actions_ok(const Handle *h, const float *p, size_t rows) {
-    const int dim = action_dim_of(h->cfg);
-    return is_mobile(h->cfg.env_kind) ? all_finite_f32(p, rows * (size_t)dim) : kuka_rows_ok(p, rows, dim);
-}
-
 int field_lookup(Handle *h, int field, void **dptr, size_t *elem, int *count) {
     *count = 1;
     switch (field) {
@@ -212,8 +182,7 @@ int field_lookup(Handle *h, int field, void **dptr, size_t *elem, int *count) {
         case SRLHIP_F_EP_RETURN: *dptr = h->stats.ep_return; *elem = 8; return 0;
         case SRLHIP_F_EP_LENGTH: *dptr = h->stats.ep_length; *elem = 4; return 0;
     }
-    if (is_mobile(h->cfg.env_kind)) return mobile_field(h, field, dptr, elem, count);
-    return kuka_field(h, field, dptr, elem, count);
+    return env_ops(h).field(h, field, dptr, elem, count);
 }
 
 }  // namespace
@@ -229,22 +198,8 @@ extern "C" {
 int srlhip_abi_version(void) { return SRLHIP_ABI_VERSION; }
 
 int srlhip_default_config(int32_t env_kind, srlhip_config *cfg) {
-    if (!cfg || env_kind < SRLHIP_ENV_MOBILE || env_kind > SRLHIP_ENV_LAST) return SRLHIP_EINVAL;
-    memset(cfg, 0, sizeof *cfg);
-    cfg->struct_size = (int32_t)sizeof *cfg;
-    cfg->env_kind = env_kind;
-    cfg->num_envs = 1;
-    cfg->is_discrete = 1;
-    cfg->force_down = 1;
-    cfg->action_repeat = 1;
-    cfg->obs_mode = SRLHIP_OBS_GROUND_TRUTH;
-    cfg->img_h = cfg->img_w = 224;                                  // RENDER_HEIGHT/WIDTH
-    cfg->rng_mode = SRLHIP_RNG_MT19937;
-    cfg->auto_reset = 1;
-    cfg->max_distance = env_kind >= SRLHIP_ENV_KUKA_BUTTON ? 0.8 : 1.6;   // ctor defaults
-    if (env_kind == SRLHIP_ENV_KUKA_2BUTTON) { cfg->max_distance = 2.0; cfg->force_down = 0; }   // kuka_2button_gym_env.py:29
-    // every Kuka env integrates the full arm + gripper model on the tree lane-group kernel (Kuka2Button: its two-button form)
-    cfg->kuka_model = env_kind >= SRLHIP_ENV_KUKA_BUTTON ? SRLHIP_KUKA_MODEL_FULL : SRLHIP_KUKA_MODEL_LUMPED;
+    if (!cfg || !(is_mobile(env_kind) || is_kuka(env_kind))) return SRLHIP_EINVAL;
+    fill_default_config(env_kind, cfg);
     return 0;
 }
 
@@ -256,40 +211,7 @@ const char *srlhip_last_error(srlhip_handle hh) {
 int srlhip_create(const srlhip_config *cfg, srlhip_handle *out) {
     if (!cfg || !out) { g_create_error = "create: null argument"; return SRLHIP_EINVAL; }
     *out = nullptr;
-    if (cfg->struct_size != (int32_t)sizeof(srlhip_config)) {
-        g_create_error = "create: srlhip_config.struct_size mismatch (ABI)"; return SRLHIP_EINVAL;
-    }
-    if (cfg->num_envs <= 0) { g_create_error = "create: num_envs must be positive"; return SRLHIP_EINVAL; }
-    if (cfg->env_kind < SRLHIP_ENV_MOBILE || cfg->env_kind > SRLHIP_ENV_LAST) {
-        g_create_error = "create: unknown env_kind"; return SRLHIP_EINVAL;
-    }
-    if (cfg->rng_mode < SRLHIP_RNG_HOST || cfg->rng_mode > SRLHIP_RNG_MT19937) {
-        g_create_error = "create: unknown rng_mode"; return SRLHIP_EINVAL;
-    }
-    if (cfg->auto_reset && cfg->rng_mode == SRLHIP_RNG_HOST) {
-        g_create_error = "create: auto_reset needs a device RNG mode"; return SRLHIP_EINVAL;
-    }
-    if (!cfg->is_discrete &&
-        (cfg->env_kind == SRLHIP_ENV_MOBILE_1D || cfg->env_kind == SRLHIP_ENV_MOBILE_2TARGET)) {
-        // mobile_robot_1D_env.py:44, mobile_robot_2target_env.py:128-129 raise ValueError
-        g_create_error = "Only discrete actions is supported"; return SRLHIP_ENOTSUP;
-    }
-    if (is_mobile(cfg->env_kind) && cfg->obs_mode != SRLHIP_OBS_GROUND_TRUTH &&
-        cfg->obs_mode != SRLHIP_OBS_RAW_PIXELS) {
-        g_create_error = "create: MobileRobot envs support ground_truth / raw_pixels only"; return SRLHIP_EINVAL;
-    }
-    // every obs_mode: srlhip_render() also serves ground-truth handles (dataset_generator --img-size), and the rasteriser's
-    // LDS band holds one image row of at most 2048 pixels
-    if (cfg->img_h < 8 || cfg->img_w < 8 || cfg->img_h > 1024 || cfg->img_w > 1024) {
-        g_create_error = "create: img_h / img_w must be in [8, 1024]"; return SRLHIP_EINVAL;
-    }
-    if (cfg->env_kind >= SRLHIP_ENV_KUKA_BUTTON && cfg->kuka_model != SRLHIP_KUKA_MODEL_LUMPED && cfg->kuka_model != SRLHIP_KUKA_MODEL_FULL) {
-        g_create_error = "create: unknown kuka_model"; return SRLHIP_EINVAL;
-    }
-    if (cfg->info_bits != 0 && cfg->info_bits != 1) { g_create_error = "create: info_bits must be 0 or 1"; return SRLHIP_EINVAL; }
-    if (cfg->env_kind >= SRLHIP_ENV_KUKA_BUTTON && cfg->action_repeat < 1) {
-        g_create_error = "create: action_repeat must be >= 1"; return SRLHIP_EINVAL;
-    }
+    if (const Verdict v = check_config(*cfg); v.code) { g_create_error = v.msg; return v.code; }
     hipError_t e = hipSetDevice(cfg->device_id);
     if (e != hipSuccess) {
         g_create_error = std::string("create: hipSetDevice failed (no MI355X visible?): ") + hipGetErrorString(e);
@@ -297,16 +219,11 @@ int srlhip_create(const srlhip_config *cfg, srlhip_handle *out) {
     }
     Handle *h = new (std::nothrow) Handle();
     if (!h) { g_create_error = "create: out of host memory"; return SRLHIP_ENOMEM; }
-    h->cfg = *cfg; h->n = cfg->num_envs; h->kuka = nullptr;
-    h->st_actions = h->st_noise = h->st_obs = h->st_rew = h->st_done = h->st_mask = h->st_rand = nullptr;
-    h->st_actions_sz = h->st_noise_sz = h->st_obs_sz = h->st_rew_sz = h->st_done_sz = h->st_mask_sz = h->st_rand_sz = 0;
-    h->pin_in = h->pin_out = nullptr; h->pin_in_sz = h->pin_out_sz = 0;
-    h->raster_rays[0] = h->raster_rays[1] = nullptr; h->raster_bg[0] = h->raster_bg[1] = nullptr;
-    memset(&h->rng, 0, sizeof h->rng); memset(&h->stats, 0, sizeof h->stats); memset(&h->mobile, 0, sizeof h->mobile);
+    h->cfg = *cfg; h->n = cfg->num_envs;
     int rc = 0;
     auto bail = [&](int code) { g_create_error = h->err; srlhip_destroy(reinterpret_cast<srlhip_handle>(h)); return code; };
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        h->stream = nullptr; h->ev_begin = h->ev_end = nullptr; h->err = "create: hipStreamCreate failed";
+        h->err = "create: hipStreamCreate failed";
         return bail(SRLHIP_EHIP);
     }
     (void)hipEventCreate(&h->ev_begin); (void)hipEventCreate(&h->ev_end);
@@ -326,16 +243,14 @@ int srlhip_create(const srlhip_config *cfg, srlhip_handle *out) {
         // Monitor's (r, l) of the last finished episode where the host can read them without a copy: the kernels' exit stores go
         // over PCIe (12 bytes per env and launch), srlhip_episode_records() hands out the host view
         void *dp = nullptr;
-        if (hipHostMalloc(&h->ep_host, 12 * n, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess || hipHostGetDevicePointer(&dp, h->ep_host, 0) != hipSuccess) {
+        if (hipHostMalloc(&h->ep_host, episode_block_bytes(n), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess || hipHostGetDevicePointer(&dp, h->ep_host, 0) != hipSuccess) {
             h->err = "create: hipHostMalloc (episode records) failed"; return bail(SRLHIP_ENOMEM);
         }
-        memset(h->ep_host, 0, 12 * n);
-        st.last_return = static_cast<double *>(dp);
-        st.last_length = reinterpret_cast<int32_t *>(static_cast<uint8_t *>(dp) + 8 * n);
+        memset(h->ep_host, 0, episode_block_bytes(n));
+        st.last_return = episode_returns(dp);
+        st.last_length = episode_lengths(dp, n);
     } else if ((rc = h->dalloc(&st.last_return, n)) || (rc = h->dalloc(&st.last_length, n))) return bail(rc);
-    rc = is_mobile(cfg->env_kind) ? mobile_alloc(h) : kuka_alloc(h);
-    if (rc) return bail(rc);
-    if (!is_mobile(cfg->env_kind) && (rc = h->dalloc(&h->policy_hdr, 16))) return bail(rc);
+    if ((rc = env_ops(h).alloc(h))) return bail(rc);
     std::vector<int64_t> seeds(n);
     for (size_t i = 0; i < n; i++) seeds[i] = cfg->seed0 + cfg->first_env_id + (int64_t)i;   // environments/utils.py:52
     if ((rc = seed_impl(h, nullptr, seeds.data()))) return bail(rc);
@@ -358,11 +273,9 @@ int srlhip_destroy(srlhip_handle hh) {
     if (h->persist_stage) (void)hipFree(h->persist_stage);
     if (h->kuka) kuka_free(h);
     for (void *p : h->allocs) (void)hipFree(p);
-    void *st[] = {h->st_actions, h->st_noise, h->st_obs, h->st_rew, h->st_done, h->st_mask, h->st_rand, h->st_jpeg};
-    for (void *p : st) if (p) (void)hipFree(p);
-    for (void *p : h->act_plane) if (p) (void)hipFree(p);
-    if (h->pin_in) (void)hipHostFree(h->pin_in);
-    if (h->pin_out) (void)hipHostFree(h->pin_out);
+    for (const DevBuf &b : h->st) if (b.p) (void)hipFree(b.p);
+    for (const DevBuf &b : h->act_plane) if (b.p) (void)hipFree(b.p);
+    for (const PinBuf &b : h->pin) if (b.p) (void)hipHostFree(b.p);
     if (h->ep_host) (void)hipHostFree(h->ep_host);
     if (h->ev_begin) (void)hipEventDestroy(h->ev_begin);
     if (h->ev_end) (void)hipEventDestroy(h->ev_end);
@@ -372,15 +285,11 @@ int srlhip_destroy(srlhip_handle hh) {
 }
 
 int srlhip_obs_dim(srlhip_handle hh) { return hh ? obs_dim_of(reinterpret_cast<Handle *>(hh)->cfg) : SRLHIP_EINVAL; }
-int srlhip_obs_bytes(srlhip_handle hh) { return hh ? (int)obs_bytes_per_env(reinterpret_cast<Handle *>(hh)) : SRLHIP_EINVAL; }
+int srlhip_obs_bytes(srlhip_handle hh) { return hh ? (int)obs_bytes_per_env(reinterpret_cast<Handle *>(hh)->cfg) : SRLHIP_EINVAL; }
 int srlhip_action_dim(srlhip_handle hh) { return hh ? action_dim_of(reinterpret_cast<Handle *>(hh)->cfg) : SRLHIP_EINVAL; }
 int srlhip_num_actions(srlhip_handle hh) { return hh ? num_actions_of(reinterpret_cast<Handle *>(hh)->cfg) : SRLHIP_EINVAL; }
 
-int srlhip_reset_rand_count(srlhip_handle hh) {
-    if (!hh) return SRLHIP_EINVAL;
-    Handle *h = reinterpret_cast<Handle *>(hh);
-    return is_mobile(h->cfg.env_kind) ? mobile_reset_rand_count(h->cfg) : kuka_reset_rand_count(h->cfg);
-}
+int srlhip_reset_rand_count(srlhip_handle hh) { return hh ? reset_rand_count(reinterpret_cast<Handle *>(hh)->cfg) : SRLHIP_EINVAL; }
 
 int srlhip_seed(srlhip_handle hh, const uint8_t *mask, const int64_t *seeds) {
     if (!hh || !seeds) return SRLHIP_EINVAL;
@@ -399,28 +308,26 @@ int srlhip_reset(srlhip_handle hh, const uint8_t *mask, const double *host_rand,
     const int n = h->n;
     const uint8_t *d_mask = nullptr;
     if (mask) {
-        if ((rc = stage_in(h, &h->st_mask, &h->st_mask_sz, mask, n))) return rc;
-        d_mask = static_cast<const uint8_t *>(h->st_mask);
+        if ((rc = stage_in(h, h->st[ST_MASK], mask, n))) return rc;
+        d_mask = static_cast<const uint8_t *>(h->st[ST_MASK].p);
     }
     const double *d_rand = host_rand;
     void *d_obs = obs_out;
-    const size_t ob = obs_bytes_per_env(h) * n;
+    const size_t ob = obs_bytes_per_env(h->cfg) * n;
     if (!h->cfg.io_device) {
         if (host_rand) {
-            size_t bytes = sizeof(double) * (size_t)srlhip_reset_rand_count(hh) * n;
-            if ((rc = stage_in(h, &h->st_rand, &h->st_rand_sz, host_rand, bytes))) return rc;
-            d_rand = static_cast<const double *>(h->st_rand);
+            size_t bytes = sizeof(double) * (size_t)reset_rand_count(h->cfg) * n;
+            if ((rc = stage_in(h, h->st[ST_RAND], host_rand, bytes))) return rc;
+            d_rand = static_cast<const double *>(h->st[ST_RAND].p);
         }
         if (obs_out) {
             // unselected rows must keep the caller's contents
-            if ((rc = stage_in(h, &h->st_obs, &h->st_obs_sz, obs_out, ob))) return rc;
-            d_obs = h->st_obs;
+            if ((rc = stage_in(h, h->st[ST_OBS], obs_out, ob))) return rc;
+            d_obs = h->st[ST_OBS].p;
         }
     }
     const bool pixels = h->cfg.obs_mode == SRLHIP_OBS_RAW_PIXELS;
-    rc = is_mobile(h->cfg.env_kind) ? mobile_reset(h, d_mask, d_rand, pixels ? nullptr : static_cast<float *>(d_obs))
-                                    : kuka_reset(h, d_mask, d_rand, pixels ? nullptr : d_obs);
-    if (rc) return rc;
+    if ((rc = env_ops(h).reset(h, d_mask, d_rand, pixels ? nullptr : d_obs))) return rc;
     if (pixels && d_obs && (rc = raster_render(h, d_obs))) return rc;     // every env is (re)drawn: rows of unselected envs too
     if (!h->cfg.io_device) {
         if (obs_out) SRL_HIP_CHECK(h, hipMemcpyAsync(obs_out, d_obs, ob, hipMemcpyDeviceToHost, h->stream));
@@ -435,59 +342,39 @@ int srlhip_reset(srlhip_handle hh, const uint8_t *mask, const double *host_rand,
 
 namespace {
 // The host-pointer step in two halves (srlhip_step = both, srlhip_step_async / srlhip_step_wait = one each).
-// Small steps (ground-truth observations of a few thousand envs: < 1 MiB each way) are ZERO-COPY: the kernel reads the actions from
-// and writes obs / reward / done to mapped pinned host memory over PCIe, so a step is one launch + one stream sync (measured ~10 us
-// faster per 4096-env step than enqueueing an H2D and a D2H copy).  Larger steps (images, very large batches): one pinned bounce
-// buffer each way -> one H2D and one D2H DMA transfer.
-struct StepLayout { size_t ob, ab, in_noise, in_total, out_rew, out_done, out_total; bool pixels, zero_copy; };
-StepLayout step_layout(const Handle *h) {
-    StepLayout L;
-    const size_t n = (size_t)h->n;
-    L.ob = obs_bytes_per_env(h) * n; L.ab = action_bytes(h);
-    L.in_noise = (L.ab + 15) & ~(size_t)15; L.in_total = L.in_noise + sizeof(double) * n;
-    L.out_rew = (L.ob + 15) & ~(size_t)15; L.out_done = L.out_rew + 4 * n; L.out_total = L.out_done + n;
-    L.pixels = h->cfg.obs_mode == SRLHIP_OBS_RAW_PIXELS;
-    static const bool zc_enabled = [] { const char *v = getenv("SRLHIP_ZERO_COPY"); return !v || atoi(v) != 0; }();   // =0: bounce buffers
-    L.zero_copy = zc_enabled && !h->cfg.io_device && !L.pixels && L.out_total <= ((size_t)1 << 20);
-    return L;
-}
+// (the buffers' layout and the zero-copy rule: api_rules.hpp, StepLayout)
 
 // validate + stage the inputs, enqueue the step (and, in bounce mode, the D2H copy of its outputs) on the handle's stream; no wait
 int host_step_begin(Handle *h, const void *actions, const double *host_noise, bool want_obs) {
     const int n = h->n;
     const StepLayout L = step_layout(h);
     int rc;
-    if (!h->cfg.is_discrete && !continuous_actions_ok(h, static_cast<const float *>(actions), (size_t)n))
+    if (!h->cfg.is_discrete && !continuous_actions_ok(h->cfg, static_cast<const float *>(actions), (size_t)n))
         return h->fail(SRLHIP_EINVAL, "step: non-finite continuous action (a Kuka env's `None` is a row of NaNs)");
     if (host_noise && !all_finite_f64(host_noise, (size_t)n)) return h->fail(SRLHIP_EINVAL, "step: non-finite host_noise");
-    if ((rc = ensure_pinned(h, &h->pin_in, &h->pin_in_sz, L.in_total)) || (rc = ensure_pinned(h, &h->pin_out, &h->pin_out_sz, L.out_total)))
+    if ((rc = ensure_pinned(h, h->pin[PIN_IN], L.in_total)) || (rc = ensure_pinned(h, h->pin[PIN_OUT], L.out_total)))
         return rc;
+    void *const pin_in = h->pin[PIN_IN].p;
     if (h->cfg.is_discrete) {
-        // copy and range-check in one pass: the reference indexes a per-action list (`[-dv, dv, 0, 0, 0, 0][action]`) — an IndexError in
-        // its worker; -1 is its `None` action.  (Checked here so that the per-step Python path needs no reductions over the batch.)
-        const int32_t *src = static_cast<const int32_t *>(actions);
-        int32_t *dst = static_cast<int32_t *>(h->pin_in);
-        const int32_t top = num_actions_of(h->cfg);
-        int32_t bad = 0;
-        for (int i = 0; i < n; i++) { const int32_t a = src[i]; dst[i] = a; bad |= (a < -1) | (a >= top); }
-        if (bad) return h->fail(SRLHIP_EINVAL, "step: discrete action out of range (valid: -1 = no-op, 0 .. num_actions - 1)");
+        if (!copy_discrete_checked(static_cast<const int32_t *>(actions), static_cast<int32_t *>(pin_in), (size_t)n, num_actions_of(h->cfg)))
+            return h->fail(SRLHIP_EINVAL, "step: discrete action out of range (valid: -1 = no-op, 0 .. num_actions - 1)");
     } else {
-        memcpy(h->pin_in, actions, L.ab);
+        memcpy(pin_in, actions, L.ab);
     }
-    if (host_noise) memcpy(static_cast<uint8_t *>(h->pin_in) + L.in_noise, host_noise, sizeof(double) * n);
+    if (host_noise) memcpy(static_cast<uint8_t *>(pin_in) + L.in_noise, host_noise, sizeof(double) * n);
     uint8_t *din = nullptr, *o = nullptr;
     if (L.zero_copy) {
         void *dp = nullptr;
-        SRL_HIP_CHECK(h, hipHostGetDevicePointer(&dp, h->pin_in, 0));
+        SRL_HIP_CHECK(h, hipHostGetDevicePointer(&dp, pin_in, 0));
         din = static_cast<uint8_t *>(dp);
-        SRL_HIP_CHECK(h, hipHostGetDevicePointer(&dp, h->pin_out, 0));
+        SRL_HIP_CHECK(h, hipHostGetDevicePointer(&dp, h->pin[PIN_OUT].p, 0));
         o = static_cast<uint8_t *>(dp);
     } else {
-        if ((rc = ensure(h, &h->st_actions, &h->st_actions_sz, L.in_total)) || (rc = ensure(h, &h->st_obs, &h->st_obs_sz, L.out_total)))
+        if ((rc = ensure(h, h->st[ST_ACTIONS], L.in_total)) || (rc = ensure(h, h->st[ST_OBS], L.out_total)))
             return rc;
-        SRL_HIP_CHECK(h, hipMemcpyAsync(h->st_actions, h->pin_in, host_noise ? L.in_total : L.ab, hipMemcpyHostToDevice, h->stream));
-        din = static_cast<uint8_t *>(h->st_actions);
-        o = static_cast<uint8_t *>(h->st_obs);
+        SRL_HIP_CHECK(h, hipMemcpyAsync(h->st[ST_ACTIONS].p, pin_in, host_noise ? L.in_total : L.ab, hipMemcpyHostToDevice, h->stream));
+        din = static_cast<uint8_t *>(h->st[ST_ACTIONS].p);
+        o = static_cast<uint8_t *>(h->st[ST_OBS].p);
     }
     if (h->persist_on && L.zero_copy && !host_noise) {
         // persistent stepping: no launch — (re)start the resident kernel if it is parked, then hand it the step's sequence number
@@ -520,15 +407,14 @@ int host_step_begin(Handle *h, const void *actions, const double *host_noise, bo
         h->step_signal.start_seq = h->signal_seq + 1;
         h->step_signal_armed = false;
     }
-    rc = is_mobile(h->cfg.env_kind) ? mobile_step(h, din, d_noise, L.pixels ? nullptr : static_cast<float *>(d_obs), d_rew, d_done)
-                                    : kuka_step(h, din, d_noise, L.pixels ? nullptr : d_obs, d_rew, d_done);
+    rc = env_ops(h).step(h, din, d_noise, L.pixels ? nullptr : d_obs, d_rew, d_done);
     h->step_signal = PersistArgs{};
     if (rc) return rc;
     if (h->step_signal_armed) { h->signal_seq += 1; h->signal_wait = true; h->step_signal_armed = false; }
     if (L.pixels && d_obs && (rc = raster_render(h, d_obs))) return rc;
     if (!L.zero_copy) {
         const size_t from = want_obs ? 0 : L.out_rew;
-        SRL_HIP_CHECK(h, hipMemcpyAsync(static_cast<uint8_t *>(h->pin_out) + from, static_cast<uint8_t *>(h->st_obs) + from,
+        SRL_HIP_CHECK(h, hipMemcpyAsync(static_cast<uint8_t *>(h->pin[PIN_OUT].p) + from, static_cast<uint8_t *>(h->st[ST_OBS].p) + from,
                                         L.out_total - from, hipMemcpyDeviceToHost, h->stream));
     }
     return 0;
@@ -589,7 +475,7 @@ int host_step_finish(Handle *h, void *obs_out, float *reward_out, uint8_t *done_
         h->signal_steps++;
     } else
     SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));
-    const uint8_t *po = static_cast<const uint8_t *>(h->pin_out);
+    const uint8_t *po = static_cast<const uint8_t *>(h->pin[PIN_OUT].p);
     if (obs_out) memcpy(obs_out, po, L.ob);
     if (reward_out) memcpy(reward_out, po + L.out_rew, 4 * (size_t)h->n);
     if (done_out) memcpy(done_out, po + L.out_done, h->n);
@@ -602,38 +488,36 @@ struct RolloutPlanes { void *obs; float *rew; uint8_t *done; void *act; };      
 int stage_rollout_planes(Handle *h, int32_t T, RolloutPlanes &d) {
     const size_t tn = (size_t)h->n * (size_t)T;
     int rc;
-    if (d.act) { if ((rc = ensure(h, &h->st_actions, &h->st_actions_sz, action_bytes(h) * (size_t)T))) return rc; d.act = h->st_actions; }
-    if (d.obs) { if ((rc = ensure(h, &h->st_obs, &h->st_obs_sz, obs_bytes_per_env(h) * tn))) return rc; d.obs = h->st_obs; }
-    if (d.rew) { if ((rc = ensure(h, &h->st_rew, &h->st_rew_sz, 4 * tn))) return rc; d.rew = static_cast<float *>(h->st_rew); }
-    if (d.done) { if ((rc = ensure(h, &h->st_done, &h->st_done_sz, tn))) return rc; d.done = static_cast<uint8_t *>(h->st_done); }
+    if (d.act) { if ((rc = ensure(h, h->st[ST_ACTIONS], action_bytes(h->cfg, tn)))) return rc; d.act = h->st[ST_ACTIONS].p; }
+    if (d.obs) { if ((rc = ensure(h, h->st[ST_OBS], obs_bytes_per_env(h->cfg) * tn))) return rc; d.obs = h->st[ST_OBS].p; }
+    if (d.rew) { if ((rc = ensure(h, h->st[ST_REW], 4 * tn))) return rc; d.rew = static_cast<float *>(h->st[ST_REW].p); }
+    if (d.done) { if ((rc = ensure(h, h->st[ST_DONE], tn))) return rc; d.done = static_cast<uint8_t *>(h->st[ST_DONE].p); }
     return 0;
 }
 // ... and back: the planes staged in `dev` (a null dev.act: none was recorded) to the host's, then the call's one synchronisation
 int fetch_rollout_planes(Handle *h, int32_t T, const RolloutPlanes &host, const RolloutPlanes &dev) {
     const size_t tn = (size_t)h->n * (size_t)T;
-    if (host.obs) SRL_HIP_CHECK(h, hipMemcpyAsync(host.obs, dev.obs, obs_bytes_per_env(h) * tn, hipMemcpyDeviceToHost, h->stream));
+    if (host.obs) SRL_HIP_CHECK(h, hipMemcpyAsync(host.obs, dev.obs, obs_bytes_per_env(h->cfg) * tn, hipMemcpyDeviceToHost, h->stream));
     if (host.rew) SRL_HIP_CHECK(h, hipMemcpyAsync(host.rew, dev.rew, 4 * tn, hipMemcpyDeviceToHost, h->stream));
     if (host.done) SRL_HIP_CHECK(h, hipMemcpyAsync(host.done, dev.done, tn, hipMemcpyDeviceToHost, h->stream));
-    if (host.act && dev.act) SRL_HIP_CHECK(h, hipMemcpyAsync(host.act, dev.act, action_bytes(h) * (size_t)T, hipMemcpyDeviceToHost, h->stream));
+    if (host.act && dev.act) SRL_HIP_CHECK(h, hipMemcpyAsync(host.act, dev.act, action_bytes(h->cfg, tn), hipMemcpyDeviceToHost, h->stream));
     SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
 
-// ---- srlhip_rollout_policy / srlhip_rollout_mlp_policy: one host path ---------------------------------------------------------------------
-// Order of the checks, as before the two entry points shared them: the entry point's null policy and struct_size, policy_call_begin
-// (T, a pending step), the entry point's other struct checks (the MLP's hidden and reserved), then everything in rollout_policy.
-// what differs between the two entry points
+// ---- the fused policy rollouts (and srlhip_policy_act's struct checks): one host path -----------------------------------------------------
+// Order of the checks (their text: api_rules.hpp), as before the entry points shared them: check_policy_abi (null policy, struct_size),
+// policy_call_begin (T, a pending step), check_policy_shape (the MLP's hidden and reserved), then — in rollout_policy —
+// check_policy_pointers, check_rollout_policy_config and, on a host-pointer handle after the device is set, check_policy_values.
+// what differs between the entry points
 struct PolicyCall {
     const char *name;              // the entry point, as every message begins
-    const char *what;              // what the struct calls its parameter block: "weights" / "params"
-    size_t elem, count;            // bytes per parameter, parameters per policy
-    int (*kuka)(Handle *, int, const PolicyArgs &, double *, float *, float *, uint8_t *, void *);
+    KukaPolicyLaunch kuka;
     bool sample = false;           // srlhip_rollout_mlp_policy_sampled: the discrete action is drawn from the softmax of the scores
 };
-size_t policy_outputs(const srlhip_config &c) { return (size_t)(c.is_discrete ? num_actions_of(c) : action_dim_of(c)); }
-template <class P> PolicyArgs policy_args(const P &pol, const void *w, int32_t hidden) {
-    return PolicyArgs{w, pol.normalize ? pol.obs_mean : nullptr, pol.normalize ? pol.obs_std : nullptr, pol.clip_obs,
-                      pol.per_env ? 1 : 0, pol.freeze_after_done ? 1 : 0, pol.normalize ? 1 : 0, hidden};
+int refuse(Handle *h, const char *name, const Verdict &v) { return h->fail(v.code, std::string(name) + ": " + v.msg); }      // (built on a failing call only)
+PolicyArgs policy_args(const PolicyView &v) {
+    return PolicyArgs{v.w, v.normalize ? v.mean : nullptr, v.normalize ? v.std : nullptr, v.clip, v.per_env ? 1 : 0, v.freeze ? 1 : 0, v.normalize ? 1 : 0, v.hidden};
 }
 
 int policy_call_begin(Handle *h, const char *name, int32_t T) {
@@ -642,46 +526,44 @@ int policy_call_begin(Handle *h, const char *name, int32_t T) {
     return 0;
 }
 
-int rollout_policy(Handle *h, int32_t T, const PolicyCall &pc, PolicyArgs pa, const RolloutPlanes &host) {
-    const auto fail = [&](int code, const std::string &tail) { return h->fail(code, std::string(pc.name) + ": " + tail); };      // (built on a failing call only)
-    if (!pa.w) return fail(SRLHIP_EINVAL, std::string("null ") + pc.what);
-    if (pa.normalize && (!pa.mean || !pa.std)) return fail(SRLHIP_EINVAL, "normalize needs obs_mean and obs_std");
+int rollout_policy(Handle *h, int32_t T, const PolicyCall &pc, const PolicyView &pv, const RolloutPlanes &host) {
     const srlhip_config &c = h->cfg;
-    // what has no policy kernel: refused by name, the handle stays as it was
-    if (c.rng_mode == SRLHIP_RNG_HOST) return fail(SRLHIP_ENOTSUP, "RNG_HOST is not supported (needs a device RNG mode)");
-    if (!c.auto_reset) return fail(SRLHIP_ENOTSUP, "needs auto_reset");
-    if (c.obs_mode == SRLHIP_OBS_RAW_PIXELS) return fail(SRLHIP_ENOTSUP, "raw_pixels observations are not supported (ground_truth only)");
-    if (c.obs_mode == SRLHIP_OBS_JOINTS) return fail(SRLHIP_ENOTSUP, "the joints observation mode is not supported (ground_truth only)");
-    if (c.obs_mode == SRLHIP_OBS_JOINTS_POSITION) return fail(SRLHIP_ENOTSUP, "the joints_position observation mode is not supported (ground_truth only)");
-    if (c.env_kind == SRLHIP_ENV_KUKA_RAND) return fail(SRLHIP_ENOTSUP, "KukaRandButtonGymEnv is not supported");
-    if (!is_mobile(c.env_kind) && c.kuka_model != SRLHIP_KUKA_MODEL_FULL) return fail(SRLHIP_ENOTSUP, "the lumped Kuka model is not supported");
-    if (pc.sample && !c.is_discrete) return fail(SRLHIP_ENOTSUP, "only discrete actions are sampled (the reference never samples continuous ones)");
+    Verdict v = check_policy_pointers(pv);
+    if (!v.code) v = check_rollout_policy_config(c, pc.sample);
+    if (v.code) return refuse(h, pc.name, v);
     int rc = set_device(h);                            // (parks a resident kernel)
     if (rc) return rc;
-    const size_t D = (size_t)obs_dim_of(c), wcount = pc.count * (pa.per_env ? (size_t)h->n : 1);
+    PolicyArgs pa = policy_args(pv);
+    const size_t D = (size_t)obs_dim_of(c), wcount = policy_param_count(c, pv) * (pv.per_env ? (size_t)h->n : 1), elem = pv.mlp ? 4 : 8;
     RolloutPlanes dev = host;
     std::vector<double> packed;                        // host-pointer handles: [mean D][std D] doubles, then the parameters, one staged block
     if (!c.io_device) {
-        if (!(pc.elem == 8 ? all_finite_f64(static_cast<const double *>(pa.w), wcount) : all_finite_f32(static_cast<const float *>(pa.w), wcount)))
-            return fail(SRLHIP_EINVAL, std::string("non-finite ") + pc.what);
-        if (pa.normalize) {
-            if (!all_finite_f64(pa.mean, D)) return fail(SRLHIP_EINVAL, "non-finite obs_mean");
-            for (size_t d = 0; d < D; d++)
-                if (!(std::isfinite(pa.std[d]) && pa.std[d] > 0.0)) return fail(SRLHIP_EINVAL, "obs_std entries must be finite and > 0");
-        }
-        packed.assign(2 * D + (pc.elem * wcount + 7) / 8, 1.0);
+        if ((v = check_policy_values(pv, wcount, D)).code) return refuse(h, pc.name, v);
+        packed.assign(2 * D + (elem * wcount + 7) / 8, 1.0);
         if (pa.normalize) { memcpy(packed.data(), pa.mean, 8 * D); memcpy(packed.data() + D, pa.std, 8 * D); }
-        memcpy(packed.data() + 2 * D, pa.w, pc.elem * wcount);
-        if ((rc = stage_in(h, &h->st_rand, &h->st_rand_sz, packed.data(), 8 * packed.size()))) return rc;
-        const double *blk = static_cast<const double *>(h->st_rand);
+        memcpy(packed.data() + 2 * D, pa.w, elem * wcount);
+        if ((rc = stage_in(h, h->st[ST_RAND], packed.data(), 8 * packed.size()))) return rc;
+        const double *blk = static_cast<const double *>(h->st[ST_RAND].p);
         pa.w = blk + 2 * D;
         if (pa.normalize) { pa.mean = blk; pa.std = blk + D; }
         if ((rc = stage_rollout_planes(h, T, dev))) return rc;
     }
-    rc = is_mobile(c.env_kind) ? mobile_rollout_policy(h, T, pa, pc.sample, static_cast<float *>(dev.obs), dev.rew, dev.done, dev.act)
-                               : pc.kuka(h, T, pa, h->policy_hdr, static_cast<float *>(dev.obs), dev.rew, dev.done, dev.act);
-    if (rc) return rc;
+    if ((rc = env_ops(h).rollout_policy(h, T, pa, pc.sample, pc.kuka, dev.obs, dev.rew, dev.done, dev.act))) return rc;
     return c.io_device ? 0 : fetch_rollout_planes(h, T, host, dev);      // (`packed` must outlive its copy: the synchronisation is in there)
+}
+
+// the three entry points: one body
+template <class P>
+int rollout_policy_entry(srlhip_handle hh, const PolicyCall &pc, int32_t T, const P *pol, const RolloutPlanes &host) {
+    if (!hh) return SRLHIP_EINVAL;
+    Handle *h = reinterpret_cast<Handle *>(hh);
+    Verdict v = check_policy_abi(pol);
+    if (v.code) return refuse(h, pc.name, v);
+    int rc = policy_call_begin(h, pc.name, T);
+    if (rc) return rc;
+    const PolicyView pv = policy_view(*pol);
+    if ((v = check_policy_shape(pv)).code) return refuse(h, pc.name, v);
+    return rollout_policy(h, T, pc, pv, host);
 }
 }  // namespace
 
@@ -701,9 +583,7 @@ int srlhip_step(srlhip_handle hh, const void *actions, const double *host_noise,
         return host_step_finish(h, obs_out, reward_out, done_out);
     }
     const bool pixels = h->cfg.obs_mode == SRLHIP_OBS_RAW_PIXELS;
-    rc = is_mobile(h->cfg.env_kind) ? mobile_step(h, actions, host_noise, pixels ? nullptr : static_cast<float *>(obs_out), reward_out, done_out)
-                                    : kuka_step(h, actions, host_noise, pixels ? nullptr : obs_out, reward_out, done_out);
-    if (rc) return rc;
+    if ((rc = env_ops(h).step(h, actions, host_noise, pixels ? nullptr : obs_out, reward_out, done_out))) return rc;
     if (pixels && obs_out && (rc = raster_render(h, obs_out))) return rc;
     return 0;
 }
@@ -739,22 +619,19 @@ int srlhip_set_persistent(srlhip_handle hh, int32_t on, int32_t park_us) {
     if (rc) return rc;
     if (!on) { h->persist_on = false; persist_release(h); return 0; }
     if (h->cfg.io_device) return h->fail(SRLHIP_ENOTSUP, "set_persistent: host-pointer handles only");
-    int capacity = 0;
+    int capacity = 0, grid = 0;
     uint32_t eighths = 0;
-    const bool mobile = is_mobile(h->cfg.env_kind);
-    const int blocks = mobile ? mobile_persist_blocks(h, &capacity, &eighths) : kuka_persist_blocks(h, &capacity);
-    if (!mobile) eighths = contiguous_eighths(blocks);
+    const int blocks = env_ops(h).persist_blocks(h, &capacity, &eighths, &grid);
     if (blocks <= 0 || !step_layout(h).zero_copy)
         return h->fail(SRLHIP_ENOTSUP, "set_persistent: needs a MobileRobot env, KukaButtonGymEnv, KukaMovingButtonGymEnv or Kuka2ButtonGymEnv (full model) on a device RNG mode, non-pixel "
                                        "observations, zero-copy step buffers, and a batch whose wavefronts are all resident at once (4096 envs on an MI355X)");
     if ((rc = ensure_signal_buffers(h))) return rc;
     if (!h->persist_stage) {
         const StepLayout L = step_layout(h);
-        if ((rc = ensure_pinned(h, &h->pin_in, &h->pin_in_sz, L.in_total)) || (rc = ensure_pinned(h, &h->pin_out, &h->pin_out_sz, L.out_total))) return rc;
+        if ((rc = ensure_pinned(h, h->pin[PIN_IN], L.in_total)) || (rc = ensure_pinned(h, h->pin[PIN_OUT], L.out_total))) return rc;
         if (hipMalloc(&h->persist_stage, L.out_total + 16) != hipSuccess) return h->fail(SRLHIP_ENOMEM, "set_persistent: hipMalloc failed");
     }
     if (!h->persist_reserved) {
-        const int grid = mobile ? blocks : contiguous_grid(blocks);
         std::lock_guard<std::mutex> lk(g_persist_mu);
         if (g_persist_reserved[h->cfg.device_id & 63] + grid > capacity)
             return h->fail(SRLHIP_ENOTSUP, "set_persistent: the resident kernels of the handles already in persistent mode on this device leave no room for this one");
@@ -794,30 +671,25 @@ int srlhip_rollout(srlhip_handle hh, int32_t T, const void *actions_TN, void *ob
     const RolloutPlanes host{obs_TN, reward_TN, done_TN, act_out_TN};
     RolloutPlanes dev = host;
     if (!h->cfg.io_device) {
-        if (actions_TN && !h->cfg.is_discrete && !continuous_actions_ok(h, static_cast<const float *>(actions_TN), tn))
+        if (actions_TN && !h->cfg.is_discrete && !continuous_actions_ok(h->cfg, static_cast<const float *>(actions_TN), tn))
             return h->fail(SRLHIP_EINVAL, "rollout: non-finite continuous action (a Kuka env's `None` is a row of NaNs)");
-        if (actions_TN) {                              // st_actions holds the given plane: none is recorded (below), none comes back
-            if ((rc = stage_in(h, &h->st_actions, &h->st_actions_sz, actions_TN, action_bytes(h) * (size_t)T))) return rc;
-            d_act = h->st_actions; dev.act = nullptr;
+        if (actions_TN) {                              // ST_ACTIONS holds the given plane: none is recorded (below), none comes back
+            if ((rc = stage_in(h, h->st[ST_ACTIONS], actions_TN, action_bytes(h->cfg, tn)))) return rc;
+            d_act = h->st[ST_ACTIONS].p; dev.act = nullptr;
         }
         if ((rc = stage_rollout_planes(h, T, dev))) return rc;
     }
     if (h->cfg.obs_mode != SRLHIP_OBS_RAW_PIXELS) {
-        rc = is_mobile(h->cfg.env_kind)
-                 ? mobile_rollout(h, T, d_act, static_cast<float *>(dev.obs), dev.rew, dev.done, actions_TN ? nullptr : dev.act)
-                 : kuka_rollout(h, T, d_act, dev.obs, dev.rew, dev.done, actions_TN ? nullptr : dev.act);
-        if (rc) return rc;
+        if ((rc = env_ops(h).rollout(h, T, d_act, dev.obs, dev.rew, dev.done, actions_TN ? nullptr : dev.act))) return rc;
     } else {
         // images are drawn between steps: one stepper launch + one rasteriser launch per step, same stream
-        const size_t a_step = action_bytes(h), o_step = obs_bytes_per_env(h) * n;
+        const size_t a_step = action_bytes(h->cfg, n), o_step = obs_bytes_per_env(h->cfg) * n;
         for (int32_t t = 0; t < T; t++) {
             const void *a_t = d_act ? static_cast<const uint8_t *>(d_act) + (size_t)t * a_step : nullptr;
             void *ao_t = (!actions_TN && dev.act) ? static_cast<uint8_t *>(dev.act) + (size_t)t * a_step : nullptr;
             float *r_t = dev.rew ? dev.rew + (size_t)t * n : nullptr;
             uint8_t *dn_t = dev.done ? dev.done + (size_t)t * n : nullptr;
-            rc = is_mobile(h->cfg.env_kind) ? mobile_rollout(h, 1, a_t, nullptr, r_t, dn_t, ao_t)
-                                            : kuka_rollout(h, 1, a_t, nullptr, r_t, dn_t, ao_t);
-            if (rc) return rc;
+            if ((rc = env_ops(h).rollout(h, 1, a_t, nullptr, r_t, dn_t, ao_t))) return rc;
             if (dev.obs && (rc = raster_render(h, static_cast<uint8_t *>(dev.obs) + (size_t)t * o_step))) return rc;
         }
     }
@@ -826,68 +698,41 @@ int srlhip_rollout(srlhip_handle hh, int32_t T, const void *actions_TN, void *ob
 
 int srlhip_rollout_policy(srlhip_handle hh, int32_t T, const srlhip_linear_policy *pol, void *obs_TN, float *reward_TN,
                           uint8_t *done_TN, void *act_out_TN) {
-    if (!hh) return SRLHIP_EINVAL;
-    Handle *h = reinterpret_cast<Handle *>(hh);
-    if (!pol) return h->fail(SRLHIP_EINVAL, "rollout_policy: null policy");
-    if (pol->struct_size != (int32_t)sizeof(srlhip_linear_policy)) return h->fail(SRLHIP_EINVAL, "rollout_policy: srlhip_linear_policy.struct_size mismatch (ABI)");
-    int rc = policy_call_begin(h, "rollout_policy", T);
-    if (rc) return rc;
-    const PolicyCall pc{"rollout_policy", "weights", 8, (size_t)obs_dim_of(h->cfg) * policy_outputs(h->cfg), kuka_rollout_policy};
-    return rollout_policy(h, T, pc, policy_args(*pol, pol->weights, 0), {obs_TN, reward_TN, done_TN, act_out_TN});
-}
-
-// srlhip_rollout_mlp_policy / srlhip_rollout_mlp_policy_sampled: one body, two names
-static int rollout_mlp_policy_entry(srlhip_handle hh, const std::string &name, bool sample, int32_t T, const srlhip_mlp_policy *pol,
-                                    const RolloutPlanes &host) {
-    if (!hh) return SRLHIP_EINVAL;
-    Handle *h = reinterpret_cast<Handle *>(hh);
-    if (!pol) return h->fail(SRLHIP_EINVAL, name + ": null policy");
-    if (pol->struct_size != (int32_t)sizeof(srlhip_mlp_policy)) return h->fail(SRLHIP_EINVAL, name + ": srlhip_mlp_policy.struct_size mismatch (ABI)");
-    int rc = policy_call_begin(h, name.c_str(), T);
-    if (rc) return rc;
-    if (pol->hidden < 1 || pol->hidden > 128) return h->fail(SRLHIP_EINVAL, name + ": hidden must be in 1..128");
-    if (pol->reserved != 0) return h->fail(SRLHIP_EINVAL, name + ": reserved must be 0");
-    const size_t D = (size_t)obs_dim_of(h->cfg), A = policy_outputs(h->cfg), H = (size_t)pol->hidden;
-    const PolicyCall pc{name.c_str(), "params", 4, H * D + H + A * H + A, sample ? kuka_rollout_mlp_policy_sampled : kuka_rollout_mlp_policy, sample};
-    return rollout_policy(h, T, pc, policy_args(*pol, pol->params, pol->hidden), host);
+    return rollout_policy_entry(hh, {"rollout_policy", kuka_rollout_policy}, T, pol, {obs_TN, reward_TN, done_TN, act_out_TN});
 }
 
 int srlhip_rollout_mlp_policy(srlhip_handle hh, int32_t T, const srlhip_mlp_policy *pol, void *obs_TN, float *reward_TN,
                               uint8_t *done_TN, void *act_out_TN) {
-    return rollout_mlp_policy_entry(hh, "rollout_mlp_policy", false, T, pol, {obs_TN, reward_TN, done_TN, act_out_TN});
+    return rollout_policy_entry(hh, {"rollout_mlp_policy", kuka_rollout_mlp_policy}, T, pol, {obs_TN, reward_TN, done_TN, act_out_TN});
 }
 
 int srlhip_rollout_mlp_policy_sampled(srlhip_handle hh, int32_t T, const srlhip_mlp_policy *pol, void *obs_TN, float *reward_TN,
                                       uint8_t *done_TN, void *act_out_TN) {
-    return rollout_mlp_policy_entry(hh, "rollout_mlp_policy_sampled", true, T, pol, {obs_TN, reward_TN, done_TN, act_out_TN});
+    return rollout_policy_entry(hh, {"rollout_mlp_policy_sampled", kuka_rollout_mlp_policy_sampled, true}, T, pol, {obs_TN, reward_TN, done_TN, act_out_TN});
 }
 
-// srlhip_policy_act: the struct checks and messages of the fused rollouts (policy_call_begin, policy_args), none of their refusals
-// by env kind or observation mode — the call never looks at the env state
+// srlhip_policy_act: the struct checks and messages of the fused rollouts in their order, its own argument checks between them, none
+// of the rollouts' refusals by env kind or observation mode — the call never looks at the env state
 int srlhip_policy_act(srlhip_handle hh, const srlhip_linear_policy *linear, const srlhip_mlp_policy *mlp, int32_t sample, const float *obs,
                       int32_t obs_dim, const uint8_t *done_prev, uint8_t *frozen, void *act_out, double *score_out) {
     if (!hh) return SRLHIP_EINVAL;
     Handle *h = reinterpret_cast<Handle *>(hh);
-    const std::string name = "policy_act";
-    if (!linear == !mlp) return h->fail(SRLHIP_EINVAL, name + ": pass exactly one of the linear and the MLP policy");
-    if (linear && linear->struct_size != (int32_t)sizeof(srlhip_linear_policy)) return h->fail(SRLHIP_EINVAL, name + ": srlhip_linear_policy.struct_size mismatch (ABI)");
-    if (mlp && mlp->struct_size != (int32_t)sizeof(srlhip_mlp_policy)) return h->fail(SRLHIP_EINVAL, name + ": srlhip_mlp_policy.struct_size mismatch (ABI)");
-    int rc = policy_call_begin(h, name.c_str(), 1);
+    const char *name = "policy_act";
+    Verdict v = check_policy_act_which(linear != nullptr, mlp != nullptr);
+    if (!v.code) v = mlp ? check_policy_abi(mlp) : check_policy_abi(linear);
+    if (v.code) return refuse(h, name, v);
+    int rc = policy_call_begin(h, name, 1);
     if (rc) return rc;
-    if (mlp && (mlp->hidden < 1 || mlp->hidden > 128)) return h->fail(SRLHIP_EINVAL, name + ": hidden must be in 1..128");
-    if (mlp && mlp->reserved != 0) return h->fail(SRLHIP_EINVAL, name + ": reserved must be 0");
-    if (obs_dim < 1 || obs_dim > 1024) return h->fail(SRLHIP_EINVAL, name + ": obs_dim must be in 1..1024");
-    if (sample && !mlp) return h->fail(SRLHIP_EINVAL, name + ": only an MLP policy's actions are sampled");
-    const PolicyArgs pa = mlp ? policy_args(*mlp, mlp->params, mlp->hidden) : policy_args(*linear, linear->weights, 0);
-    if (!pa.w) return h->fail(SRLHIP_EINVAL, name + ": null " + (mlp ? "params" : "weights"));
-    if (pa.normalize && (!pa.mean || !pa.std)) return h->fail(SRLHIP_EINVAL, name + ": normalize needs obs_mean and obs_std");
-    if (!obs || !act_out) return h->fail(SRLHIP_EINVAL, name + ": null obs or act_out");
-    if (pa.freeze && !frozen) return h->fail(SRLHIP_EINVAL, name + ": freeze_after_done needs the frozen plane");
+    const PolicyView pv = mlp ? policy_view(*mlp) : policy_view(*linear);
     const srlhip_config &c = h->cfg;
-    if (!c.io_device) return h->fail(SRLHIP_ENOTSUP, name + ": device-pointer handles only (io_device = 1)");
-    if (sample && !c.is_discrete) return h->fail(SRLHIP_ENOTSUP, name + ": only discrete actions are sampled (the reference never samples continuous ones)");
+    v = check_policy_shape(pv);
+    if (!v.code) v = check_policy_act_shape(obs_dim, sample != 0, pv.mlp);
+    if (!v.code) v = check_policy_pointers(pv);
+    if (!v.code) v = check_policy_act_planes(c, pv, sample != 0, obs != nullptr, act_out != nullptr, frozen != nullptr);
+    if (v.code) return refuse(h, name, v);
     if ((rc = set_device(h))) return rc;               // (parks a resident kernel)
-    return policy_act_launch(h, pa, sample != 0, obs_dim, (int)policy_outputs(c), !is_mobile(c.env_kind), obs, done_prev, frozen, act_out, score_out);
+    // none_nan: a frozen env's continuous row is the family's `None` — NaNs for Kuka, zeros for MobileRobot
+    return policy_act_launch(h, policy_args(pv), sample != 0, obs_dim, (int)policy_outputs(c), !is_mobile(c.env_kind), obs, done_prev, frozen, act_out, score_out);
 }
 
 int srlhip_get_state(srlhip_handle hh, int32_t field, void *out) {
@@ -899,7 +744,7 @@ int srlhip_get_state(srlhip_handle hh, int32_t field, void *out) {
     if ((rc = field_lookup(h, field, &d, &elem, &count))) return rc;
     SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));
     if (h->ep_host && (field == SRLHIP_F_LAST_RETURN || field == SRLHIP_F_LAST_LENGTH)) {        // mapped host block (create)
-        memcpy(out, static_cast<const uint8_t *>(h->ep_host) + (field == SRLHIP_F_LAST_LENGTH ? 8 * (size_t)h->n : 0), elem * (size_t)h->n);
+        memcpy(out, field == SRLHIP_F_LAST_LENGTH ? (const void *)episode_lengths(h->ep_host, (size_t)h->n) : episode_returns(h->ep_host), elem * (size_t)h->n);
         return 0;
     }
     SRL_HIP_CHECK(h, hipMemcpy(out, d, elem * count * (size_t)h->n, hipMemcpyDeviceToHost));
@@ -916,7 +761,7 @@ int srlhip_set_state(srlhip_handle hh, int32_t field, const void *in) {
     h->snap_valid = false;                 // (MobileRobot: the rollout's chained snapshot no longer equals the live state)
     SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));
     if (h->ep_host && (field == SRLHIP_F_LAST_RETURN || field == SRLHIP_F_LAST_LENGTH)) {
-        memcpy(static_cast<uint8_t *>(h->ep_host) + (field == SRLHIP_F_LAST_LENGTH ? 8 * (size_t)h->n : 0), in, elem * (size_t)h->n);
+        memcpy(field == SRLHIP_F_LAST_LENGTH ? (void *)episode_lengths(h->ep_host, (size_t)h->n) : episode_returns(h->ep_host), in, elem * (size_t)h->n);
         return 0;
     }
     SRL_HIP_CHECK(h, hipMemcpy(d, in, elem * count * (size_t)h->n, hipMemcpyHostToDevice));
@@ -936,9 +781,9 @@ int srlhip_render(srlhip_handle hh, void *img_out) {
     Handle *h = reinterpret_cast<Handle *>(hh);
     int rc = set_device(h);
     if (rc) return rc;
-    const size_t bytes = (size_t)h->cfg.img_h * h->cfg.img_w * (h->cfg.multi_view ? 6 : 3) * h->n;
+    const size_t bytes = frame_bytes(h->cfg) * h->n;
     void *d_img = img_out;
-    if (!h->cfg.io_device) { if ((rc = ensure(h, &h->st_obs, &h->st_obs_sz, bytes))) return rc; d_img = h->st_obs; }
+    if (!h->cfg.io_device) { if ((rc = ensure(h, h->st[ST_OBS], bytes))) return rc; d_img = h->st[ST_OBS].p; }
     if ((rc = raster_render(h, d_img))) return rc;
     if (!h->cfg.io_device) {
         SRL_HIP_CHECK(h, hipMemcpyAsync(img_out, d_img, bytes, hipMemcpyDeviceToHost, h->stream));
@@ -955,18 +800,15 @@ int srlhip_render_jpeg(srlhip_handle hh, int32_t quality, void *blob_out, int64_
     if (h->step_pending) return h->fail(SRLHIP_EINVAL, "render_jpeg: a srlhip_step_async is pending (call srlhip_step_wait first)");
     int rc = set_device(h);                            // (parks a resident kernel)
     if (rc) return rc;
-    const int ch = h->cfg.multi_view ? 6 : 3;
-    const size_t ns = (size_t)h->n * (ch / 3), frames = ((size_t)h->cfg.img_h * h->cfg.img_w * ch * h->n + 15) & ~(size_t)15;
-    const int64_t cap = blob_cap / (int64_t)ns;
-    // scratch: the frames; on a host-pointer handle also offsets [ns + 1], overflow [ns] and the blob's ns slots of `cap` bytes
-    const size_t off_at = frames, ovf_at = off_at + 8 * (ns + 1), blob_at = (ovf_at + 4 * ns + 15) & ~(size_t)15;
-    if ((rc = ensure(h, &h->st_jpeg, &h->st_jpeg_sz, h->cfg.io_device ? frames : blob_at + (size_t)cap * ns))) return rc;
-    uint8_t *d = static_cast<uint8_t *>(h->st_jpeg);
+    const JpegScratch S = jpeg_scratch(h->cfg, (size_t)h->n, blob_cap);
+    const size_t ns = S.ns;
+    if ((rc = ensure(h, h->st[ST_JPEG], S.bytes(h->cfg.io_device != 0)))) return rc;
+    uint8_t *d = static_cast<uint8_t *>(h->st[ST_JPEG].p);
     if ((rc = raster_render(h, d))) return rc;
-    uint8_t *d_blob = h->cfg.io_device ? static_cast<uint8_t *>(blob_out) : d + blob_at;
-    int64_t *d_off = h->cfg.io_device ? offsets_out : reinterpret_cast<int64_t *>(d + off_at);
-    int32_t *d_ovf = h->cfg.io_device ? overflow_out : reinterpret_cast<int32_t *>(d + ovf_at);
-    if ((rc = jpeg_encode_launch(d, h->n, h->cfg.img_h, h->cfg.img_w, ch, quality, d_blob, cap, d_off, d_ovf, h->stream)))
+    uint8_t *d_blob = h->cfg.io_device ? static_cast<uint8_t *>(blob_out) : d + S.blob_at;
+    int64_t *d_off = h->cfg.io_device ? offsets_out : reinterpret_cast<int64_t *>(d + S.off_at);
+    int32_t *d_ovf = h->cfg.io_device ? overflow_out : reinterpret_cast<int32_t *>(d + S.ovf_at);
+    if ((rc = jpeg_encode_launch(d, h->n, h->cfg.img_h, h->cfg.img_w, S.ch, quality, d_blob, S.cap, d_off, d_ovf, h->stream)))
         return h->fail(rc, "render_jpeg: frames of 8..1024 pixels a side only, or the launch failed");
     if (!h->cfg.io_device) {
         SRL_HIP_CHECK(h, hipMemcpyAsync(offsets_out, d_off, 8 * (ns + 1), hipMemcpyDeviceToHost, h->stream));
@@ -987,8 +829,8 @@ int srlhip_episode_stats(srlhip_handle hh, double *last_return, int32_t *last_le
     SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));
     const size_t n = (size_t)h->n;
     if (h->ep_host) {          // host-pointer handle: the records already are in host memory
-        if (last_return) memcpy(last_return, h->ep_host, 8 * n);
-        if (last_length) memcpy(last_length, static_cast<const uint8_t *>(h->ep_host) + 8 * n, 4 * n);
+        if (last_return) memcpy(last_return, episode_returns(h->ep_host), 8 * n);
+        if (last_length) memcpy(last_length, episode_lengths(h->ep_host, n), 4 * n);
     } else {
         if (last_return) SRL_HIP_CHECK(h, hipMemcpy(last_return, h->stats.last_return, 8 * n, hipMemcpyDeviceToHost));
         if (last_length) SRL_HIP_CHECK(h, hipMemcpy(last_length, h->stats.last_length, 4 * n, hipMemcpyDeviceToHost));
@@ -1001,8 +843,8 @@ int srlhip_episode_records(srlhip_handle hh, const double **last_return, const i
     if (!hh) return SRLHIP_EINVAL;
     Handle *h = reinterpret_cast<Handle *>(hh);
     if (!h->ep_host) return h->fail(SRLHIP_EINVAL, "episode_records: host-pointer handles only (cfg.io_device = 0); device-pointer handles use srlhip_episode_stats_device");
-    if (last_return) *last_return = static_cast<const double *>(h->ep_host);
-    if (last_length) *last_length = reinterpret_cast<const int32_t *>(static_cast<const uint8_t *>(h->ep_host) + 8 * (size_t)h->n);
+    if (last_return) *last_return = episode_returns(h->ep_host);
+    if (last_length) *last_length = episode_lengths(h->ep_host, (size_t)h->n);
     return 0;
 }
 
@@ -1029,9 +871,7 @@ int srlhip_set_kuka_model(srlhip_handle hh, const srlhip_kuka_model *m) {
     if (is_mobile(h->cfg.env_kind)) return h->fail(SRLHIP_EINVAL, "set_kuka_model: not a Kuka handle");
     int rc = set_device(h);
     if (rc) return rc;
-    for (int i = 0; i < 7; i++)
-        if (!(m->mass[i] > 0.0) || !(m->inertia[i][0] > 0.0) || !(m->inertia[i][1] > 0.0) || !(m->inertia[i][2] > 0.0) || !(m->joint_lower[i] < m->joint_upper[i]))
-            return h->fail(SRLHIP_EINVAL, "set_kuka_model: masses and principal inertias must be positive, joint_lower < joint_upper");
+    if (const Verdict v = check_kuka_model(*m); v.code) return h->fail(v.code, v.msg);
     return kuka_set_model(h, reinterpret_cast<const double *>(m));
 }
 
@@ -1046,22 +886,7 @@ int srlhip_set_kuka_tree_model(srlhip_handle hh, const srlhip_kuka_tree_model *m
     Handle *h = reinterpret_cast<Handle *>(hh);
     if (is_mobile(h->cfg.env_kind)) return h->fail(SRLHIP_EINVAL, "set_kuka_tree_model: not a Kuka handle");
     if (h->cfg.kuka_model != SRLHIP_KUKA_MODEL_FULL) return h->fail(SRLHIP_EINVAL, "set_kuka_tree_model: the handle was created with the lumped model");
-    const int nd = (int)m->nd, ns = (int)m->nsphere;
-    if (nd != 12 || ns < 0 || ns > 16 || (int)m->max_generic_rows < 0 || (int)m->max_generic_rows > 6 || (int)m->ee_link != 6 || (int)m->grip_link < 0 || (int)m->grip_link >= nd)
-        return h->fail(SRLHIP_EINVAL, "set_kuka_tree_model: 12 DoFs, <= 16 spheres, end effector = link 6, max_generic_rows <= 6 (the lane group's row bank)");
-    for (int i = 0; i < nd; i++) {
-        const srlhip_kuka_tree_joint &J = m->j[i];
-        const double a2 = J.axis[0] * J.axis[0] + J.axis[1] * J.axis[1] + J.axis[2] * J.axis[2];
-        if (!((int)J.parent < i && (int)J.parent >= -1) || !(J.mass > 0) || !(J.inertia[0] > 0 && J.inertia[3] > 0 && J.inertia[5] > 0) ||
-            !(a2 > 0.999999 && a2 < 1.000001) || !(J.max_force > 0) || !(J.kp > 0))
-            return h->fail(SRLHIP_EINVAL, "set_kuka_tree_model: parents before children, positive masses / inertias / motor gains, unit axes");
-        if (i < 7 && ((int)J.parent != i - 1)) return h->fail(SRLHIP_EINVAL, "set_kuka_tree_model: DoFs 0..6 must be the serial arm");
-    }
-    const int detail = (int)m->solver_detail;
-    if (m->solver_detail != (double)detail || detail < 0 || detail > (SRLHIP_KUKA_DETAIL_ALT_SWEEP | SRLHIP_KUKA_DETAIL_BODY_ORDER | SRLHIP_KUKA_DETAIL_FRICTION2) ||
-        !(m->contact_erp >= 0.0 && m->contact_erp <= 1.0) || !(m->limit_erp >= 0.0 && m->limit_erp <= 1.0) || !(m->linear_slop >= 0.0 && m->linear_slop <= 0.01))
-        return h->fail(SRLHIP_EINVAL, "set_kuka_tree_model: solver_detail is a mask of SRLHIP_KUKA_DETAIL_* bits, erp values in [0, 1], linear_slop in [0, 0.01]");
-    for (int k = 0; k < ns; k++) if ((int)m->s[k].link < 0 || (int)m->s[k].link >= nd || !(m->s[k].r > 0)) return h->fail(SRLHIP_EINVAL, "set_kuka_tree_model: bad sphere");
+    if (const Verdict v = check_kuka_tree_model(*m); v.code) return h->fail(v.code, v.msg);
     return kuka_set_tree_model(h, reinterpret_cast<const double *>(m));
 }
 

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/srlhip.h"
+#include "api_rules.hpp"
 #include "rng.hpp"
 #include "step_signal.hpp"
 
@@ -17,29 +18,29 @@ namespace srl {
 
 // ---- per-env random-stream state (all modes allocated lazily) --------------
 struct RngState {
-    Mt19937View mt;        // RNG_MT19937
-    uint32_t *key;         // [2][N] Philox key (seed lo, hi) — also the action stream in every mode
-    uint64_t *ctr;         // [N] Philox block counter, env stream
-    uint64_t *act_ctr;     // [N] Philox block counter, synthetic-agent action stream
+    Mt19937View mt = {};             // RNG_MT19937
+    uint32_t *key = nullptr;         // [2][N] Philox key (seed lo, hi) — also the action stream in every mode
+    uint64_t *ctr = nullptr;         // [N] Philox block counter, env stream
+    uint64_t *act_ctr = nullptr;     // [N] Philox block counter, synthetic-agent action stream
 };
 
 // ---- episode accounting (bench.Monitor equivalent, environments/utils.py:54)
 struct EpisodeStats {
-    double *ep_return;       // running
-    int32_t *ep_length;      // running
-    double *last_return;     // of the most recently finished episode
-    int32_t *last_length;
-    int32_t *n_finished;
-    double *last_reward;     // reward of the last step, uncast (f64)
+    double *ep_return = nullptr;       // running
+    int32_t *ep_length = nullptr;      // running
+    double *last_return = nullptr;     // of the most recently finished episode
+    int32_t *last_length = nullptr;
+    int32_t *n_finished = nullptr;
+    double *last_reward = nullptr;     // reward of the last step, uncast (f64)
 };
 
 // ---- MobileRobot family: SoA state, f64 exactly as the reference's numpy ---
 struct MobileState {
-    double *pos_x, *pos_y;       // robot_pos[:2]            (mobile_robot_env.py:97)
-    double *tgt_x, *tgt_y;       // target_pos / button_pos[0]
-    double *tgt2_x, *tgt2_y;     // button_pos[1]            (2Target only)
-    int32_t *counter;            // _env_step_counter
-    int32_t *cur_target;         // current_target           (2Target only)
+    double *pos_x = nullptr, *pos_y = nullptr;       // robot_pos[:2]            (mobile_robot_env.py:97)
+    double *tgt_x = nullptr, *tgt_y = nullptr;       // target_pos / button_pos[0]
+    double *tgt2_x = nullptr, *tgt2_y = nullptr;     // button_pos[1]            (2Target only)
+    int32_t *counter = nullptr;                      // _env_step_counter
+    int32_t *cur_target = nullptr;                   // current_target           (2Target only)
 };
 
 struct MobileParams {
@@ -58,13 +59,6 @@ struct MobileSnapSet {
 
 struct Handle;
 
-// mobile.hip
-int mobile_alloc(Handle *h);
-int mobile_reset(Handle *h, const uint8_t *d_mask, const double *d_host_rand, float *d_obs);
-int mobile_step(Handle *h, const void *d_actions, const double *d_noise, float *d_obs, float *d_rew,
-                uint8_t *d_done);
-int mobile_rollout(Handle *h, int T, const void *d_actions, float *d_obs, float *d_rew, uint8_t *d_done,
-                   void *d_act_out);
 // srlhip_rollout_policy / srlhip_rollout_mlp_policy: the policy as the kernels take it (device pointers; mean / std null without
 // normalisation).  hidden == 0: the linear policy, w = float64 [n][D][A] or [D][A]; hidden = H >= 1: the one-hidden-layer MLP,
 // w = float32 [n][P] or [P], P = H D + H + A H + A.  Passed to kernels BY VALUE: the layout is part of their argument block.
@@ -78,32 +72,39 @@ static_assert(sizeof(PolicyArgs) == 48 && offsetof(PolicyArgs, w) == 0 && offset
                   offsetof(PolicyArgs, clip) == 24 && offsetof(PolicyArgs, per_env) == 32 && offsetof(PolicyArgs, freeze) == 36 &&
                   offsetof(PolicyArgs, normalize) == 40 && offsetof(PolicyArgs, hidden) == 44,
               "PolicyArgs is a kernel argument: its layout is what the policy kernels were compiled against");
-// mobile.hip: the linear or the MLP kernel family by pol.hidden; sample: the MLP's discrete action drawn from the softmax of its scores
-int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, bool sample, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
 // kuka_tree_policy.hip / kuka_tree_mlp.hip / kuka_tree_mlp_sample.hip (full model); d_hdr: the handle's 16-double policy header
 int kuka_rollout_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
 int kuka_rollout_mlp_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
 int kuka_rollout_mlp_policy_sampled(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
+using KukaPolicyLaunch = int (*)(Handle *, int, const PolicyArgs &, double *, float *, float *, uint8_t *, void *);
 int kuka_policy_header(Handle *h, double *d_hdr, const PolicyArgs &pol);      // kuka_tree_policy.hip: the one header kernel's launch
+
+// What api.hip asks of an env family, one table per family (mobile.hip, kuka.hip); every pointer is a device pointer.
+struct EnvOps {
+    int (*alloc)(Handle *h);
+    int (*reset)(Handle *h, const uint8_t *d_mask, const double *d_host_rand, void *d_obs);
+    int (*step)(Handle *h, const void *d_actions, const double *d_noise, void *d_obs, float *d_rew, uint8_t *d_done);
+    int (*rollout)(Handle *h, int T, const void *d_actions, void *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
+    // the fused policy rollouts.  MobileRobot: the linear or the MLP kernel family by pol.hidden, with `sample` the MLP's discrete action
+    // drawn from the softmax of its scores; Kuka: `kuka`, the launcher api.hip's PolicyCall names, on the handle's policy header
+    int (*rollout_policy)(Handle *h, int T, const PolicyArgs &pol, bool sample, KukaPolicyLaunch kuka, void *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
+    int (*field)(Handle *h, int field, void **dptr, size_t *elem, int *count);
+    // persistent stepping: the real workgroups of the resident kernel (0: this handle has no persistent form); capacity: how many
+    // workgroups of it the device holds at once; eighths: which of the 8 `done` words it writes; grid: the workgroups it launches
+    int (*persist_blocks)(Handle *h, int *capacity, uint32_t *eighths, int *grid);
+    // launch the resident kernel: MobileRobot's writes the host's planes (pa.host_out), the Kuka kernels take the staging copy
+    // (Handle::persist_stage) and switch to the host's planes themselves; the reward / done planes start pa.rew_dw / pa.done_dw dwords in
+    int (*persist_start)(Handle *h, const void *d_actions, const PersistArgs &pa);
+};
+const EnvOps &mobile_env_ops();      // mobile.hip
+const EnvOps &kuka_env_ops();        // kuka.hip
 // policy_act.hip: srlhip_policy_act behind its argument checks — one launch on the handle's stream, no allocation, no synchronisation.
 // D = floats per row of obs, A = scores per env; none_nan: a frozen env's continuous row is NaNs (Kuka), not zeros (MobileRobot)
 int policy_act_launch(Handle *h, const PolicyArgs &pol, bool sample, int D, int A, bool none_nan, const float *d_obs, const uint8_t *d_done_prev,
                       uint8_t *d_frozen, void *d_act, double *d_score);
-int mobile_field(Handle *h, int field, void **dptr, size_t *elem, int *count);
-int mobile_reset_rand_count(const srlhip_config &c);
-int mobile_persist_blocks(Handle *h, int *capacity, uint32_t *eighths);      // persistent stepping (mobile.hip)
-int mobile_persist_start(Handle *h, const void *d_actions, float *d_obs, float *d_rew, uint8_t *d_done, const PersistArgs &pa);
 
 // kuka.hip
-int kuka_alloc(Handle *h);
 void kuka_free(Handle *h);
-int kuka_reset(Handle *h, const uint8_t *d_mask, const double *d_host_rand, void *d_obs);
-int kuka_step(Handle *h, const void *d_actions, const double *d_noise, void *d_obs, float *d_rew,
-              uint8_t *d_done);
-int kuka_rollout(Handle *h, int T, const void *d_actions, void *d_obs, float *d_rew, uint8_t *d_done,
-                 void *d_act_out);
-int kuka_field(Handle *h, int field, void **dptr, size_t *elem, int *count);
-int kuka_reset_rand_count(const srlhip_config &c);
 int kuka_refresh(Handle *h);
 int kuka_uses_group_kernel(const Handle *h);
 int kuka_set_model(Handle *h, const double *table138);
@@ -117,8 +118,6 @@ hipError_t mt_seed_launch(const Mt19937View &v, int n, const uint8_t *d_mask, co
 int rng_probe_run(int generator, int stream, int n, int stride, const uint32_t *keys, const int32_t *key_len, const uint8_t *mask,
                   const uint64_t *state_in, const int32_t *script, int n_ops, const double *args, int n_args, const int32_t *skip,
                   uint64_t *out, int64_t out_words, uint64_t *state_out, int64_t state_words);
-int kuka_persist_blocks(Handle *h, int *capacity);   // persistent stepping: real workgroups of the resident kernel (0: this handle has no persistent form); capacity: how many the device holds at once
-int kuka_persist_start(Handle *h, const void *d_actions, float *d_obs, float *d_rew, uint8_t *d_done, const PersistArgs &pa);
 
 // raster.hip
 int raster_render(Handle *h, void *d_img);
@@ -135,11 +134,22 @@ int jpeg_encode_launch(const uint8_t *images_dev, int n, int img_h, int img_w, i
 
 struct KukaState;   // defined in kuka.hip
 
+// Grow-only buffers of a handle (ensure / ensure_pinned: contents are not kept across a regrow).  Device memory ...
+struct DevBuf { void *p = nullptr; size_t cap = 0; };
+// ... and mapped, coherent pinned host memory
+struct PinBuf { void *p = nullptr; size_t cap = 0; };
+// staging buffers of the host-pointer calls (io_device == 0).  ST_NOISE: the MT19937 key lengths of srlhip_seed, the synthetic agent's
+// action plane (mobile.hip); ST_RAND: reset draws, seed words, a policy's packed block; ST_JPEG: srlhip_render_jpeg's scratch
+// (api_rules.hpp: JpegScratch; device-pointer handles: the frames).  srlhip_destroy frees the whole array.
+enum StageBuf { ST_ACTIONS, ST_NOISE, ST_OBS, ST_REW, ST_DONE, ST_MASK, ST_RAND, ST_JPEG, ST_COUNT };
+enum PinnedBuf { PIN_IN, PIN_OUT, PIN_COUNT };      // the two bounce buffers of srlhip_step (api_rules.hpp: StepLayout)
+
+// Every member has its initial value here: srlhip_create fills in what it creates, srlhip_destroy releases whatever is set.
 struct Handle {
-    srlhip_config cfg;
-    int n;
-    hipStream_t stream;
-    hipEvent_t ev_begin, ev_end;
+    srlhip_config cfg = {};
+    int n = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     std::string err;
     RngState rng;
     EpisodeStats stats;
@@ -153,28 +163,23 @@ struct Handle {
     bool snap_valid = false;
     // synthetic-agent rollouts of the MobileRobot family: the [T][N] action plane of the NEXT rollout is drawn by spare workgroups
     // of the current rollout's launch (mobile_rollout_ep_k), from the action-stream counters in the snapshot; two planes in turn
-    void *act_plane[2] = {nullptr, nullptr};
-    size_t act_plane_sz[2] = {0, 0};
+    DevBuf act_plane[2];
     bool prefetch_valid = false;
     int prefetch_T = 0, prefetch_buf = 0;
-    KukaState *kuka;
+    KukaState *kuka = nullptr;
     double kuka_tmodel_host[510] = {0};   // host copy of the installed full-model table (srlhip_kuka_tree_model): the rasteriser's gripper joint frames
     std::vector<void *> allocs;      // everything hipMalloc'ed for this handle
-    // staging buffers for io_device == 0
-    void *st_actions, *st_noise, *st_obs, *st_rew, *st_done, *st_mask, *st_rand;
-    size_t st_actions_sz, st_noise_sz, st_obs_sz, st_rew_sz, st_done_sz, st_mask_sz, st_rand_sz;
+    DevBuf st[ST_COUNT];
     // rasteriser: per fixed camera, the unit ray of every pixel + depth / colour of the static scenery behind it
     // (built lazily on the first render; lives in `allocs`)
-    float4 *raster_rays[2];
-    uint32_t *raster_bg[2];
+    float4 *raster_rays[2] = {nullptr, nullptr};
+    uint32_t *raster_bg[2] = {nullptr, nullptr};
     float *raster_grip = nullptr;         // [42][n] full Kuka model: the gripper capsules' end points, then the arm's joint origins (raster_grip_k, refreshed by every render)
-    void *st_jpeg = nullptr;         // srlhip_render_jpeg on a host-pointer handle: blob, then offsets, then overflow flags (grow-only)
-    size_t st_jpeg_sz = 0;
-    void *pin_in, *pin_out;          // pinned host bounce buffers of srlhip_step (host-pointer mode)
-    // host-pointer handles (io_device = 0): stats.last_return / last_length live in ONE mapped pinned host block ([n] f64, then [n] i32)
-    // that the kernels address directly, so the per-step API reads an ended episode's (r, l) without a device copy (srlhip_episode_records)
+    PinBuf pin[PIN_COUNT];
+    // host-pointer handles (io_device = 0): stats.last_return / last_length live in ONE mapped pinned host block (api_rules.hpp:
+    // episode_returns / episode_lengths) that the kernels address directly, so the per-step API reads an ended episode's (r, l) without
+    // a device copy (srlhip_episode_records)
     void *ep_host = nullptr;
-    size_t pin_in_sz, pin_out_sz;
     bool step_pending = false;       // srlhip_step_async enqueued a step that srlhip_step_wait has not collected yet
     // persistent stepping (step_signal.hpp): the mapped control block (PersistHost) and the device words
     bool persist_on = false, persist_running = false, persist_step = false;
@@ -226,37 +231,16 @@ bool dispatch_arm_matched(F &f, C c) {
 template <int... Vs, class F>
 bool dispatch_int(int v, F &&f) { return (((v == Vs) && dispatch_arm_matched(f, Const<Vs>{})) || ...); }
 
-// a grow-only device buffer: at least `bytes` at *buf afterwards (contents are not kept; the caller orders the free against the stream)
-inline int ensure(Handle *h, void **buf, size_t *cap, size_t bytes) {
-    if (*cap >= bytes) return 0;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr; *cap = 0;
-    SRL_HIP_CHECK(h, hipMalloc(buf, bytes));
-    *cap = bytes;
+// a grow-only device buffer: at least `bytes` at b.p afterwards (contents are not kept; the caller orders the free against the stream)
+inline int ensure(Handle *h, DevBuf &b, size_t bytes) {
+    if (b.cap >= bytes) return 0;
+    if (b.p) (void)hipFree(b.p);
+    b = DevBuf{};
+    SRL_HIP_CHECK(h, hipMalloc(&b.p, bytes));
+    b.cap = bytes;
     return 0;
 }
 
-inline int obs_dim_of(const srlhip_config &c) {
-    switch (c.env_kind) {
-        case SRLHIP_ENV_MOBILE_1D: return 1;
-        case SRLHIP_ENV_MOBILE: case SRLHIP_ENV_MOBILE_2TARGET: case SRLHIP_ENV_MOBILE_LINE: return 2;
-        case SRLHIP_ENV_KUKA_BUTTON: case SRLHIP_ENV_KUKA_MOVING: case SRLHIP_ENV_KUKA_2BUTTON: case SRLHIP_ENV_KUKA_RAND:
-            return c.obs_mode == SRLHIP_OBS_JOINTS ? 14 : c.obs_mode == SRLHIP_OBS_JOINTS_POSITION ? 17 : 3;
-    }
-    return 0;
-}
-inline int num_actions_of(const srlhip_config &c) {
-    if (!c.is_discrete) return 0;
-    switch (c.env_kind) {
-        case SRLHIP_ENV_MOBILE_1D: return 2;
-        case SRLHIP_ENV_KUKA_BUTTON: case SRLHIP_ENV_KUKA_MOVING: case SRLHIP_ENV_KUKA_2BUTTON: case SRLHIP_ENV_KUKA_RAND: return 6;
-        default: return 4;
-    }
-}
-inline int action_dim_of(const srlhip_config &c) {
-    if (c.is_discrete) return 1;
-    if (c.env_kind >= SRLHIP_ENV_KUKA_BUTTON) return c.action_joints ? 7 : 3;
-    return 2;
-}
+inline const EnvOps &env_ops(const Handle *h) { return is_mobile(h->cfg.env_kind) ? mobile_env_ops() : kuka_env_ops(); }
 
 }  // namespace srl

@@ -237,13 +237,7 @@ int lane_rollout_launch(Handle *h, const KukaParams &p, dim3 grid, dim3 block, s
 
 }  // namespace
 
-int kuka_reset_rand_count(const srlhip_config &c) {
-    const int init = c.is_discrete ? 10 : 5;
-    if (c.env_kind == SRLHIP_ENV_KUKA_2BUTTON) return (c.random_target ? 4 : 0) + 2 + init;   // kuka_2button_gym_env.py:55-70
-    return (c.env_kind == SRLHIP_ENV_KUKA_MOVING ? 1 : 0) + (c.random_target ? 2 : 0) + (c.env_kind == SRLHIP_ENV_KUKA_RAND ? 20 : 0) + init;
-}
-
-int kuka_alloc(Handle *h) {
+static int kuka_alloc(Handle *h) {
     KukaState *s = new KukaState();
     h->kuka = s;
     const size_t n = (size_t)h->n;
@@ -252,7 +246,7 @@ int kuka_alloc(Handle *h) {
     if ((rc = h->dalloc(&s->d, NDBL * n)) || (rc = h->dalloc(&s->i, NINT * n)) || (rc = h->dalloc(&s->rows, SC_ROWS_TOTAL * n)) || (rc = h->dalloc(&s->objs, 30 * n)) || (rc = h->dalloc(&s->rb, 66 * n)) ||
         (rc = h->dalloc(&s->settled, kStartDoubles)) || (rc = h->dalloc(&s->starts, (size_t)(s->nstarts > 0 ? s->nstarts : 1) * kStartDoubles)))
         return rc;
-    if ((rc = h->dalloc(&s->model, 1))) return rc;
+    if ((rc = h->dalloc(&s->model, 1)) || (rc = h->dalloc(&h->policy_hdr, 16))) return rc;
     {
         Model m; default_model(m);
         SRL_HIP_CHECK(h, hipMemcpyAsync(s->model, &m, sizeof m, hipMemcpyHostToDevice, h->stream));
@@ -288,10 +282,10 @@ int kuka_alloc(Handle *h) {
 
 void kuka_free(Handle *h) { delete h->kuka; h->kuka = nullptr; }
 
-int kuka_reset(Handle *h, const uint8_t *d_mask, const double *d_host_rand, void *d_obs) {
+static int kuka_reset(Handle *h, const uint8_t *d_mask, const double *d_host_rand, void *d_obs) {
     KukaParams p = params_of(h);
     dim3 grid((h->n + kWave - 1) / kWave), block(kWave);
-    const int stride = kuka_reset_rand_count(h->cfg);
+    const int stride = reset_rand_count(h->cfg);
     float *obs = static_cast<float *>(d_obs);
     if (h->cfg.rng_mode == SRLHIP_RNG_HOST && !d_host_rand) return h->fail(SRLHIP_EINVAL, "reset: RNG_HOST needs host_rand");
     if (h->kuka->full) return kuka_tree_reset(h, p, d_mask, d_host_rand, stride, obs);
@@ -350,7 +344,7 @@ static int kuka_group_launch(Handle *h, const KukaParams &p, int T, const void *
                                  : kuka_group_launch_baked(h, p, T, d_actions, d_noise, obs, d_rew, d_done, d_act_out);
 }
 
-int kuka_rollout(Handle *h, int T, const void *d_actions, void *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
+static int kuka_rollout(Handle *h, int T, const void *d_actions, void *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
     KukaParams p = params_of(h);
     if (use_group_kernel(h)) {
         if (h->cfg.rng_mode != SRLHIP_RNG_PHILOX && h->cfg.rng_mode != SRLHIP_RNG_MT19937)
@@ -374,7 +368,7 @@ int kuka_rollout(Handle *h, int T, const void *d_actions, void *d_obs, float *d_
     return hit ? rc : h->fail(SRLHIP_EINVAL, "rollout: needs a device RNG mode (PHILOX or MT19937)");
 }
 
-int kuka_step(Handle *h, const void *d_actions, const double *d_noise, void *d_obs, float *d_rew, uint8_t *d_done) {
+static int kuka_step(Handle *h, const void *d_actions, const double *d_noise, void *d_obs, float *d_rew, uint8_t *d_done) {
     if (h->cfg.rng_mode != SRLHIP_RNG_HOST) return kuka_rollout(h, 1, d_actions, d_obs, d_rew, d_done, nullptr);
     KukaParams p = params_of(h);
     if (use_group_kernel(h)) return kuka_group_launch(h, p, 1, d_actions, d_noise, static_cast<float *>(d_obs), d_rew, d_done, nullptr);
@@ -382,9 +376,24 @@ int kuka_step(Handle *h, const void *d_actions, const double *d_noise, void *d_o
     return lane_rollout_launch<SRLHIP_RNG_HOST>(h, p, grid, block, kLdsBytes, 1, d_actions, d_noise, static_cast<float *>(d_obs), d_rew, d_done, nullptr);
 }
 
-int kuka_persist_blocks(Handle *h, int *capacity) { if (capacity) *capacity = 0; return h->kuka && h->kuka->full ? kuka_tree_persist_blocks(h, capacity) : 0; }
-int kuka_persist_start(Handle *h, const void *d_actions, float *d_obs, float *d_rew, uint8_t *d_done, const PersistArgs &pa) {
-    return kuka_tree_persist_launch(h, params_of(h), d_actions, d_obs, d_rew, d_done, pa);
+// the policy launcher api.hip's PolicyCall selected, on the handle's policy header
+static int kuka_rollout_policy_with(Handle *h, int T, const PolicyArgs &pol, bool, KukaPolicyLaunch launch, void *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
+    return launch(h, T, pol, h->policy_hdr, static_cast<float *>(d_obs), d_rew, d_done, d_act_out);
+}
+
+// persistent stepping: the full model's resident kernel; its grid is the contiguous one (step_signal.hpp), padding workgroups included
+static int kuka_persist_blocks(Handle *h, int *capacity, uint32_t *eighths, int *grid) {
+    if (capacity) *capacity = 0;
+    const int blocks = h->kuka && h->kuka->full ? kuka_tree_persist_blocks(h, capacity) : 0;
+    if (eighths) *eighths = contiguous_eighths(blocks);
+    if (grid) *grid = contiguous_grid(blocks);
+    return blocks;
+}
+// (the kernels take the staging copy and switch to the host's planes themselves)
+static int kuka_persist_start(Handle *h, const void *d_actions, const PersistArgs &pa) {
+    uint32_t *o = static_cast<uint32_t *>(h->persist_stage);
+    return kuka_tree_persist_launch(h, params_of(h), d_actions, reinterpret_cast<float *>(o), reinterpret_cast<float *>(o + pa.rew_dw),
+                                    reinterpret_cast<uint8_t *>(o + pa.done_dw), pa);
 }
 
 // (RasterKukaView: internal.hpp — one definition for this file and raster.hip)
@@ -420,7 +429,7 @@ int kuka_refresh(Handle *h) {
     return 0;
 }
 
-int kuka_field(Handle *h, int field, void **dptr, size_t *elem, int *count) {
+static int kuka_field(Handle *h, int field, void **dptr, size_t *elem, int *count) {
     KukaState *s = h->kuka;
     const size_t n = (size_t)h->n;
     *elem = 8; *count = 1;
@@ -451,6 +460,11 @@ int kuka_field(Handle *h, int field, void **dptr, size_t *elem, int *count) {
             *dptr = s->d + (field == SRLHIP_F_KUKA_GRIPPER_Q ? D_GQ : D_GQD) * n; *count = 5; return 0;
     }
     return h->fail(SRLHIP_EINVAL, "unknown field for KukaButtonGymEnv");
+}
+
+const EnvOps &kuka_env_ops() {
+    static const EnvOps ops = {kuka_alloc, kuka_reset, kuka_step, kuka_rollout, kuka_rollout_policy_with, kuka_field, kuka_persist_blocks, kuka_persist_start};
+    return ops;
 }
 
 }  // namespace srl

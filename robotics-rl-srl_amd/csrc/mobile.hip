@@ -941,16 +941,6 @@ MobileParams params_of(const Handle *h) {
 
 }  // namespace
 
-int mobile_reset_rand_count(const srlhip_config &c) {
-    int base = c.env_kind == SRLHIP_ENV_MOBILE_1D ? 1 : 2;
-    if (!c.random_target) return base;
-    switch (c.env_kind) {
-        case SRLHIP_ENV_MOBILE_1D: case SRLHIP_ENV_MOBILE_LINE: return base + 1;
-        case SRLHIP_ENV_MOBILE_2TARGET: return base + 4;
-        default: return base + 2;
-    }
-}
-
 namespace {
 
 int alloc_state(Handle *h, MobileState &s) {
@@ -977,7 +967,7 @@ constexpr bool policy_combination(int kind, int disc) { return disc || (kind != 
 
 }  // namespace
 
-int mobile_alloc(Handle *h) {
+static int mobile_alloc(Handle *h) {
     int rc = alloc_state(h, h->mobile);
     if (rc) return rc;
     if (h->cfg.rng_mode == SRLHIP_RNG_PHILOX) {
@@ -992,11 +982,12 @@ int mobile_alloc(Handle *h) {
     return 0;
 }
 
-int mobile_reset(Handle *h, const uint8_t *d_mask, const double *d_host_rand, float *d_obs) {
+static int mobile_reset(Handle *h, const uint8_t *d_mask, const double *d_host_rand, void *d_obs_plane) {
+    float *d_obs = static_cast<float *>(d_obs_plane);
     h->snap_valid = false;
     MobileParams p = params_of(h);
     dim3 grid((h->n + kBlock - 1) / kBlock), block(kBlock);
-    int stride = mobile_reset_rand_count(h->cfg);
+    int stride = reset_rand_count(h->cfg);
     if (h->cfg.rng_mode == SRLHIP_RNG_HOST && !d_host_rand) return h->fail(SRLHIP_EINVAL, "reset: RNG_HOST needs host_rand");
     dispatch_int<SRLHIP_RNG_HOST, SRLHIP_RNG_PHILOX, SRLHIP_RNG_MT19937>(h->cfg.rng_mode, [&](auto mode) {
         hipLaunchKernelGGL(mobile_reset_k<decltype(mode)::value>, grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, d_mask,
@@ -1047,7 +1038,7 @@ int launch_rollout_ep(Handle *h, const MobileParams &p, int T, const void *d_act
     const int64_t extra = next_plane ? plane_rows(p, T) * pm.bpr : 0;
     const NextPlane next{next_plane, snap.actr, ep_blocks, pm};
     dim3 grid((unsigned)(ep_blocks + extra)), block(kBlock);
-    const int draws = mobile_reset_rand_count(h->cfg);
+    const int draws = reset_rand_count(h->cfg);
     const int planes = d_obs && d_rew && d_done ? (act_out ? 2 : 1) : 0;   // the fast loop stores without checking
     dispatch_env(p, [&](auto kind, auto disc) {
         dispatch_int<0, 1>(p.shape_reward ? 1 : 0, [&](auto shape) {
@@ -1063,8 +1054,9 @@ int launch_rollout_ep(Handle *h, const MobileParams &p, int T, const void *d_act
 
 }  // namespace
 
-int mobile_rollout(Handle *h, int T, const void *d_actions, float *d_obs, float *d_rew, uint8_t *d_done,
-                   void *d_act_out) {
+static int mobile_rollout(Handle *h, int T, const void *d_actions, void *d_obs_plane, float *d_rew, uint8_t *d_done,
+                          void *d_act_out) {
+    float *d_obs = static_cast<float *>(d_obs_plane);
     MobileParams p = params_of(h);
     if (h->cfg.rng_mode != SRLHIP_RNG_PHILOX && h->cfg.rng_mode != SRLHIP_RNG_MT19937)
         return h->fail(SRLHIP_EINVAL, "rollout: needs a device RNG mode (PHILOX or MT19937)");
@@ -1078,10 +1070,10 @@ int mobile_rollout(Handle *h, int T, const void *d_actions, float *d_obs, float 
             // previous launch's spare workgroups filled (or fills one now), its own spare workgroups fill the other one.
             const size_t bytes = (size_t)T * h->n * (p.is_discrete ? 4 : 8);
             for (int b = 0; b < 2; b++)
-                if (h->act_plane_sz[b] < bytes) {           // regrown: a launch in flight may still read or fill the old plane
+                if (h->act_plane[b].cap < bytes) {           // regrown: a launch in flight may still read or fill the old plane
                     SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));
                     h->prefetch_valid = false;
-                    int rc = ensure(h, &h->act_plane[b], &h->act_plane_sz[b], bytes);
+                    int rc = ensure(h, h->act_plane[b], bytes);
                     if (rc) return rc;
                 }
             int cur = 0;
@@ -1089,10 +1081,10 @@ int mobile_rollout(Handle *h, int T, const void *d_actions, float *d_obs, float 
             else {
                 const PlaneMap pm = plane_map(h->n);
                 hipLaunchKernelGGL(mobile_sample_actions_k, dim3((unsigned)(plane_rows(p, T) * pm.bpr)), dim3(kBlock), 0, h->stream,
-                                   p, h->rng, T, pm, h->act_plane[0]);
+                                   p, h->rng, T, pm, h->act_plane[0].p);
                 SRL_HIP_CHECK(h, hipGetLastError());
             }
-            int rc = launch_rollout_ep(h, p, T, h->act_plane[cur], d_obs, d_rew, d_done, 1, h->act_plane[cur ^ 1], d_act_out);
+            int rc = launch_rollout_ep(h, p, T, h->act_plane[cur].p, d_obs, d_rew, d_done, 1, h->act_plane[cur ^ 1].p, d_act_out);
             if (rc) return rc;
             SRL_HIP_CHECK(h, hipGetLastError());
             h->prefetch_valid = true; h->prefetch_T = T; h->prefetch_buf = cur ^ 1;
@@ -1105,9 +1097,9 @@ int mobile_rollout(Handle *h, int T, const void *d_actions, float *d_obs, float 
         const size_t bytes = (size_t)T * h->n * (p.is_discrete ? 4 : 8);
         void *plane = d_act_out;
         if (!plane) {
-            int rc = ensure(h, &h->st_noise, &h->st_noise_sz, bytes);
+            int rc = ensure(h, h->st[ST_NOISE], bytes);
             if (rc) return rc;
-            plane = h->st_noise;
+            plane = h->st[ST_NOISE].p;
         }
         const PlaneMap pm = plane_map(h->n);
         hipLaunchKernelGGL(mobile_sample_actions_k, dim3((unsigned)(plane_rows(p, T) * pm.bpr)), dim3(kBlock), 0, h->stream,
@@ -1132,7 +1124,8 @@ int mobile_rollout(Handle *h, int T, const void *d_actions, float *d_obs, float 
 
 // srlhip_rollout_policy (pol.hidden == 0: one lane per env) / srlhip_rollout_mlp_policy and, with `sample`, srlhip_rollout_mlp_policy_sampled
 // (16 lanes per env)
-int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, bool sample, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
+static int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, bool sample, KukaPolicyLaunch, void *d_obs_plane, float *d_rew, uint8_t *d_done, void *d_act_out) {
+    float *d_obs = static_cast<float *>(d_obs_plane);
     const MobileParams p = params_of(h);
     if ((h->cfg.rng_mode != SRLHIP_RNG_PHILOX && h->cfg.rng_mode != SRLHIP_RNG_MT19937) || !p.auto_reset)
         return h->fail(SRLHIP_ENOTSUP, std::string(sample ? "rollout_mlp_policy_sampled" : pol.hidden ? "rollout_mlp_policy" : "rollout_policy") + ": needs auto_reset and a device RNG mode (PHILOX or MT19937)");
@@ -1165,9 +1158,10 @@ int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, bool sample, 
     return 0;
 }
 
-int mobile_step(Handle *h, const void *d_actions, const double *d_noise, float *d_obs, float *d_rew,
-                uint8_t *d_done) {
-    if (h->cfg.rng_mode != SRLHIP_RNG_HOST) return mobile_rollout(h, 1, d_actions, d_obs, d_rew, d_done, nullptr);
+static int mobile_step(Handle *h, const void *d_actions, const double *d_noise, void *d_obs_plane, float *d_rew,
+                       uint8_t *d_done) {
+    if (h->cfg.rng_mode != SRLHIP_RNG_HOST) return mobile_rollout(h, 1, d_actions, d_obs_plane, d_rew, d_done, nullptr);
+    float *d_obs = static_cast<float *>(d_obs_plane);
     h->snap_valid = false;
     MobileParams p = params_of(h);
     dim3 grid((h->n + kBlock - 1) / kBlock), block(kBlock);
@@ -1189,8 +1183,8 @@ static const void *mobile_persist_fn(const Handle *h, const MobileParams &p) {
     return fn;
 }
 // workgroups of the resident kernel (0: no persistent form for this handle); capacity: how many the device holds at once;
-// eighths: which of the 8 `done` words it writes
-int mobile_persist_blocks(Handle *h, int *capacity, uint32_t *eighths) {
+// eighths: which of the 8 `done` words it writes; grid: the workgroups it launches (all real)
+static int mobile_persist_blocks(Handle *h, int *capacity, uint32_t *eighths, int *grid_out) {
     if (capacity) *capacity = 0;
     const srlhip_config &c = h->cfg;
     if (!(c.rng_mode == SRLHIP_RNG_PHILOX || c.rng_mode == SRLHIP_RNG_MT19937) || c.obs_mode == SRLHIP_OBS_RAW_PIXELS) return 0;
@@ -1203,9 +1197,13 @@ int mobile_persist_blocks(Handle *h, int *capacity, uint32_t *eighths) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, 0) != hipSuccess) return 0;
     if (capacity) *capacity = per_cu * prop.multiProcessorCount;
     if (eighths) *eighths = strided_eighths(grid);
+    if (grid_out) *grid_out = grid;
     return (long long)per_cu * prop.multiProcessorCount >= grid ? grid : 0;
 }
-int mobile_persist_start(Handle *h, const void *d_actions, float *d_obs, float *d_rew, uint8_t *d_done, const PersistArgs &pa) {
+// (the kernel writes the host's planes)
+static int mobile_persist_start(Handle *h, const void *d_actions, const PersistArgs &pa) {
+    float *d_obs = reinterpret_cast<float *>(pa.host_out), *d_rew = reinterpret_cast<float *>(pa.host_out + pa.rew_dw);
+    uint8_t *d_done = reinterpret_cast<uint8_t *>(pa.host_out + pa.done_dw);
     h->snap_valid = false; h->prefetch_valid = false;
     MobileParams p = params_of(h);
     const void *fn = mobile_persist_fn(h, p);
@@ -1216,7 +1214,7 @@ int mobile_persist_start(Handle *h, const void *d_actions, float *d_obs, float *
     return 0;
 }
 
-int mobile_field(Handle *h, int field, void **dptr, size_t *elem, int *count) {
+static int mobile_field(Handle *h, int field, void **dptr, size_t *elem, int *count) {
     MobileState &s = h->mobile;
     *count = 1;
     switch (field) {
@@ -1230,6 +1228,11 @@ int mobile_field(Handle *h, int field, void **dptr, size_t *elem, int *count) {
         case SRLHIP_F_CUR_TARGET: *dptr = s.cur_target; *elem = 4; return 0;
     }
     return h->fail(SRLHIP_EINVAL, "unknown field for the MobileRobot family");
+}
+
+const EnvOps &mobile_env_ops() {
+    static const EnvOps ops = {mobile_alloc, mobile_reset, mobile_step, mobile_rollout, mobile_rollout_policy, mobile_field, mobile_persist_blocks, mobile_persist_start};
+    return ops;
 }
 
 }  // namespace srl
