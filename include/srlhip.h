@@ -356,6 +356,57 @@ int srlhip_rollout_mlp_policy_sampled(srlhip_handle h, int32_t T, const srlhip_m
 int srlhip_policy_act(srlhip_handle h, const srlhip_linear_policy *linear, const srlhip_mlp_policy *mlp, int32_t sample,
                       const float *obs, int32_t obs_dim, const uint8_t *done_prev, uint8_t *frozen, void *act_out, double *score_out);
 
+/* The policy's action FROM THE FRAME: srlhip_policy_act for the reference's CNN-from-pixels policy (CMA-ES with --srl-model raw_pixels,
+ * rl_baselines/evolution_strategies/cma_es.py: CNNPolicyPytorch), every env with its own network.  A T-step rollout from pixels is
+ * T x (srlhip_cnn_policy_act, srlhip_step), every call enqueue-only on the handle's stream, no host read in the loop.
+ * Device-pointer handles only (cfg.io_device = 1; SRLHIP_ENOTSUP otherwise), cfg.obs_mode = raw pixels (SRLHIP_ENOTSUP otherwise), any env
+ * kind and model: the call reads the handle's frame shape, action space and action-stream counters, never the env state.
+ *   images     uint8 [num_envs][H][W][C], the plane srlhip_step / srlhip_reset write: H = cfg.img_h, W = cfg.img_w, C = 3, or 6 with
+ *              cfg.multi_view.  Every side from 43 to 224 (SRLHIP_ENOTSUP outside: below 43 the third pooled plane is empty).
+ *   params     float32 [num_envs][P] (per_env) or [P], in nn.Module.parameters() order — the layout of a CMA-ES candidate vector:
+ *              conv1.weight [8][C][5][5], norm1.weight [8], norm1.bias [8], conv2.weight [16][8][3][3], norm2.weight [16], norm2.bias [16],
+ *              conv3.weight [32][16][3][3], norm3.weight [32], norm3.bias [32], fc.weight [A][F], fc.bias [A]; A = num_actions or
+ *              action_dim of the handle, F = 32 h3 w3 with h3 x w3 the plane behind the third pool (224 x 224: F = 288 as in the
+ *              reference, P = 8206 at C = 3, A = 6; other sizes: the linear layer the reference would need there).
+ *   done_prev, frozen, act_out: as in srlhip_policy_act (the `None` rows of frozen envs included).
+ *   score_out  NULL, or float32 [num_envs][A]: the scores as they stood in front of the selection (frozen envs included).
+ * NETWORK.  x = (float)(byte / 255.0), NHWC read as NCHW.  Three times: a convolution without bias, stride 2 (5x5 pad 2 to 8 channels,
+ * 3x3 pad 1 to 16, 3x3 pad 1 to 32; plane side (s + 2 pad - k) / 2 + 1), batch-norm, ReLU, max-pool 2x2 (floor).  The batch-norm is
+ * the reference's as it RUNS: never put in eval mode, one observation per forward, so the statistics are this frame's own per-channel
+ * mean and biased variance over the whole conv plane (before the pool), eps = 1e-5; gamma and beta are parameters, running statistics play
+ * no part.  Then the pooled planes flattened channel-major and score_a = fc.bias[a] + sum_f fc.weight[a][f] x_f.
+ * ARITHMETIC (csrc/cnn_policy.hpp is its one text for device and host, built with -ffp-contract=off on both sides, so the device's scores
+ * equal the host program's bit for bit): conv sums in float32, taps in (input channel, row, column) order from +0; a channel's sum and sum
+ * of squares in float64 (partial sums per thread of the workgroup, a fixed pairwise tree over them); mean = S / n, var = max(Q / n - mean^2, 0),
+ * g = gamma / sqrt(var + eps) in float64; y = max((float)(((double)x - mean) g + beta), 0).  The pool is taken BEFORE the normalisation —
+ * the window's max where gamma >= 0, its min where gamma < 0: y is monotone in x in that direction, rounding included, so this is the
+ * pooled value of the normalised plane itself.  The linear layer: float64 from (double)bias, f ascending, rounded to float32 once.
+ * Against the float64 forward the scores agree to float32 rounding of the conv sums (tests/cnn_policy_ref.py has the measured figures).
+ *   selection  on (double)score_a, the functions of srlhip_policy_act (csrc/policy_act.hpp): discrete: the strict argmax, lowest index
+ *            first; continuous: the row score_a; sample != 0 (discrete action modes only): the inverse-CDF draw of
+ *            srlhip_rollout_mlp_policy_sampled word for word, with u from the Philox block at the env's CURRENT action-stream counter c, stream 1.
+ * COUNTER: a sampled call leaves c + 1 for EVERY env, frozen or not, and advances it inside the kernel — a captured call draws fresh
+ * numbers at every replay; K calls from c0 use the blocks c0 .. c0 + K - 1 that srlhip_rollout_mlp_policy_sampled with T = K uses.
+ * A non-sampled call does not touch the counter.
+ * The result for env e depends on its own frame, its parameters, done_prev[e], frozen[e] and its counter alone: not on num_envs, on e,
+ * or on the launch geometry — shards and batch sizes agree bit for bit.
+ * One launch on the handle's stream (one workgroup per env), no allocation, no synchronisation; capturable under srlhip_graph_begin.
+ * SRLHIP_EINVAL: a null policy, a wrong struct_size, reserved != 0, null params / images / act_out, freeze_after_done without the
+ * frozen plane, a pending srlhip_step_async.  SRLHIP_ENOTSUP: a host-pointer handle; an obs_mode other than raw pixels; a side outside
+ * 43..224 (the message names the bound); sample on a continuous action mode (the message names "discrete").  A resident persistent
+ * kernel parks. */
+typedef struct srlhip_cnn_policy {
+    int32_t struct_size;        /* sizeof(srlhip_cnn_policy): ABI check */
+    int32_t per_env;            /* 1: params [num_envs][P]; 0: one [P] for every env */
+    int32_t freeze_after_done;  /* as in srlhip_linear_policy */
+    int32_t reserved;           /* 0 */
+    const float *params;        /* a device pointer */
+} srlhip_cnn_policy;
+int srlhip_cnn_policy_act(srlhip_handle h, const srlhip_cnn_policy *pol, int32_t sample, const uint8_t *images,
+                          const uint8_t *done_prev, uint8_t *frozen, void *act_out, float *score_out);
+/* P of srlhip_cnn_policy for a frame of C channels, H x W, and A outputs; 0 for a shape the call refuses (no handle, no GPU needed) */
+int64_t srlhip_cnn_param_count(int32_t channels, int32_t img_h, int32_t img_w, int32_t outputs);
+
 /* Raw state access (checkpoint / parity): field ids below; arrays are
  * [num_envs] (or [k][num_envs] for vector fields) of the field's own type.
  * Always HOST pointers. */

@@ -735,6 +735,29 @@ int srlhip_policy_act(srlhip_handle hh, const srlhip_linear_policy *linear, cons
     return policy_act_launch(h, policy_args(pv), sample != 0, obs_dim, (int)policy_outputs(c), !is_mobile(c.env_kind), obs, done_prev, frozen, act_out, score_out);
 }
 
+// srlhip_cnn_policy_act: the struct, a pending step, then the planes and the config (api_rules.hpp: check_cnn_policy_abi, check_cnn_policy_act)
+int srlhip_cnn_policy_act(srlhip_handle hh, const srlhip_cnn_policy *pol, int32_t sample, const uint8_t *images, const uint8_t *done_prev,
+                          uint8_t *frozen, void *act_out, float *score_out) {
+    if (!hh) return SRLHIP_EINVAL;
+    Handle *h = reinterpret_cast<Handle *>(hh);
+    const char *name = "cnn_policy_act";
+    Verdict v = check_cnn_policy_abi(pol);
+    if (v.code) return refuse(h, name, v);
+    int rc = policy_call_begin(h, name, 1);
+    if (rc) return rc;
+    const srlhip_config &c = h->cfg;
+    v = check_cnn_policy_act(c, pol->freeze_after_done != 0, sample != 0, images != nullptr, act_out != nullptr, frozen != nullptr);
+    if (v.code) return refuse(h, name, v);
+    if ((rc = set_device(h))) return rc;               // (parks a resident kernel)
+    return cnn_policy_act_launch(h, pol->params, pol->per_env != 0, pol->freeze_after_done != 0, sample != 0, (int)policy_outputs(c), !is_mobile(c.env_kind),
+                                 images, done_prev, frozen, act_out, score_out);
+}
+
+int64_t srlhip_cnn_param_count(int32_t channels, int32_t img_h, int32_t img_w, int32_t outputs) {
+    if ((channels != 3 && channels != 6) || !cnn_side_ok(img_h) || !cnn_side_ok(img_w) || outputs < 1 || outputs > 8) return 0;
+    return (int64_t)cnn_param_count(channels, img_h, img_w, outputs);
+}
+
 int srlhip_get_state(srlhip_handle hh, int32_t field, void *out) {
     if (!hh || !out) return SRLHIP_EINVAL;
     Handle *h = reinterpret_cast<Handle *>(hh);

@@ -282,6 +282,61 @@ inline Verdict check_policy_act_planes(const srlhip_config &c, const PolicyView 
     return kAccepted;
 }
 
+// ---- srlhip_cnn_policy_act: the CNN's shapes and argument checks --------------------------------------------------------------------------
+// The reference's CNNPolicyPytorch (cma_es.py:259-300) on an [H][W][C] frame: conv 5x5 s2 p2 C->8, conv 3x3 s2 p1 8->16, conv 3x3 s2 p1
+// 16->32, each behind it batch-norm, ReLU and a 2x2 max-pool (floor), then a linear layer F -> A.  conv: (x + 2 pad - k) / 2 + 1.
+constexpr int kCnnMinSide = 43, kCnnMaxSide = 224;      // 43: the smallest side whose third conv plane is 2x2 (pool output non-empty)
+constexpr int kCnnCh1 = 8, kCnnCh2 = 16, kCnnCh3 = 32;
+struct CnnShape {
+    int C, H, W;
+    int hc[3], wc[3];              // the conv planes
+    int hp[3], wp[3];              // the pooled planes
+    int F;                         // 32 hp[2] wp[2]: the linear layer's inputs, channel-major
+};
+inline CnnShape cnn_shape(int C, int H, int W) {
+    CnnShape s{};
+    s.C = C; s.H = H; s.W = W;
+    s.hc[0] = (H + 4 - 5) / 2 + 1; s.wc[0] = (W + 4 - 5) / 2 + 1;
+    for (int l = 0; l < 3; l++) {
+        if (l) { s.hc[l] = (s.hp[l - 1] + 2 - 3) / 2 + 1; s.wc[l] = (s.wp[l - 1] + 2 - 3) / 2 + 1; }
+        s.hp[l] = s.hc[l] / 2; s.wp[l] = s.wc[l] / 2;
+    }
+    s.F = kCnnCh3 * s.hp[2] * s.wp[2];
+    return s;
+}
+// the offsets of the eleven blocks of one parameter vector, nn.Module.parameters() order, and their total P
+struct CnnParamLayout { size_t w1, g1, b1, w2, g2, b2, w3, g3, b3, fcw, fcb, total; };
+inline CnnParamLayout cnn_param_layout(int C, int H, int W, int A) {
+    CnnParamLayout L;
+    size_t o = 0;
+    L.w1 = o; o += (size_t)kCnnCh1 * C * 25; L.g1 = o; o += kCnnCh1; L.b1 = o; o += kCnnCh1;
+    L.w2 = o; o += (size_t)kCnnCh2 * kCnnCh1 * 9; L.g2 = o; o += kCnnCh2; L.b2 = o; o += kCnnCh2;
+    L.w3 = o; o += (size_t)kCnnCh3 * kCnnCh2 * 9; L.g3 = o; o += kCnnCh3; L.b3 = o; o += kCnnCh3;
+    L.fcw = o; o += (size_t)A * cnn_shape(C, H, W).F; L.fcb = o; o += (size_t)A;
+    L.total = o;
+    return L;
+}
+inline size_t cnn_param_count(int C, int H, int W, int A) { return cnn_param_layout(C, H, W, A).total; }
+inline bool cnn_side_ok(int side) { return side >= kCnnMinSide && side <= kCnnMaxSide; }
+// srlhip_cnn_policy_act's checks in their order (tails; the entry point prefixes "cnn_policy_act: "): the struct, then the planes and
+// what the handle's config rules out
+inline Verdict check_cnn_policy_abi(const srlhip_cnn_policy *p) {
+    if (!p) return {SRLHIP_EINVAL, "null policy"};
+    if (p->struct_size != (int32_t)sizeof(srlhip_cnn_policy)) return {SRLHIP_EINVAL, "srlhip_cnn_policy.struct_size mismatch (ABI)"};
+    if (p->reserved != 0) return {SRLHIP_EINVAL, "reserved must be 0"};
+    if (!p->params) return {SRLHIP_EINVAL, "null params"};
+    return kAccepted;
+}
+inline Verdict check_cnn_policy_act(const srlhip_config &c, bool freeze, bool sample, bool have_images, bool have_act, bool have_frozen) {
+    if (!have_images || !have_act) return {SRLHIP_EINVAL, "null images or act_out"};
+    if (freeze && !have_frozen) return {SRLHIP_EINVAL, "freeze_after_done needs the frozen plane"};
+    if (!c.io_device) return {SRLHIP_ENOTSUP, "device-pointer handles only (io_device = 1)"};
+    if (c.obs_mode != SRLHIP_OBS_RAW_PIXELS) return {SRLHIP_ENOTSUP, "raw_pixels observations only (the policy reads the handle's frames)"};
+    if (!cnn_side_ok(c.img_h) || !cnn_side_ok(c.img_w)) return {SRLHIP_ENOTSUP, "img_h and img_w must be in 43..224 (below 43 the third pooled plane is empty)"};
+    if (sample && !c.is_discrete) return {SRLHIP_ENOTSUP, "only discrete actions are sampled (the reference never samples continuous ones)"};
+    return kAccepted;
+}
+
 // ---- srlhip_render_jpeg's scratch buffer ------------------------------------------------------------------------------------------------
 // the frames; on a host-pointer handle also offsets i64 [ns + 1], overflow i32 [ns] and the blob's ns slots of `cap` bytes
 struct JpegScratch {

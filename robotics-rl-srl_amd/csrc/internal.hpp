@@ -102,6 +102,10 @@ const EnvOps &kuka_env_ops();        // kuka.hip
 // D = floats per row of obs, A = scores per env; none_nan: a frozen env's continuous row is NaNs (Kuka), not zeros (MobileRobot)
 int policy_act_launch(Handle *h, const PolicyArgs &pol, bool sample, int D, int A, bool none_nan, const float *d_obs, const uint8_t *d_done_prev,
                       uint8_t *d_frozen, void *d_act, double *d_score);
+// cnn_policy.hip: srlhip_cnn_policy_act behind its argument checks — one launch on the handle's stream, no allocation, no synchronisation.
+// The frame shape is the handle's config's; A = scores per env; none_nan as above
+int cnn_policy_act_launch(Handle *h, const float *d_params, bool per_env, bool freeze, bool sample, int A, bool none_nan, const uint8_t *d_images,
+                          const uint8_t *d_done_prev, uint8_t *d_frozen, void *d_act, float *d_score);
 
 // kuka.hip
 void kuka_free(Handle *h);

@@ -12,7 +12,7 @@ the int32 action tensor is read by the stepper in place, and the only host read 
 The `cma` package is not available in this environment; the strategy itself — (mu/mu_w, lambda)-CMA-ES with cumulative
 step-size adaptation and rank-one + rank-mu covariance updates, Hansen's tutorial parameter settings, i.e. what
 `cma.CMAEvolutionStrategy(x0, sigma0, {'popsize': n})` runs — is restated in `CMAES` below as torch tensor code on the same
-device.  Learned-from-pixels policies (the reference's CNNPolicyPytorch) are not part of the device loop.
+device.
 
 --fused-rollout (off by default; the envs ARS fuses; ground-truth observations, --deterministic or --continuous-actions, no frame
 stacking): one generation is reset + ONE srlhip_rollout_mlp_policy launch — the population, cast to float32 as the reference's torch
@@ -27,7 +27,15 @@ draws from the global np.random: no per-env stream could reproduce it either.)
 
 A learned SRL model (--srl-model autoencoder, ...; SRLType.SRL) runs on every path: makeEnv builds a PixelStateVecEnv under the same
 wrappers (ars.py: make_base_env), and --fused-rollout / --fused-sampling become T x (srlhip_policy_act, step + rasteriser, encoder)
-on the env's stream (env.rollout_mlp_policy).  raw_pixels — the reference's CNN-from-pixels policy — is still not part of it."""
+on the env's stream (env.rollout_mlp_policy).
+
+--cnn-policy (off by default; with --srl-model raw_pixels, --num-stack 1): the reference's default form — CNNPolicyPytorch on the frame
+itself (cma_es.py:93-99,259-300), every member its own three-layer CNN whose batch-norm runs in training mode on the one frame it sees.
+makeEnv builds a RawPixelVecEnv (no VecNormalize: the reference has none on raw pixels either, rl_baselines/utils.py:224), the CMA-ES
+vector has cnn_param_count() entries, and member k's action for env k is ONE srlhip_cnn_policy_act launch on the frames where the
+rasteriser left them: the argmax with --deterministic, a draw from the softmax with the env's own action stream by default, the score
+row with --continuous-actions.  --fused-rollout (--fused-sampling included) enqueues the whole generation, T x (srlhip_cnn_policy_act,
+step + rasteriser), with no host read in between (env.rollout_cnn_policy).  Without the flag raw_pixels is refused as before."""
 import math
 import pickle
 import time
@@ -122,6 +130,42 @@ class BatchedMLP(object):
         return torch.bmm(w2, h.unsqueeze(-1)).squeeze(-1) + b2
 
 
+class BatchedCNN(object):
+    """The reference's CNNPolicyPytorch(C, A) on [H][W][C] frames, shape and host forward: parameters in nn.Module.parameters() order
+    (conv1.weight [8][C][5][5], norm1.weight, norm1.bias, conv2.weight [16][8][3][3], norm2.*, conv3.weight [32][16][3][3], norm3.*,
+    fc.weight [A][F], fc.bias [A]); F = 32 h3 w3 follows the frame size (288 at 224 x 224, the reference's constant).  The batch-norm is
+    the reference's as it runs: training mode on one observation, i.e. every frame's own per-channel statistics."""
+    CHANNELS = (8, 16, 32)
+
+    def __init__(self, in_channels, img_h, img_w, out_dim):
+        self.C, self.img_h, self.img_w, self.A = int(in_channels), int(img_h), int(img_w), int(out_dim)
+        h, w = (self.img_h + 4 - 5) // 2 + 1, (self.img_w + 4 - 5) // 2 + 1
+        for _ in range(2):
+            h, w = (h // 2 + 2 - 3) // 2 + 1, (w // 2 + 2 - 3) // 2 + 1
+        self.F = 32 * (h // 2) * (w // 2)
+        assert self.F > 0, "frames of {} x {} leave nothing behind the third pool (sides 43..224)".format(img_h, img_w)
+        self.blocks = [(8, self.C, 5, 5), (8,), (8,), (16, 8, 3, 3), (16,), (16,), (32, 16, 3, 3), (32,), (32,), (self.A, self.F), (self.A,)]
+        self.n_params = int(sum(np.prod(b) for b in self.blocks))
+
+    def split(self, params):
+        out, o = [], 0
+        for b in self.blocks:
+            k = int(np.prod(b))
+            out.append(params[o:o + k].reshape(b)); o += k
+        return out
+
+    def forward(self, params, frames):
+        """params [n_params] (a float tensor), frames uint8 / float [B][H][W][C] -> scores [B][A]; every frame is normalised on its own"""
+        w1, g1, b1, w2, g2, b2, w3, g3, b3, fw, fb = self.split(params)
+        x = (torch.as_tensor(np.asarray(frames, dtype=np.float64) / 255.0)).permute(0, 3, 1, 2).to(params.dtype)
+        for w, g, b, pad in ((w1, g1, b1, 2), (w2, g2, b2, 1), (w3, g3, b3, 1)):
+            x = torch.nn.functional.conv2d(x, w, stride=2, padding=pad)
+            mean, var = x.mean(dim=(2, 3), keepdim=True), x.var(dim=(2, 3), unbiased=False, keepdim=True)
+            x = (x - mean) / torch.sqrt(var + 1e-5) * g.view(1, -1, 1, 1) + b.view(1, -1, 1, 1)
+            x = torch.nn.functional.max_pool2d(torch.relu(x), 2)
+        return x.reshape(x.shape[0], -1) @ fw.T + fb
+
+
 class CMAESModel(object):
     def __init__(self):
         self.policy = None              # BatchedMLP (shape only; the parameters are best_model)
@@ -163,6 +207,9 @@ class CMAESModel(object):
                             help='with --fused-rollout and discrete actions: draw each action from the softmax of the scores inside '
                                  'the fused launch (no --deterministic needed). The draws come from each env\'s own action stream, not '
                                  'from the torch.multinomial generator of the per-step path: same distribution, other bits')
+        parser.add_argument('--cnn-policy', action='store_true', default=False,
+                            help='with --srl-model raw_pixels: the reference\'s CNN-from-pixels policy, one network per member, run on '
+                                 'the device from the rendered frames (srlhip_cnn_policy_act; --num-stack 1, frames of 43..224 a side)')
         return parser
 
     HIDDEN = 100                        # MLPPolicyPytorch(obs_dim, [100], n_actions)
@@ -174,6 +221,15 @@ class CMAESModel(object):
     def check_fused_arguments(args):
         """--fused-sampling against the rest of the arguments, then ARS's rules for --fused-rollout, whose "--deterministic or
         --continuous-actions" requirement --fused-sampling meets; raises ValueError before any env is built."""
+        if CMAESModel.cnn_from_pixels(args):
+            # the CNN-from-pixels path: every action selection has a fused form (the loop of launches samples as the per-step path does)
+            if int(getattr(args, "num_stack", 1)) != 1:
+                raise ValueError("--cnn-policy needs --num-stack 1: the CNN reads one frame")
+            if getattr(args, "fused_sampling", False) and not getattr(args, "fused_rollout", False):
+                raise ValueError("--fused-sampling needs --fused-rollout")
+            if getattr(args, "fused_sampling", False) and getattr(args, "continuous_actions", False):
+                raise ValueError("--fused-sampling needs discrete actions (not --continuous-actions): continuous actions are never sampled")
+            return
         if not getattr(args, "fused_sampling", False):
             return ARSModel.check_fused_arguments(args)
         if not getattr(args, "fused_rollout", False):
@@ -182,6 +238,10 @@ class CMAESModel(object):
             raise ValueError("--fused-sampling needs discrete actions (not --continuous-actions): continuous actions are never sampled")
         met = type(args)(**dict(vars(args), deterministic=True))       # ARS's rules with that one requirement met
         return ARSModel.check_fused_arguments(met)
+
+    @staticmethod
+    def cnn_from_pixels(args):
+        return bool(getattr(args, "cnn_policy", False)) and getattr(args, "srl_model", "ground_truth") == "raw_pixels"
 
     @staticmethod
     def returns_from_planes(reward, done):
@@ -198,6 +258,9 @@ class CMAESModel(object):
         argument rules have asked for --fused-sampling)."""
         sample = self.deterministic is False and not self.continuous_actions       # (None, a model train() has not configured: the argmax)
         kw = {"sample": True} if sample else {}
+        if isinstance(self.policy, BatchedCNN):
+            planes = env.rollout_cnn_policy(T, population.to(torch.float32).contiguous(), per_env=True, freeze_after_done=True, sample=sample)
+            return self.returns_from_planes(planes["reward"], planes["done"])
         planes = env.rollout_mlp_policy(T, population.to(torch.float32).contiguous(), self.policy.H, per_env=True, freeze_after_done=True, **kw)
         return self.returns_from_planes(planes["reward"], planes["done"])
 
@@ -208,6 +271,11 @@ class CMAESModel(object):
     # ---- host-side single-policy interface (replay / enjoy) ----------------------------------------------------------
     def _scores(self, observation):
         assert self.policy is not None and self.best_model is not None, "Error: must train or load model before use"
+        if isinstance(self.policy, BatchedCNN):          # frames [B][H][W][C] (or one frame): obs / 255.0, NHWC -> NCHW as the reference does
+            frames = np.asarray(observation)
+            frames = frames[None] if frames.ndim == 3 else frames
+            # the parameters as the device (and the reference's toTensor) holds them: float32; the forward itself in float64
+            return self.policy.forward(torch.as_tensor(np.asarray(self.best_model, dtype=np.float32)).double(), frames).numpy()
         obs = torch.as_tensor(np.atleast_2d(np.asarray(observation, dtype=np.float64)))
         params = torch.as_tensor(self.best_model, dtype=torch.float64).unsqueeze(0).expand(len(obs), -1)
         return self.policy.forward(params, obs).numpy()
@@ -233,8 +301,16 @@ class CMAESModel(object):
         env_kwargs = dict(env_kwargs or {})
         env_kwargs.setdefault("srl_model", getattr(args, "srl_model", "ground_truth"))
         if env_kwargs["srl_model"] == "raw_pixels":
-            raise NotImplementedError("CMA-ES on the device stack evaluates state policies (MLP); the reference's CNN-from-pixels "
-                                      "policy is not part of it")
+            if not getattr(args, "cnn_policy", False):
+                raise NotImplementedError("CMA-ES on the device stack evaluates state policies (MLP); the reference's CNN-from-pixels "
+                                          "policy is not part of it unless --cnn-policy is given")
+            if int(getattr(args, "num_stack", 1)) != 1:
+                raise ValueError("--cnn-policy needs --num-stack 1: the CNN reads one frame")
+            from srlhip.pixel_env import RawPixelVecEnv
+            from srlhip.vec_env import RNG_MODES, default_rng_mode
+            img_shape = tuple(env_kwargs.get("img_shape") or getattr(args, "img_shape", None) or (224, 224))[-2:]
+            return RawPixelVecEnv(args.env, args.num_cpu, seed=args.seed, img_shape=img_shape, device_id=getattr(args, "device_id", 0),
+                                  rng_mode=RNG_MODES[default_rng_mode("device")], env_kwargs=env_kwargs)
         envs = ARSModel.make_base_env(args, env_kwargs)
         envs = DeviceVecFrameStack(envs, getattr(args, "num_stack", 1))
         envs = DeviceVecNormalize(envs, norm_obs=True, norm_reward=False)
@@ -254,7 +330,13 @@ class CMAESModel(object):
         continuous = bool(getattr(args, "continuous_actions", False))
         none_rows = continuous and ENV_CLASSES[args.env].ENV_KIND >= _lib.ENV_KUKA_BUTTON      # finished members: `None` (Kuka)
         action_space = int(np.prod(env.action_space.shape)) if continuous else env.action_space.n
-        self.policy = BatchedMLP(int(np.prod(env.observation_space.shape)), action_space, self.HIDDEN)
+        cnn = self.cnn_from_pixels(args)
+        if cnn:
+            img_h, img_w, channels = env.observation_space.shape
+            self.policy = BatchedCNN(channels, img_h, img_w, action_space)
+            assert self.policy.n_params == env.cnn_param_count(), (self.policy.n_params, env.cnn_param_count())
+        else:
+            self.policy = BatchedMLP(int(np.prod(env.observation_space.shape)), action_space, self.HIDDEN)
         self.n_population, self.mu, self.sigma = args.num_population, args.mu, args.sigma
         self.continuous_actions, self.deterministic = continuous, bool(getattr(args, "deterministic", False))
         P, dev = self.n_population, env.device
@@ -280,14 +362,17 @@ class CMAESModel(object):
                     r = torch.zeros(P, dtype=torch.float64, device=dev)
                     done = torch.zeros(P, dtype=torch.bool, device=dev)
                     k = 0
+                    params32 = population.to(torch.float32).contiguous() if cnn else None
                     while True:
-                        scores = self.policy.forward(population, obs)
+                        if cnn:                                 # one launch: member k's CNN on env k's frame, the selection included
+                            picked = env.cnn_policy_act(params32, per_env=True, sample=not (continuous or self.deterministic))
+                        scores = picked if cnn else self.policy.forward(population, obs)      # (continuous: the CNN's row IS the scores)
                         if none_rows:
                             actions = torch.where(done.unsqueeze(-1), torch.full_like(scores, float("nan")), scores).to(torch.float32).contiguous()
                         elif continuous:
                             actions = (scores * (~done).unsqueeze(-1).to(scores.dtype)).to(torch.float32).contiguous()
                         else:
-                            a = torch.argmax(scores, dim=1) if self.deterministic else \
+                            a = picked if cnn else torch.argmax(scores, dim=1) if self.deterministic else \
                                 torch.multinomial(torch.softmax(scores, dim=1), 1, generator=gen).squeeze(1)
                             actions = torch.where(done, torch.full_like(a, -1), a).to(torch.int32).contiguous()      # None: "do nothing, as we are done"
                         live += (~done).sum()                   # step += np.sum(~done) (cma_es.py:127)
@@ -304,7 +389,7 @@ class CMAESModel(object):
                 self.es.tell(population, -r)
                 self.best_model = self.es.xbest.cpu().numpy()
                 self.history.append(float(r.mean()))
-        if log_dir is not None:
+        if log_dir is not None and hasattr(env, "save_running_average"):
             env.save_running_average(log_dir)
         env.close()
         return self

@@ -37,7 +37,7 @@ _FIELD_SHAPES = {
 EXPORTS = [
     "srlhip_abi_version", "srlhip_default_config", "srlhip_create", "srlhip_destroy", "srlhip_obs_dim",
     "srlhip_obs_bytes", "srlhip_action_dim", "srlhip_num_actions", "srlhip_seed", "srlhip_reset",
-    "srlhip_reset_rand_count", "srlhip_step", "srlhip_step_async", "srlhip_step_wait", "srlhip_step_pending", "srlhip_set_persistent", "srlhip_rollout", "srlhip_rollout_policy", "srlhip_rollout_mlp_policy", "srlhip_rollout_mlp_policy_sampled", "srlhip_policy_act", "srlhip_get_state", "srlhip_set_state",
+    "srlhip_reset_rand_count", "srlhip_step", "srlhip_step_async", "srlhip_step_wait", "srlhip_step_pending", "srlhip_set_persistent", "srlhip_rollout", "srlhip_rollout_policy", "srlhip_rollout_mlp_policy", "srlhip_rollout_mlp_policy_sampled", "srlhip_policy_act", "srlhip_cnn_policy_act", "srlhip_cnn_param_count", "srlhip_get_state", "srlhip_set_state",
     "srlhip_device_ptr", "srlhip_render", "srlhip_episode_stats", "srlhip_episode_records", "srlhip_episode_stats_device", "srlhip_sync", "srlhip_copy_async", "srlhip_stream", "srlhip_timing_begin",
     "srlhip_timing_end", "srlhip_last_error", "srlhip_selftest_group_primitives", "srlhip_selftest_rng", "srlhip_kuka_kernel", "srlhip_kuka_default_model", "srlhip_set_kuka_model", "srlhip_kuka_tree_default_model", "srlhip_set_kuka_tree_model",
     "srlhip_graph_begin", "srlhip_graph_end", "srlhip_graph_launch", "srlhip_graph_destroy",
@@ -102,6 +102,14 @@ class MlpPolicy(ctypes.Structure):
     ]
 
 
+class CnnPolicy(ctypes.Structure):
+    """struct srlhip_cnn_policy"""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("per_env", ctypes.c_int32), ("freeze_after_done", ctypes.c_int32),
+        ("reserved", ctypes.c_int32), ("params", ctypes.c_void_p),
+    ]
+
+
 class SrlHipError(RuntimeError):
     pass
 
@@ -147,6 +155,9 @@ def load():
     lib.srlhip_rollout_mlp_policy.argtypes = [vp, i32, ctypes.POINTER(MlpPolicy), vp, vp, vp, vp]
     lib.srlhip_rollout_mlp_policy_sampled.argtypes = [vp, i32, ctypes.POINTER(MlpPolicy), vp, vp, vp, vp]
     lib.srlhip_policy_act.argtypes = [vp, ctypes.POINTER(LinearPolicy), ctypes.POINTER(MlpPolicy), i32, vp, i32, vp, vp, vp, vp]
+    lib.srlhip_cnn_policy_act.argtypes = [vp, ctypes.POINTER(CnnPolicy), i32, vp, vp, vp, vp, vp]
+    lib.srlhip_cnn_param_count.argtypes = [i32, i32, i32, i32]
+    lib.srlhip_cnn_param_count.restype = ctypes.c_int64
     lib.srlhip_get_state.argtypes = [vp, i32, vp]
     lib.srlhip_set_state.argtypes = [vp, i32, vp]
     lib.srlhip_device_ptr.argtypes = [vp, i32, ctypes.POINTER(vp)]
@@ -420,6 +431,29 @@ class Handle(object):
         self._check(self._lib.srlhip_policy_act(self._h, None if lin is None else ctypes.byref(lin), None if mlp is None else ctypes.byref(mlp),
                                                 int(bool(sample)), _ptr(obs), int(obs_dim), _ptr(done_prev or None), _ptr(frozen or None),
                                                 _ptr(act_out), _ptr(score_out or None)), "srlhip_policy_act")
+
+    def cnn_param_count(self, A=None):
+        """P of cnn_policy_act for this handle's frames: the reference's CNNPolicyPytorch (conv 5x5 to 8, 3x3 to 16, 3x3 to 32, each with
+        batch-norm, then fc F -> A) in nn.Module.parameters() order; A defaults to num_actions (discrete) or action_dim"""
+        if A is None:
+            A = self.num_actions if self.cfg.is_discrete else self.action_dim
+        p = int(self._lib.srlhip_cnn_param_count(6 if self.cfg.multi_view else 3, self.cfg.img_h, self.cfg.img_w, int(A)))
+        if not p:
+            raise SrlHipError("cnn_param_count: frames of {} x {} are outside the CNN policy's range (sides 43..224)".format(self.cfg.img_h, self.cfg.img_w))
+        return p
+
+    def cnn_policy_act(self, images, act_out, params, per_env=True, freeze_after_done=False, done_prev=None, frozen=None, sample=False,
+                       score_out=None):
+        """srlhip_cnn_policy_act: one launch on the handle's stream that writes every env's action to `act_out` from the uint8
+        [num_envs][H][W][C] plane `images` that step / reset wrote, through the env's own CNN (include/srlhip.h has the contract).
+        Device-pointer raw_pixels handles only; every array argument is a raw device pointer.  `params`: float32 [(num_envs)][P],
+        P = cnn_param_count().  done_prev / frozen / sample as in policy_act; score_out: optional float32 [num_envs][A] plane.
+        Only enqueues: capturable between graph_begin / graph_end."""
+        pol = CnnPolicy()
+        pol.struct_size, pol.per_env, pol.freeze_after_done, pol.reserved = ctypes.sizeof(CnnPolicy), int(bool(per_env)), int(bool(freeze_after_done)), 0
+        pol.params = params
+        self._check(self._lib.srlhip_cnn_policy_act(self._h, ctypes.byref(pol), int(bool(sample)), _ptr(images), _ptr(done_prev or None),
+                                                    _ptr(frozen or None), _ptr(act_out), _ptr(score_out or None)), "srlhip_cnn_policy_act")
 
     def get_state(self, field):
         dtype, k = _FIELD_SHAPES[field]

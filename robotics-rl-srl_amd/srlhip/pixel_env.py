@@ -176,3 +176,106 @@ class PixelStateVecEnv(object):
             self.h.graph_destroy(g)
         self._graphs = {}
         self.h.close()
+
+
+class RawPixelVecEnv(object):
+    """The raw_pixels form without an encoder: the observation IS the uint8 frame the rasteriser writes, and the policy is the
+    reference's CNN-from-pixels (CMA-ES: CNNPolicyPytorch), one network per env, run by srlhip_cnn_policy_act on the frame where it
+    lies.  Constructor arguments as PixelStateVecEnv's less the encoder; reset() / step(actions) return the image tensor
+    ([N][H][W][C] uint8, overwritten by the next call), rewards and dones on the device."""
+
+    def __init__(self, env_id, num_envs, seed=0, img_shape=(64, 64), device_id=0, first_env_id=0, rng_mode=_lib.RNG_PHILOX, env_kwargs=None):
+        kw = dict(env_kwargs or {})
+        cfg = _lib.default_config(ENV_CLASSES[env_id].ENV_KIND)
+        cfg.num_envs, cfg.device_id, cfg.first_env_id, cfg.seed0 = num_envs, device_id, first_env_id, seed
+        cfg.random_target, cfg.multi_view = int(kw.get("random_target", False)), int(bool(kw.get("multi_view", False)) or bool(kw.get("fpv", False)))
+        cfg.obs_mode, cfg.img_h, cfg.img_w = _lib.OBS_RAW_PIXELS, img_shape[0], img_shape[1]
+        cfg.rng_mode, cfg.auto_reset, cfg.io_device = rng_mode, 1, 1
+        for name in ("is_discrete", "shape_reward", "force_down", "action_repeat"):      # as DeviceVecEnv; absent: the env's defaults
+            if name in kw:
+                setattr(cfg, name, int(kw[name]))
+        if "max_distance" in kw:
+            cfg.max_distance = float(kw["max_distance"])
+        self.h = _lib.Handle(cfg)
+        self.cfg, self.env_id, self.num_envs = cfg, env_id, num_envs
+        self.device = torch.device("cuda", device_id)
+        ch = 6 if cfg.multi_view else 3
+        self.images = torch.zeros((num_envs, img_shape[0], img_shape[1], ch), dtype=torch.uint8, device=self.device)
+        self.rewards = torch.zeros((num_envs,), dtype=torch.float32, device=self.device)
+        self.dones = torch.zeros((num_envs,), dtype=torch.uint8, device=self.device)
+        if cfg.is_discrete:
+            self.actions = torch.zeros((num_envs,), dtype=torch.int32, device=self.device)
+            self.action_space = Discrete(self.h.num_actions)
+        else:
+            self.actions = torch.zeros((num_envs, self.h.action_dim), dtype=torch.float32, device=self.device)
+            self.action_space = Box(low=-1, high=1, shape=(self.h.action_dim,), dtype=np.float32)
+        self.observation_space = Box(low=0, high=255, shape=(img_shape[0], img_shape[1], ch), dtype=np.uint8)
+        self._ready = False               # the frame buffer holds the env's current frame (after reset / step / a rollout)
+        self._stream_ptr = self.h.stream()
+        self._stream = self.torch_stream = torch.cuda.ExternalStream(self._stream_ptr, device=self.device)
+
+    def cnn_param_count(self):
+        return self.h.cnn_param_count()
+
+    def reset(self):
+        self._stream.wait_stream(torch.cuda.current_stream(self.device))
+        self.h.reset(obs_out=self.images.data_ptr())
+        torch.cuda.current_stream(self.device).wait_stream(self._stream)
+        self._ready = True
+        return self.images
+
+    def step(self, actions):
+        """actions: device tensor, int32 [N] or float32 [N][action_dim] -> images, rewards, dones (overwritten by the next call)"""
+        self._stream.wait_stream(torch.cuda.current_stream(self.device))
+        self.h.step(actions.data_ptr(), out=(self.images.data_ptr(), self.rewards.data_ptr(), self.dones.data_ptr()))
+        torch.cuda.current_stream(self.device).wait_stream(self._stream)
+        return self.images, self.rewards, self.dones
+
+    def _check_params(self, params, per_env):
+        shape = ((self.num_envs,) if per_env else ()) + (self.cnn_param_count(),)
+        assert params.is_cuda and params.dtype == torch.float32 and params.is_contiguous() and tuple(params.shape) == shape, (tuple(params.shape), shape)
+
+    def cnn_policy_act(self, params, per_env=True, sample=False, act_out=None, score_out=None):
+        """the CNN's actions for the frames the env holds now -> the action tensor (self.actions unless act_out is given); enqueued on
+        the handle's stream, the caller's stream ordered behind it"""
+        assert self._ready, "reset() the env first"
+        self._check_params(params, per_env)
+        act = self.actions if act_out is None else act_out
+        self._stream.wait_stream(torch.cuda.current_stream(self.device))
+        self.h.cnn_policy_act(self.images.data_ptr(), act.data_ptr(), params.data_ptr(), per_env=per_env, sample=sample,
+                              score_out=None if score_out is None else score_out.data_ptr())
+        torch.cuda.current_stream(self.device).wait_stream(self._stream)
+        return act
+
+    def rollout_cnn_policy(self, T, params, per_env=True, freeze_after_done=False, sample=False):
+        """T x (srlhip_cnn_policy_act, step + rasteriser) on the handle's stream, enqueue-only as PixelStateVecEnv._rollout is: the
+        action kernel reads the frame buffer and row t - 1 of the done plane and writes row t of the action plane, the stepper reads
+        that row, writes row t of reward / done and redraws the frames in place.  `params`: float32 CUDA tensor [N][P] (or [P]),
+        P = cnn_param_count() — a CMA-ES population as it is.  Returns {"reward", "done", "actions"}: new [T][N]... tensors (no
+        observation plane: T frames per env is gigabytes)."""
+        assert self._ready, "reset() the env first"
+        self._check_params(params, per_env)
+        n, dev = self.num_envs, self.device
+        ordered = torch.cuda.current_stream(dev).cuda_stream == self.torch_stream.cuda_stream
+        if not ordered:
+            torch.cuda.current_stream(dev).synchronize()
+        with torch.cuda.stream(self.torch_stream):         # the planes are allocated (and later freed) on the stream that fills them
+            out = {"reward": torch.empty((T, n), dtype=torch.float32, device=dev),
+                   "done": torch.empty((T, n), dtype=torch.uint8, device=dev),
+                   "actions": torch.empty((T,) + tuple(self.actions.shape), dtype=self.actions.dtype, device=dev)}
+            frozen = torch.zeros((n,), dtype=torch.uint8, device=dev)
+            images = self.images.data_ptr()
+            for t in range(T):
+                act_t = out["actions"][t]
+                self.h.cnn_policy_act(images, act_t.data_ptr(), params.data_ptr(), per_env=per_env, freeze_after_done=freeze_after_done,
+                                      done_prev=out["done"][t - 1].data_ptr() if t else None, frozen=frozen.data_ptr(), sample=sample)
+                self.h.step(act_t.data_ptr(), out=(images, out["reward"][t].data_ptr(), out["done"][t].data_ptr()))
+        if not ordered:
+            self.h.sync()
+        return out
+
+    def episode_stats(self):
+        return self.h.episode_stats()
+
+    def close(self):
+        self.h.close()
