@@ -407,6 +407,45 @@ int srlhip_cnn_policy_act(srlhip_handle h, const srlhip_cnn_policy *pol, int32_t
 /* P of srlhip_cnn_policy for a frame of C channels, H x W, and A outputs; 0 for a shape the call refuses (no handle, no GPU needed) */
 int64_t srlhip_cnn_param_count(int32_t channels, int32_t img_h, int32_t img_w, int32_t outputs);
 
+/* The LINEAR policy's action from the frame: srlhip_cnn_policy_act for ARS with --srl-model raw_pixels
+ * (rl_baselines/evolution_strategies/ars.py:85,162-166: np.dot(obs.reshape(-1), M +- noise * delta_k) on the uint8 frame as it lies — no
+ * / 255, no VecNormalize).  The call follows srlhip_cnn_policy_act: device-pointer handles only (SRLHIP_ENOTSUP otherwise), cfg.obs_mode =
+ * raw pixels (SRLHIP_ENOTSUP otherwise), any env kind and model, any frame a handle can have (sides 8..1024, C = 3, or 6 with multi_view).
+ *   images     uint8 [num_envs][H][W][C], the plane srlhip_step / srlhip_reset write; a frame is the vector x of D = H W C bytes, NHWC.
+ *   weights    float64 M [D][A], A = num_actions or action_dim of the handle; delta float64 [num_envs / 2][D][A] (paired) or NULL.
+ *   paired = 1 env 2k acts with M + noise delta[k], env 2k + 1 with M - noise delta[k], k counted inside this handle (num_envs even): the
+ *              ARS directions as the population lies in the batch; delta[k] is read once for both.  paired = 0: every env acts with M.
+ *   done_prev, frozen, act_out: as in srlhip_policy_act (the `None` rows of frozen envs included).
+ *   score_out  NULL, or float64 [num_envs][A]: the scores as they stood in front of the selection (frozen envs included).
+ *   selection  discrete: the strict argmax, lowest index first; continuous: the row (float)score_a.  No sampling: a learner that samples
+ *              draws from score_out.
+ * ARITHMETIC (csrc/pixel_policy.hpp is its one text for device and host, -ffp-contract=off on both sides: the device's scores equal the
+ * host program's bit for bit), all float64, no product fused with a sum: t = noise * delta[k][d][a]; w = M[d][a] + t (env 2k) or
+ * M[d][a] - t (env 2k + 1), w = M[d][a] unpaired; term_d = (double)x_d * w; score_a = the sum of the D terms in THIS ORDER, a function of
+ * (D, A) alone: the rows d are cut into chunks of 2048 (the last one ragged); inside chunk c, 256 virtual lanes: lane v owns the rows
+ * 2048 c + v + 256 j, j = 0, 1, ..., and adds their terms in that order to a partial that starts from +0.0 (rows >= D add nothing); the
+ * 256 partials meet in a pairwise tree, far halves first: p[i] = p[i] + p[i + h] for every i < h, for h = 128, 64, ..., 1; p[0] is the
+ * chunk's sum; score_a = chunk 0's sum, + chunk 1's, + chunk 2's, ... in ascending order.  Against any other float64 summation of the
+ * same terms |score_a - s| <= (8 + 8 + chunks) 2^-53 sum_d x_d |w_d[a]| to first order (tests/pixel_policy_ref.py).
+ * The result for env e depends on its frame, M, its direction's delta block, noise, done_prev[e] and frozen[e] alone: not on num_envs, on
+ * e, or on the launch geometry (a small population's launch gives every chunk a workgroup of its own and adds the chunk sums in the same
+ * order) — shards and batch sizes agree bit for bit.
+ * One kernel launch on the handle's stream, no allocation, no synchronisation; capturable under srlhip_graph_begin.  A resident persistent kernel parks.
+ * SRLHIP_EINVAL: a null policy, a wrong struct_size, reserved != 0, null weights / images / act_out, paired without delta, delta without
+ * paired, paired with an odd num_envs, freeze_after_done without the frozen plane, a pending srlhip_step_async.  SRLHIP_ENOTSUP: a
+ * host-pointer handle; an obs_mode other than raw pixels. */
+typedef struct srlhip_pixel_policy {
+    int32_t struct_size;        /* sizeof(srlhip_pixel_policy): ABI check */
+    int32_t paired;             /* 1: the ARS directions (above); 0: delta must be NULL */
+    int32_t freeze_after_done;  /* as in srlhip_linear_policy */
+    int32_t reserved;           /* 0 */
+    const double *weights;      /* M [D][A], a device pointer */
+    const double *delta;        /* [num_envs / 2][D][A], a device pointer, or NULL */
+    double noise;               /* nu */
+} srlhip_pixel_policy;
+int srlhip_pixel_policy_act(srlhip_handle h, const srlhip_pixel_policy *pol, const uint8_t *images,
+                            const uint8_t *done_prev, uint8_t *frozen, void *act_out, double *score_out);
+
 /* Raw state access (checkpoint / parity): field ids below; arrays are
  * [num_envs] (or [k][num_envs] for vector fields) of the field's own type.
  * Always HOST pointers. */

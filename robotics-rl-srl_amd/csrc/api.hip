@@ -251,6 +251,9 @@ int srlhip_create(const srlhip_config *cfg, srlhip_handle *out) {
         st.last_length = episode_lengths(dp, n);
     } else if ((rc = h->dalloc(&st.last_return, n)) || (rc = h->dalloc(&st.last_length, n))) return bail(rc);
     if ((rc = env_ops(h).alloc(h))) return bail(rc);
+    if (cfg->io_device && cfg->obs_mode == SRLHIP_OBS_RAW_PIXELS &&
+        ((rc = h->dalloc(&h->pix_part, (size_t)kPixSplitWgs * kPixSplitSlot)) || (rc = h->dalloc(&h->pix_ticket, (size_t)kPixSplitItems))))
+        return bail(rc);
     std::vector<int64_t> seeds(n);
     for (size_t i = 0; i < n; i++) seeds[i] = cfg->seed0 + cfg->first_env_id + (int64_t)i;   // environments/utils.py:52
     if ((rc = seed_impl(h, nullptr, seeds.data()))) return bail(rc);
@@ -751,6 +754,24 @@ int srlhip_cnn_policy_act(srlhip_handle hh, const srlhip_cnn_policy *pol, int32_
     if ((rc = set_device(h))) return rc;               // (parks a resident kernel)
     return cnn_policy_act_launch(h, pol->params, pol->per_env != 0, pol->freeze_after_done != 0, sample != 0, (int)policy_outputs(c), !is_mobile(c.env_kind),
                                  images, done_prev, frozen, act_out, score_out);
+}
+
+// srlhip_pixel_policy_act: the struct, a pending step, then the planes and the config (api_rules.hpp: check_pixel_policy_abi, check_pixel_policy_act)
+int srlhip_pixel_policy_act(srlhip_handle hh, const srlhip_pixel_policy *pol, const uint8_t *images, const uint8_t *done_prev, uint8_t *frozen,
+                            void *act_out, double *score_out) {
+    if (!hh) return SRLHIP_EINVAL;
+    Handle *h = reinterpret_cast<Handle *>(hh);
+    const char *name = "pixel_policy_act";
+    Verdict v = check_pixel_policy_abi(pol);
+    if (v.code) return refuse(h, name, v);
+    int rc = policy_call_begin(h, name, 1);
+    if (rc) return rc;
+    const srlhip_config &c = h->cfg;
+    v = check_pixel_policy_act(c, pol->paired != 0, pol->freeze_after_done != 0, images != nullptr, act_out != nullptr, frozen != nullptr);
+    if (v.code) return refuse(h, name, v);
+    if ((rc = set_device(h))) return rc;               // (parks a resident kernel)
+    return pixel_policy_act_launch(h, pol->weights, pol->delta, pol->noise, pol->paired != 0, pol->freeze_after_done != 0, (int)policy_outputs(c),
+                                   !is_mobile(c.env_kind), images, done_prev, frozen, act_out, score_out);
 }
 
 int64_t srlhip_cnn_param_count(int32_t channels, int32_t img_h, int32_t img_w, int32_t outputs) {

@@ -337,6 +337,31 @@ inline Verdict check_cnn_policy_act(const srlhip_config &c, bool freeze, bool sa
     return kAccepted;
 }
 
+// ---- srlhip_pixel_policy_act: ARS's linear policy on the frame -----------------------------------------------------------------------------
+// Work items (pairs, or envs when unpaired) below kPixSplitItems give every chunk of rows a workgroup of its own (pixel_policy.hip); the
+// handle then holds the chunk sums of at most kPixSplitWgs workgroups, kPixSplitSlot doubles each, and one ticket word per item
+constexpr int kPixSplitItems = 256, kPixSplitWgs = 2048, kPixSplitSlot = 16;
+inline bool pix_split(int items, int chunks) { return chunks > 1 && items < kPixSplitItems && (int64_t)items * chunks <= kPixSplitWgs; }
+// the checks in their order (tails; the entry point prefixes "pixel_policy_act: "): the struct, then the planes and what the handle's
+// config rules out
+inline Verdict check_pixel_policy_abi(const srlhip_pixel_policy *p) {
+    if (!p) return {SRLHIP_EINVAL, "null policy"};
+    if (p->struct_size != (int32_t)sizeof(srlhip_pixel_policy)) return {SRLHIP_EINVAL, "srlhip_pixel_policy.struct_size mismatch (ABI)"};
+    if (p->reserved != 0) return {SRLHIP_EINVAL, "reserved must be 0"};
+    if (!p->weights) return {SRLHIP_EINVAL, "null weights"};
+    if (p->paired && !p->delta) return {SRLHIP_EINVAL, "paired needs delta"};
+    if (!p->paired && p->delta) return {SRLHIP_EINVAL, "delta must be null unless paired"};
+    return kAccepted;
+}
+inline Verdict check_pixel_policy_act(const srlhip_config &c, bool paired, bool freeze, bool have_images, bool have_act, bool have_frozen) {
+    if (!have_images || !have_act) return {SRLHIP_EINVAL, "null images or act_out"};
+    if (paired && c.num_envs % 2 != 0) return {SRLHIP_EINVAL, "paired needs an even num_envs (env 2k and 2k + 1 share delta[k])"};
+    if (freeze && !have_frozen) return {SRLHIP_EINVAL, "freeze_after_done needs the frozen plane"};
+    if (!c.io_device) return {SRLHIP_ENOTSUP, "device-pointer handles only (io_device = 1)"};
+    if (c.obs_mode != SRLHIP_OBS_RAW_PIXELS) return {SRLHIP_ENOTSUP, "raw_pixels observations only (the policy reads the handle's frames)"};
+    return kAccepted;
+}
+
 // ---- srlhip_render_jpeg's scratch buffer ------------------------------------------------------------------------------------------------
 // the frames; on a host-pointer handle also offsets i64 [ns + 1], overflow i32 [ns] and the blob's ns slots of `cap` bytes
 struct JpegScratch {

@@ -106,6 +106,10 @@ int policy_act_launch(Handle *h, const PolicyArgs &pol, bool sample, int D, int 
 // The frame shape is the handle's config's; A = scores per env; none_nan as above
 int cnn_policy_act_launch(Handle *h, const float *d_params, bool per_env, bool freeze, bool sample, int A, bool none_nan, const uint8_t *d_images,
                           const uint8_t *d_done_prev, uint8_t *d_frozen, void *d_act, float *d_score);
+// pixel_policy.hip: srlhip_pixel_policy_act behind its argument checks — one launch on the handle's stream, no allocation, no synchronisation.  D = the handle's frame bytes; d_delta null
+// unless paired; A, none_nan as above
+int pixel_policy_act_launch(Handle *h, const double *d_weights, const double *d_delta, double noise, bool paired, bool freeze, int A, bool none_nan,
+                            const uint8_t *d_images, const uint8_t *d_done_prev, uint8_t *d_frozen, void *d_act, double *d_score);
 
 // kuka.hip
 void kuka_free(Handle *h);
@@ -199,6 +203,10 @@ struct Handle {
     uint32_t signal_eighths = 0;     // which of the 8 `done` words the armed launch will write (set by the launcher)
     uint32_t persist_eighths = 0;    // which of the 8 `done` words the resident kernel writes
     int persist_reserved = 0;        // workgroups this handle holds in the per-device residency tally (api.hip)
+    // srlhip_pixel_policy_act on a small population (raw-pixel device-pointer handles; allocated with the handle: the call may be captured):
+    // the chunk sums of its split launch and one ticket word per work item (api_rules.hpp: kPixSplit*)
+    double *pix_part = nullptr;
+    uint32_t *pix_ticket = nullptr;
     double *policy_hdr = nullptr;    // srlhip_rollout_policy on a Kuka handle: the scalars its kernel reads (allocated with the handle: the call may be captured)
 
     int fail(int code, const std::string &msg) { err = msg; return code; }

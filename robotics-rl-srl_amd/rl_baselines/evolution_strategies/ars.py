@@ -18,7 +18,15 @@ stays on the per-step path above.  (CMA-ES, whose policy is a 100-unit MLP, has 
 A learned SRL model (--srl-model autoencoder, robotic_priors, ...: state_representation/registry.py, SRLType.SRL) runs on both paths:
 makeEnv then builds a PixelStateVecEnv (stepper, rasteriser, encoder on one stream) and the observation is the encoder's state vector.
 With --fused-rollout an evaluation is T x (srlhip_policy_act, step + rasteriser, encoder) enqueued by env.rollout_policy — the same
-action selection as a kernel of its own, no host read in the loop."""
+action selection as a kernel of its own, no host read in the loop.
+
+--pixel-policy (off by default; with --srl-model raw_pixels, --num-stack 1): the reference's ARS on raw pixels — np.dot(obs.reshape(-1),
+M +- noise * delta_k) on the uint8 frame as it lies, no / 255 and no VecNormalize (ars.py:85,120,162-166).  makeEnv builds a RawPixelVecEnv
+and every env step is ONE srlhip_pixel_policy_act launch on the frames where the rasteriser left them: delta_k is read once for envs 2k
+and 2k + 1, M stays in cache, no per-env weight block is formed.  With --deterministic or --continuous-actions the launch writes the
+actions; otherwise it leaves the scores and the action is drawn from their softmax as on the state path.  --fused-rollout enqueues the
+whole evaluation, T x (srlhip_pixel_policy_act, step + rasteriser), with no host read in between (env.rollout_pixel_policy).  Without the
+flag raw_pixels is refused as before."""
 import pickle
 import time
 
@@ -70,6 +78,9 @@ class ARSModel(object):
                             help='evaluate each population with one fused policy rollout launch (ground-truth observations or a learned SRL model; needs '
                                  '--deterministic or --continuous-actions and --num-stack 1; not KukaRandButton). The training '
                                  'callback then fires once per evaluation, not once per env step')
+        parser.add_argument('--pixel-policy', action='store_true', default=False,
+                            help='with --srl-model raw_pixels: the linear policy on the flattened uint8 frame, run on the device from the '
+                                 'rendered frames (srlhip_pixel_policy_act; --num-stack 1)')
         return parser
 
     # steps after which every env has reported done (`done = counter > max_steps`): MobileRobot 250 (mobile_robot_env.py:336-343),
@@ -87,11 +98,17 @@ class ARSModel(object):
                              "not fused (it stays on the per-step path)")
         if int(getattr(args, "num_stack", 1)) != 1:
             raise ValueError("--fused-rollout needs --num-stack 1: frame stacking is not fused")
-        if getattr(args, "srl_model", "ground_truth") != "ground_truth" and not ARSModel.learned_srl(args):
+        if ARSModel.linear_from_pixels(args):
+            pass                                                  # the frame itself is the observation (srlhip_pixel_policy_act)
+        elif getattr(args, "srl_model", "ground_truth") != "ground_truth" and not ARSModel.learned_srl(args):
             raise ValueError("--fused-rollout needs --srl-model ground_truth or a learned SRL model (raw_pixels, joints and "
                              "joints_position are not fused)")
         if ENV_CLASSES[args.env].ENV_KIND not in ARSModel.FUSED_EPISODE_LIMIT:
             raise ValueError("--fused-rollout: {} has no fused policy rollout".format(args.env))
+
+    @staticmethod
+    def linear_from_pixels(args):
+        return bool(getattr(args, "pixel_policy", False)) and getattr(args, "srl_model", "ground_truth") == "raw_pixels"
 
     @staticmethod
     def learned_srl(args_or_name):
@@ -106,6 +123,14 @@ class ARSModel(object):
         PixelStateVecEnv — stepper, rasteriser and encoder on one stream — with the encoder resolved as HipVecEnv does
         (srl_model_path / state_dim / random-init) and the frame size from env_kwargs["img_shape"] or args.img_shape."""
         device_id = getattr(args, "device_id", 0)
+        if env_kwargs["srl_model"] == "raw_pixels" and getattr(args, "pixel_policy", False):
+            if int(getattr(args, "num_stack", 1)) != 1:
+                raise ValueError("--pixel-policy needs --num-stack 1: the policy reads one frame")
+            from srlhip.pixel_env import RawPixelVecEnv
+            from srlhip.vec_env import RNG_MODES, default_rng_mode
+            img_shape = tuple(env_kwargs.get("img_shape") or getattr(args, "img_shape", None) or (224, 224))[-2:]
+            return RawPixelVecEnv(args.env, args.num_cpu, seed=args.seed, img_shape=img_shape, device_id=device_id,
+                                  rng_mode=RNG_MODES[default_rng_mode("device")], env_kwargs=env_kwargs)
         if not ARSModel.learned_srl(env_kwargs["srl_model"]):
             return DeviceVecEnv(args.env, args.num_cpu, seed=args.seed, env_kwargs=env_kwargs, device_id=device_id)
         from srlhip.pixel_env import PixelStateVecEnv
@@ -133,6 +158,10 @@ class ARSModel(object):
         """One evaluation of the population in one launch (the env was just reset): env 2k runs M + noise * delta_k, env 2k + 1
         runs M - noise * delta_k, frozen after its first done -> (returns [P][2] float64, rows in which some direction was live)."""
         P, (D, A) = delta.shape[0], M.shape
+        if hasattr(env, "rollout_pixel_policy"):           # --pixel-policy: M and delta as they are, no W
+            planes = env.rollout_pixel_policy(T, M, delta, self.exploration_noise, freeze_after_done=True)
+            ret, live_rows = self.returns_from_planes(planes["reward"], planes["done"])
+            return ret.view(P, 2), int(live_rows)
         sign = torch.tensor([1.0, -1.0], dtype=M.dtype, device=M.device).view(1, 2, 1, 1)
         W = (M.unsqueeze(0).unsqueeze(0) + self.exploration_noise * sign * delta.unsqueeze(1)).reshape(2 * P, D, A).contiguous()
         planes = env.rollout_policy(T, W, per_env=True, freeze_after_done=True)
@@ -147,7 +176,10 @@ class ARSModel(object):
     # ---- host-side single-policy interface (replay / enjoy: rl_baselines/evolution_strategies/ars.py:77-104) ------
     def _scores(self, observation, delta=0):
         assert self.M is not None, "Error: must train or load model before use"
-        return np.atleast_2d(np.asarray(observation, dtype=np.float64)) @ (self.M + delta)
+        obs = np.asarray(observation, dtype=np.float64)
+        if obs.ndim > 2:                                   # image observations [n][H][W][C]: the flattened frame, as it lies
+            obs = obs.reshape(len(obs), -1)
+        return np.atleast_2d(obs) @ (self.M + delta)
 
     def getActionProba(self, observation, dones=None, delta=0):
         """Continuous actions: the linear policy's output; discrete: its softmax, one row per observation."""
@@ -173,6 +205,8 @@ class ARSModel(object):
         env_kwargs = dict(env_kwargs or {})
         env_kwargs.setdefault("srl_model", getattr(args, "srl_model", "ground_truth"))
         envs = cls.make_base_env(args, env_kwargs)
+        if cls.linear_from_pixels(args):
+            return envs                                    # the frames themselves: no stack, no VecNormalize (ars.py:120)
         envs = DeviceVecFrameStack(envs, getattr(args, "num_stack", 1))
         if getattr(args, "srl_model", "ground_truth") != "raw_pixels" and getattr(args, "algo_type", "v2") == "v2":
             envs = DeviceVecNormalize(envs, norm_obs=True, norm_reward=False)
@@ -201,6 +235,23 @@ class ARSModel(object):
             a = torch.multinomial(torch.softmax(out, dim=1), 1, generator=generator).squeeze(1)
         return torch.where(active, a, torch.full_like(a, -1)).to(torch.int32).contiguous()
 
+    @staticmethod
+    def pixel_actions(env, M, delta, noise, done, frozen, scores, continuous, deterministic, generator=None):
+        """batched_actions for --pixel-policy: ONE srlhip_pixel_policy_act launch on the frames the env holds.  `done` (bool [2P]) is
+        copied into the call's frozen plane, so finished directions get the `None` rows batched_actions writes (-1; NaN rows on the
+        Kuka envs, zero rows on MobileRobot).  Deterministic or continuous: the kernel's own selection; otherwise the scores come
+        back in `scores` and the action is drawn from their softmax."""
+        frozen.copy_(done)
+        with torch.cuda.stream(env.torch_stream):
+            h = env.h
+            actions = torch.empty_like(env.actions)
+            h.pixel_policy_act(env.images.data_ptr(), actions.data_ptr(), M.data_ptr(), delta=delta.data_ptr(), noise=noise,
+                               freeze_after_done=True, frozen=frozen.data_ptr(), score_out=scores.data_ptr())
+        if continuous or deterministic:
+            return actions
+        a = torch.multinomial(torch.softmax(scores, dim=1), 1, generator=generator).squeeze(1)
+        return torch.where(~done, a, torch.full_like(a, -1)).to(torch.int32).contiguous()
+
     def train(self, args, callback=None, env_kwargs=None, train_kwargs=None):
         assert args.top_population <= args.num_population, \
             "Cannot select top %d, from population of %d." % (args.top_population, args.num_population)
@@ -210,6 +261,7 @@ class ARSModel(object):
         env = self.makeEnv(args, env_kwargs)
         args.__dict__.update(train_kwargs or {})
         fused = bool(getattr(args, "fused_rollout", False))
+        pixels = self.linear_from_pixels(args)
         fused_T = self.FUSED_EPISODE_LIMIT.get(ENV_CLASSES[args.env].ENV_KIND, 0) + 1
         continuous = bool(getattr(args, "continuous_actions", False))
         none_rows = continuous and ENV_CLASSES[args.env].ENV_KIND >= _lib.ENV_KUKA_BUTTON      # finished directions: `None` where the reference has it
@@ -242,9 +294,16 @@ class ARSModel(object):
                     r = torch.zeros((P, 2), dtype=torch.float64, device=dev)
                     done = torch.zeros(2 * P, dtype=torch.bool, device=dev)
                     live_steps = torch.zeros((), dtype=torch.int64, device=dev)      # env steps taken while some direction was still running
+                    if pixels:
+                        frozen = torch.zeros(2 * P, dtype=torch.uint8, device=dev)
+                        scores = torch.zeros((2 * P, action_space), dtype=torch.float64, device=dev)
                     while True:
-                        actions = self.batched_actions(obs, M, delta, self.exploration_noise, ~done, continuous,
-                                                       self.deterministic, gen, none_rows)
+                        if pixels:
+                            actions = self.pixel_actions(env, M, delta, self.exploration_noise, done, frozen, scores, continuous,
+                                                         self.deterministic, gen)
+                        else:
+                            actions = self.batched_actions(obs, M, delta, self.exploration_noise, ~done, continuous,
+                                                           self.deterministic, gen, none_rows)
                         live_steps += (~done).any().to(torch.int64)
                         obs, reward, new_done = env.step(actions)
                         step += P

@@ -37,7 +37,7 @@ _FIELD_SHAPES = {
 EXPORTS = [
     "srlhip_abi_version", "srlhip_default_config", "srlhip_create", "srlhip_destroy", "srlhip_obs_dim",
     "srlhip_obs_bytes", "srlhip_action_dim", "srlhip_num_actions", "srlhip_seed", "srlhip_reset",
-    "srlhip_reset_rand_count", "srlhip_step", "srlhip_step_async", "srlhip_step_wait", "srlhip_step_pending", "srlhip_set_persistent", "srlhip_rollout", "srlhip_rollout_policy", "srlhip_rollout_mlp_policy", "srlhip_rollout_mlp_policy_sampled", "srlhip_policy_act", "srlhip_cnn_policy_act", "srlhip_cnn_param_count", "srlhip_get_state", "srlhip_set_state",
+    "srlhip_reset_rand_count", "srlhip_step", "srlhip_step_async", "srlhip_step_wait", "srlhip_step_pending", "srlhip_set_persistent", "srlhip_rollout", "srlhip_rollout_policy", "srlhip_rollout_mlp_policy", "srlhip_rollout_mlp_policy_sampled", "srlhip_policy_act", "srlhip_cnn_policy_act", "srlhip_cnn_param_count", "srlhip_pixel_policy_act", "srlhip_get_state", "srlhip_set_state",
     "srlhip_device_ptr", "srlhip_render", "srlhip_episode_stats", "srlhip_episode_records", "srlhip_episode_stats_device", "srlhip_sync", "srlhip_copy_async", "srlhip_stream", "srlhip_timing_begin",
     "srlhip_timing_end", "srlhip_last_error", "srlhip_selftest_group_primitives", "srlhip_selftest_rng", "srlhip_kuka_kernel", "srlhip_kuka_default_model", "srlhip_set_kuka_model", "srlhip_kuka_tree_default_model", "srlhip_set_kuka_tree_model",
     "srlhip_graph_begin", "srlhip_graph_end", "srlhip_graph_launch", "srlhip_graph_destroy",
@@ -110,6 +110,14 @@ class CnnPolicy(ctypes.Structure):
     ]
 
 
+class PixelPolicy(ctypes.Structure):
+    """struct srlhip_pixel_policy"""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("paired", ctypes.c_int32), ("freeze_after_done", ctypes.c_int32),
+        ("reserved", ctypes.c_int32), ("weights", ctypes.c_void_p), ("delta", ctypes.c_void_p), ("noise", ctypes.c_double),
+    ]
+
+
 class SrlHipError(RuntimeError):
     pass
 
@@ -156,6 +164,7 @@ def load():
     lib.srlhip_rollout_mlp_policy_sampled.argtypes = [vp, i32, ctypes.POINTER(MlpPolicy), vp, vp, vp, vp]
     lib.srlhip_policy_act.argtypes = [vp, ctypes.POINTER(LinearPolicy), ctypes.POINTER(MlpPolicy), i32, vp, i32, vp, vp, vp, vp]
     lib.srlhip_cnn_policy_act.argtypes = [vp, ctypes.POINTER(CnnPolicy), i32, vp, vp, vp, vp, vp]
+    lib.srlhip_pixel_policy_act.argtypes = [vp, ctypes.POINTER(PixelPolicy), vp, vp, vp, vp, vp]
     lib.srlhip_cnn_param_count.argtypes = [i32, i32, i32, i32]
     lib.srlhip_cnn_param_count.restype = ctypes.c_int64
     lib.srlhip_get_state.argtypes = [vp, i32, vp]
@@ -454,6 +463,20 @@ class Handle(object):
         pol.params = params
         self._check(self._lib.srlhip_cnn_policy_act(self._h, ctypes.byref(pol), int(bool(sample)), _ptr(images), _ptr(done_prev or None),
                                                     _ptr(frozen or None), _ptr(act_out), _ptr(score_out or None)), "srlhip_cnn_policy_act")
+
+    def pixel_policy_act(self, images, act_out, weights, delta=None, noise=0.0, freeze_after_done=False, done_prev=None, frozen=None,
+                         score_out=None):
+        """srlhip_pixel_policy_act: one launch on the handle's stream that writes every env's action to `act_out` from the uint8
+        [num_envs][H][W][C] plane `images` that step / reset wrote, through ARS's linear policy on the flattened frame (include/srlhip.h
+        has the contract).  Device-pointer raw_pixels handles only; every array argument is a raw device pointer.  `weights`: float64
+        M [D][A]; `delta`: float64 [num_envs / 2][D][A] — env 2k then acts with M + noise delta[k], env 2k + 1 with M - noise delta[k] —
+        or None: every env acts with M.  done_prev / frozen as in policy_act; score_out: optional float64 [num_envs][A] plane.
+        Only enqueues: capturable between graph_begin / graph_end."""
+        pol = PixelPolicy()
+        pol.struct_size, pol.paired, pol.freeze_after_done, pol.reserved = ctypes.sizeof(PixelPolicy), int(delta is not None), int(bool(freeze_after_done)), 0
+        pol.weights, pol.delta, pol.noise = weights, delta, float(noise)
+        self._check(self._lib.srlhip_pixel_policy_act(self._h, ctypes.byref(pol), _ptr(images), _ptr(done_prev or None), _ptr(frozen or None),
+                                                      _ptr(act_out), _ptr(score_out or None)), "srlhip_pixel_policy_act")
 
     def get_state(self, field):
         dtype, k = _FIELD_SHAPES[field]

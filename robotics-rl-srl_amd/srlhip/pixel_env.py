@@ -274,6 +274,54 @@ class RawPixelVecEnv(object):
             self.h.sync()
         return out
 
+    def _check_pixel_policy(self, weights, delta):
+        D, A = int(np.prod(self.images.shape[1:])), self.h.num_actions if self.cfg.is_discrete else self.h.action_dim
+        assert weights.is_cuda and weights.dtype == torch.float64 and weights.is_contiguous() and tuple(weights.shape) == (D, A), (tuple(weights.shape), (D, A))
+        if delta is not None:
+            assert self.num_envs % 2 == 0, "a paired population needs an even number of envs"
+            shape = (self.num_envs // 2, D, A)
+            assert delta.is_cuda and delta.dtype == torch.float64 and delta.is_contiguous() and tuple(delta.shape) == shape, (tuple(delta.shape), shape)
+
+    def pixel_policy_act(self, weights, delta=None, noise=0.0, act_out=None, score_out=None):
+        """ARS's linear policy on the frames the env holds now (srlhip_pixel_policy_act) -> the action tensor (self.actions unless
+        act_out is given).  weights: float64 CUDA tensor M [D][A], D = H W C; delta: float64 [N / 2][D][A] — env 2k acts with
+        M + noise delta[k], env 2k + 1 with M - noise delta[k] — or None: every env acts with M.  score_out: optional float64 [N][A]
+        tensor that receives the scores.  Enqueued on the handle's stream, the caller's stream ordered behind it"""
+        assert self._ready, "reset() the env first"
+        self._check_pixel_policy(weights, delta)
+        act = self.actions if act_out is None else act_out
+        self._stream.wait_stream(torch.cuda.current_stream(self.device))
+        self.h.pixel_policy_act(self.images.data_ptr(), act.data_ptr(), weights.data_ptr(), delta=None if delta is None else delta.data_ptr(),
+                                noise=noise, score_out=None if score_out is None else score_out.data_ptr())
+        torch.cuda.current_stream(self.device).wait_stream(self._stream)
+        return act
+
+    def rollout_pixel_policy(self, T, weights, delta=None, noise=0.0, freeze_after_done=False):
+        """T x (srlhip_pixel_policy_act, step + rasteriser) on the handle's stream, enqueue-only as rollout_cnn_policy is: an ARS
+        population as it is — M, the directions delta as torch.randn((P, D, A)) left them, the exploration noise — with no per-env
+        weight block formed.  Returns {"reward", "done", "actions"}: new [T][N]... tensors."""
+        assert self._ready, "reset() the env first"
+        self._check_pixel_policy(weights, delta)
+        n, dev = self.num_envs, self.device
+        ordered = torch.cuda.current_stream(dev).cuda_stream == self.torch_stream.cuda_stream
+        if not ordered:
+            torch.cuda.current_stream(dev).synchronize()
+        with torch.cuda.stream(self.torch_stream):         # the planes are allocated (and later freed) on the stream that fills them
+            out = {"reward": torch.empty((T, n), dtype=torch.float32, device=dev),
+                   "done": torch.empty((T, n), dtype=torch.uint8, device=dev),
+                   "actions": torch.empty((T,) + tuple(self.actions.shape), dtype=self.actions.dtype, device=dev)}
+            frozen = torch.zeros((n,), dtype=torch.uint8, device=dev)
+            images = self.images.data_ptr()
+            for t in range(T):
+                act_t = out["actions"][t]
+                self.h.pixel_policy_act(images, act_t.data_ptr(), weights.data_ptr(), delta=None if delta is None else delta.data_ptr(), noise=noise,
+                                        freeze_after_done=freeze_after_done, done_prev=out["done"][t - 1].data_ptr() if t else None,
+                                        frozen=frozen.data_ptr())
+                self.h.step(act_t.data_ptr(), out=(images, out["reward"][t].data_ptr(), out["done"][t].data_ptr()))
+        if not ordered:
+            self.h.sync()
+        return out
+
     def episode_stats(self):
         return self.h.episode_stats()
 
