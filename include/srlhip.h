@@ -718,7 +718,15 @@ int srlhip_encoder_create(int32_t device_id, int32_t img_h, int32_t img_w, int32
 int srlhip_encoder_forward(srlhip_encoder_handle e, const uint8_t *images_dev, int32_t n, float *states_dev,
                            void *hip_stream);
 /* Synchronises the device; *flag = 1 if an activation ever left float16's range (|x| >= 65504: the split-f16
- * matrix path then lost accuracy and the caller should use the PyTorch forward for these weights). */
+ * matrix path then lost accuracy and the caller should use the PyTorch forward for these weights).
+ * Watched: the pooled, rectified activations of layers 1 and 2 — the values that travel between layers as f16
+ * hi / lo planes — in both kernels and every variant of them.  Layer 3's pooled features stay float32 and are not
+ * watched: they may exceed 65504 without loss.  The flag is STICKY: a new handle starts with 0; once a forward has
+ * set it, it stays 1 for the life of the handle — later forwards within range do not clear it, and neither does
+ * reading it (it describes the weights, which a handle never changes).  Below the line the states keep the
+ * accuracy of the float32 forward (tests/test_gpu_encoder_f64.py, tests/test_gpu_encoder_overflow.py: pooled
+ * maxima of 65504 / 2 hold the same bar as ordinary weights; at 2 x 65504 the flag is set and the states are
+ * not to be used). */
 int srlhip_encoder_overflow(srlhip_encoder_handle e, int32_t *flag);
 /* Diagnostic: one synchronous forward whose workgroup 0 stamps the shader clock (s_memtime) at nine points of its
  * first frames; cycles9[k] = cycles between stamp k and k+1, slowest wave, averaged over frames:
