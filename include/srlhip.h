@@ -756,6 +756,42 @@ int srlhip_encoder_pack_i8(const float *conv1_w, const float *conv1_b, int32_t z
 int srlhip_encoder_pack(const float *conv1_w, const float *conv1_b, const float *conv2_w, const float *conv3_w,
                         void *out, size_t out_bytes, float *scales3 /* power-of-two pre-scale of layers 1..3 */);
 
+/* ---- PCA state baseline (raw_pixels -> state) -----------------------------------------------------------
+ * Replaces SRLPCA.getState (state_representation/models.py:196-217: a pickled sklearn PCA applied on the host to one
+ * flattened uint8 observation at a time, `self.model.transform(observation.reshape(-1, n_features))`) for a whole
+ * DEVICE-resident batch of frames, as one launch.  The caller folds the model: w is [F][S] float64 =
+ * components_.T (each column divided by sqrt(explained_variance_) when the PCA whitens), b is [S] = -(mean_ @ w);
+ * F = H W C flattened in the frame's own order, 1 <= S <= 64, F >= 1 (srlhip_pca_supported() tells beforehand; anything
+ * else -> SRLHIP_ENOTSUP and the caller keeps the PyTorch formulation).
+ * THE ARITHMETIC (csrc/pca_project.hpp, one text for the kernel, the host twin and the host check program): the
+ * features f = 0 .. F - 1 are cut into chunks of 512 (the last one ragged); a chunk's sum starts from +0.0 and takes its
+ * features in ascending order, acc = fma((double) x[i][f], w[f][s], acc) — the byte as it lies, no / 255; the state is the
+ * chunks' sums added in ascending chunk order, starting with chunk 0's, then b[s]; with states_f32 the float64 state is
+ * rounded once to float32.  The order depends on F alone: a frame's state does not depend on n, on its place in the
+ * batch or on the launch's shape, and two forwards of the same input give the same bits.  Against an exactly rounded
+ * reference every element is within (F + chunks + 1) 2^-52 (sum_f x_f |w_fs| + |b_s|).
+ * srlhip_pca_forward: images_dev uint8 [n][F] and states_dev [n][S] (float64, or float32 with states_f32 = 1) are DEVICE
+ * pointers on device_id; the call only enqueues on hip_stream (NULL = the default stream); n = 0 succeeds and launches
+ * nothing.  The handle keeps grow-only scratch (the chunk sums of a launch, at most 512 MiB or one frame tile's: a larger
+ * batch goes as several launches, one behind the other) PER STREAM it has been given: forwards on one stream are ordered
+ * and share it, forwards on different streams of one handle may overlap.  A caller that captures the forward into a HIP
+ * graph calls it once with its batch size, on the stream it captures, before capturing; the captured forward uses that
+ * stream's scratch, so replays run on that stream, or ordered against its other forwards.  One host thread at a time
+ * calls into a handle.
+ * srlhip_pca_project_host is the host twin (host pointers, no GPU): the same header functions, the same bits — to this
+ * contract what srlhip_jpeg_encode_host is to the JPEG one.  Without a GPU srlhip_pca_create fails with SRLHIP_EHIP and
+ * a message (srlhip_pca_last_error(NULL)). */
+typedef struct srlhip_pca *srlhip_pca_handle;
+int srlhip_pca_supported(int64_t n_features, int32_t state_dim);              /* host only */
+int srlhip_pca_create(int32_t device_id, int64_t n_features, int32_t state_dim,
+                      const double *w /* [F][S] */, const double *b /* [S] */, srlhip_pca_handle *out);
+int srlhip_pca_forward(srlhip_pca_handle p, const uint8_t *images_dev, int32_t n,
+                       void *states_dev, int32_t states_f32, void *hip_stream);  /* enqueue-only */
+int srlhip_pca_project_host(int64_t n_features, int32_t state_dim, const double *w, const double *b,
+                            const uint8_t *images, int32_t n, void *states, int32_t states_f32); /* host only */
+int srlhip_pca_destroy(srlhip_pca_handle p);
+const char *srlhip_pca_last_error(srlhip_pca_handle p);
+
 
 #ifdef __cplusplus
 }

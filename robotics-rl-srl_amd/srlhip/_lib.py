@@ -45,6 +45,7 @@ EXPORTS = [
     "srlhip_encoder_phase_cycles",
     "srlhip_encoder_destroy", "srlhip_encoder_last_error", "srlhip_encoder_pack_bytes", "srlhip_encoder_pack", "srlhip_encoder_pack_i8_bytes", "srlhip_encoder_pack_i8", "srlhip_encoder_pack_first_layer",
     "srlhip_jpeg_encode", "srlhip_render_jpeg", "srlhip_jpeg_header_bytes", "srlhip_jpeg_encode_host",
+    "srlhip_pca_supported", "srlhip_pca_create", "srlhip_pca_forward", "srlhip_pca_project_host", "srlhip_pca_destroy", "srlhip_pca_last_error",
 ]
 
 
@@ -198,6 +199,13 @@ def load():
     lib.srlhip_encoder_destroy.argtypes = [vp]
     lib.srlhip_encoder_last_error.restype = ctypes.c_char_p
     lib.srlhip_encoder_last_error.argtypes = [vp]
+    lib.srlhip_pca_supported.argtypes = [ctypes.c_int64, i32]
+    lib.srlhip_pca_create.argtypes = [i32, ctypes.c_int64, i32, vp, vp, ctypes.POINTER(vp)]
+    lib.srlhip_pca_forward.argtypes = [vp, vp, i32, vp, i32, vp]
+    lib.srlhip_pca_project_host.argtypes = [ctypes.c_int64, i32, vp, vp, vp, i32, vp, i32]
+    lib.srlhip_pca_destroy.argtypes = [vp]
+    lib.srlhip_pca_last_error.restype = ctypes.c_char_p
+    lib.srlhip_pca_last_error.argtypes = [vp]
     lib.srlhip_encoder_pack_bytes.restype = ctypes.c_size_t
     lib.srlhip_encoder_pack_bytes.argtypes = []
     lib.srlhip_encoder_pack.argtypes = [vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
@@ -800,6 +808,65 @@ class Encoder(object):
         if self._e:
             self._lib.srlhip_encoder_destroy(self._e)
             self._e = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pca_supported(n_features, state_dim):
+    """host only: does srlhip_pca_create take this shape (1 <= state_dim <= 64, n_features >= 1)"""
+    return bool(load().srlhip_pca_supported(int(n_features), int(state_dim)))
+
+
+def _pca_weights(w, b):
+    w, b = np.ascontiguousarray(w, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    assert w.ndim == 2 and b.shape == (w.shape[1],), (w.shape, b.shape)
+    return w, b
+
+
+def pca_project_host(w, b, images, states_f32=False):
+    """srlhip_pca_project_host: the kernel's own arithmetic (csrc/pca_project.hpp) on the CPU.  w float64 [F][S], b [S], images uint8
+    [n][...] (flattened to [n][F]) -> float64 (states_f32: float32) [n][S]; raises SrlHipError on a refusal."""
+    w, b = _pca_weights(w, b)
+    images = np.ascontiguousarray(images, dtype=np.uint8)
+    n = images.shape[0]
+    images = images.reshape(n, w.shape[0])
+    out = np.zeros((n, w.shape[1]), np.float32 if states_f32 else np.float64)
+    rc = load().srlhip_pca_project_host(w.shape[0], w.shape[1], _ptr(w), _ptr(b), _ptr(images), n, _ptr(out), int(bool(states_f32)))
+    if rc:
+        raise SrlHipError("srlhip_pca_project_host failed ({})".format(rc))
+    return out
+
+
+class PcaProjector(object):
+    """srlhip_pca_handle: the PCA state baseline on device-resident uint8 frames, one launch (csrc/pca_project.hip).
+    w: float64 [n_features][state_dim] (whitened, transposed), b: float64 [state_dim] = -(mean_ @ w) — see include/srlhip.h."""
+
+    def __init__(self, device_id, w, b):
+        self._lib = load()
+        self._p = ctypes.c_void_p()
+        w, b = _pca_weights(w, b)
+        rc = self._lib.srlhip_pca_create(int(device_id), w.shape[0], w.shape[1], _ptr(w), _ptr(b), ctypes.byref(self._p))
+        if rc:
+            self._p = None
+            raise SrlHipError("srlhip_pca_create failed ({}): {}".format(rc, self._lib.srlhip_pca_last_error(None).decode()))
+        self.n_features, self.state_dim = int(w.shape[0]), int(w.shape[1])
+
+    def forward(self, images_ptr, n, states_ptr, states_f32=False, stream=None):
+        """images_ptr / states_ptr: raw device pointers (e.g. torch.Tensor.data_ptr()); states float64 [n][state_dim], or float32 with
+        states_f32; enqueue-only on `stream`."""
+        rc = self._lib.srlhip_pca_forward(self._p, _ptr(images_ptr), int(n), _ptr(states_ptr), int(bool(states_f32)),
+                                          ctypes.c_void_p(stream) if stream else None)
+        if rc:
+            raise SrlHipError("srlhip_pca_forward failed ({}): {}".format(rc, self._lib.srlhip_pca_last_error(self._p).decode()))
+
+    def close(self):
+        if self._p:
+            self._lib.srlhip_pca_destroy(self._p)
+            self._p = None
 
     def __del__(self):
         try:

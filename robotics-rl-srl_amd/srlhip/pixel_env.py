@@ -55,7 +55,7 @@ class PixelStateVecEnv(object):
 
     def _encode(self):
         if self.encoder.hip is not None:
-            # fused HIP encoder: enqueue on the stepper's own stream right behind the rasteriser (no host sync), then
+            # HIP encoder (CustomCNN kernels, or the PCA projection): enqueue on the stepper's own stream right behind the rasteriser (no host sync), then
             # order torch's current stream behind it so the caller can consume states / rewards / dones as usual
             states = self.encoder.getStates(self.images, stream=self._stream_ptr, out=self.states)
             torch.cuda.current_stream(self.device).wait_stream(self._stream)
@@ -136,7 +136,7 @@ class PixelStateVecEnv(object):
                 self.h.step(act_t.data_ptr(), out=(images, out["reward"][t].data_ptr(), out["done"][t].data_ptr()))
                 if fused:
                     self.encoder.getStates(self.images, stream=self._stream_ptr, out=obs_t)
-                else:                                      # no HIP backend (PCA, other model types): the torch forward, ordered on this stream
+                else:                                      # no HIP backend (backend="torch", uncovered shapes): the torch forward, ordered on this stream
                     obs_t.copy_(self.encoder.getStates(self.images))
                 prev = obs_t
             self._current = prev

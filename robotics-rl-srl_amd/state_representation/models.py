@@ -182,18 +182,29 @@ class SRLPCA(object):
     """state_representation/models.py:196-217 — a pickled sklearn PCA as the state representation.  The reference transforms one
     flattened uint8 observation at a time on the host (`self.model.transform(observation.reshape(-1, n_features))`); here the whole
     device-resident batch goes through ONE GEMM on the device: (X - mean_) @ components_.T [/ sqrt(explained_variance_) when the
-    PCA whitens], in float64 like sklearn (uint8 input is promoted to float64 there)."""
+    PCA whitens], in float64 like sklearn (uint8 input is promoted to float64 there).
+    backend: "auto" | "hip" | "torch".  On a GPU the projection is the HIP kernel csrc/pca_project.hip through the C-ABI (srlhip_pca_*:
+    one launch on the caller's stream, no float64 copy of the frames, float64 or float32 states); "torch" — and every model on the CPU —
+    keeps the torch formulation, `images.to(float64)` + addmm (rocBLAS dgemm on a GPU)."""
 
-    def __init__(self, state_dim, cuda=False, device=None):
+    def __init__(self, state_dim, cuda=False, device=None, backend="auto"):
+        if backend not in ("auto", "hip", "torch"):
+            raise ValueError("backend must be auto, hip or torch")
         self.state_dim = state_dim
         self.device = th.device(device if device is not None else ("cuda" if cuda else "cpu"))
+        if self.device.type == "cuda" and self.device.index is None and th.cuda.is_available():
+            # a bare "cuda" is torch's current device NOW: the tensors and the projector's handle must land on the same GPU
+            self.device = th.device("cuda", th.cuda.current_device())
+        if backend == "hip" and self.device.type != "cuda":
+            raise RuntimeError("the HIP PCA projection needs a GPU (got device {})".format(self.device))
         self.model, self._w, self._b = None, None, None
         self.hip, self.backend = None, "gemm"
+        self._backend_arg = backend
 
     state_dtype = th.float64
 
     def replicate(self, device):
-        twin = SRLPCA(self.state_dim, device=device)
+        twin = SRLPCA(self.state_dim, device=device, backend=self._backend_arg)
         twin.set_model(self.model)
         return twin
 
@@ -215,16 +226,52 @@ class SRLPCA(object):
         if getattr(pca, "whiten", False):
             w = w / np.sqrt(np.asarray(pca.explained_variance_, dtype=np.float64))[None, :]
         self._w = th.from_numpy(w).to(self.device)                               # [n_features][state_dim]
-        self._b = th.from_numpy(-(mean @ w)).to(self.device)                     # folded: X @ w - mean @ w
+        b = -(mean @ w)                                                          # folded: X @ w - mean @ w
+        self._b = th.from_numpy(b).to(self.device)
         assert self._w.shape[1] == self.state_dim, "exp_config.json state-dim does not match the pickled PCA"
+        if self.hip is not None:
+            self.hip.close()
+        self.hip, self.backend = None, "gemm"
+        if self._backend_arg != "torch" and self.device.type == "cuda":
+            from srlhip import _lib
+            if _lib.pca_supported(w.shape[0], w.shape[1]):
+                self.hip = _lib.PcaProjector(self.device.index, w, b)
+                self.backend = "hip"
+        if self._backend_arg == "hip" and self.hip is None:
+            raise RuntimeError("the HIP PCA projection needs a GPU, 1..64 state dimensions and at least one feature "
+                               "(got device {}, W {}x{})".format(self.device, w.shape[0], w.shape[1]))
 
     @th.no_grad()
-    def getStates(self, images_u8, stream=None, out=None):
-        """uint8 [N][H][W][C] (numpy or device tensor) -> float64 [N][state_dim], one GEMM (rocBLAS dgemm on the GPU)."""
+    def getStatesTorch(self, images_u8):
+        """The torch formulation: a float64 copy of the frames and one GEMM (rocBLAS dgemm on the GPU)."""
         if isinstance(images_u8, np.ndarray):
             images_u8 = th.from_numpy(images_u8)
         x = images_u8.to(self.device).reshape(images_u8.shape[0], -1).to(th.float64)
         return th.addmm(self._b, x, self._w)
+
+    @th.no_grad()
+    def getStates(self, images_u8, stream=None, out=None):
+        """uint8 [N][H][W][C] (numpy or device tensor) -> float64 [N][state_dim].
+        stream: raw HIP stream to enqueue the kernel on (default: torch's current stream); out: optional preallocated [N][state_dim]
+        device tensor, float64 or float32 — its dtype is the states' (both only used by the HIP path).  With a `stream` of the caller's
+        the frames must already be a contiguous tensor on this model's device: torch does not know that stream, so a temporary copy
+        made here could be handed out again by torch's allocator while the kernel still reads it."""
+        if self.hip is None:
+            return self.getStatesTorch(images_u8)
+        if stream is not None and not (isinstance(images_u8, th.Tensor) and images_u8.device == self.device and images_u8.is_contiguous()):
+            raise ValueError("SRLPCA.getStates(stream=...): the frames must be a contiguous tensor on {}".format(self.device))
+        if isinstance(images_u8, np.ndarray):
+            images_u8 = th.from_numpy(images_u8)
+        n = images_u8.shape[0]
+        images_u8 = images_u8.to(self.device).reshape(n, -1).contiguous()       # (a copy only without `stream`: torch's current stream, which torch tracks)
+        assert images_u8.dtype == th.uint8 and images_u8.shape[1] == self._w.shape[0], images_u8.shape
+        if out is None:
+            out = th.empty((n, self.state_dim), dtype=th.float64, device=self.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype in (th.float64, th.float32) and tuple(out.shape) == (n, self.state_dim)
+        if stream is None:
+            stream = th.cuda.current_stream(self.device).cuda_stream
+        self.hip.forward(images_u8.data_ptr(), n, out.data_ptr(), states_f32=out.dtype == th.float32, stream=stream)
+        return out
 
     def getState(self, observation, env_id=0):
         return self.getStates(np.asarray(observation)[None])[0].to("cpu").numpy()
