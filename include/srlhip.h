@@ -306,6 +306,26 @@ int srlhip_rollout_mlp_policy(srlhip_handle h, int32_t T, const srlhip_mlp_polic
 int srlhip_rollout_mlp_policy_sampled(srlhip_handle h, int32_t T, const srlhip_mlp_policy *pol,
                                       void *obs_TN, float *reward_TN, uint8_t *done_TN, void *act_out_TN);
 
+/* srlhip_rollout_policy with the selection of srlhip_rollout_mlp_policy_sampled: the discrete action is DRAWN from the softmax of the
+ * linear policy's scores, as ARS does without --deterministic (rl_baselines/evolution_strategies/ars.py: np.random.choice(len(a),
+ * p=softmax(obs @ (M +- nu delta_k)))).  Discrete action modes only.  The struct is srlhip_linear_policy, unchanged.
+ *   scores     srlhip_rollout_policy's: score_a = sum_d (double)x_d * W[d][a], d ascending, starting with the d = 0 product — the
+ *              MobileRobot kernels in exactly this order with no product fused (the arithmetic of srlhip_policy_act's linear form, bit
+ *              for bit), the Kuka kernels with the freedom to fuse a product with the sum that takes it.
+ *   selection  the draw of srlhip_rollout_mlp_policy_sampled word for word (u, m, w_k, c_k, z, a): u from the Philox block at counter
+ *              c0 + t, stream 1, key of env e; an env frozen by freeze_after_done takes -1 and its draw is discarded, not skipped.
+ * After the call the action-stream counter is c0 + T for every env: chunked calls equal one call.  The stream, what srlhip_rollout(actions
+ * = NULL) adds to its counter per step (MobileRobot, discrete: the counter is read here as a BLOCK index), and the independence of
+ * cfg.rng_mode are as described there.  One step of this call equals srlhip_policy_act(linear, score_out) followed by
+ * srlhip_sample_actions on a MobileRobot handle, bit for bit.
+ * Against another implementation of the contract the action is pinned only where z is not within the rounding of the c_k
+ * (tests/policy_sample_ref.py: the acceptance rule above with the score bound (2 D + 16) 2^-53 sum_d |x_d W[d][a]|).
+ * Refusals: everything srlhip_rollout_policy refuses, worded alike under the prefix "rollout_policy_sampled:", and SRLHIP_ENOTSUP for
+ * the continuous action modes (the message names "discrete").  EINVAL cases, graph capture on device-pointer handles, NULL planes and
+ * the parking of a resident kernel are srlhip_rollout_policy's. */
+int srlhip_rollout_policy_sampled(srlhip_handle h, int32_t T, const srlhip_linear_policy *pol,
+                                  void *obs_TN, float *reward_TN, uint8_t *done_TN, void *act_out_TN);
+
 /* The policy's action as a call of its own: ONE step of the three fused rollouts' action selection, from an observation plane the
  * caller already holds on the device — the state vectors an SRL encoder made of the rendered frames (image -> encoder -> state ->
  * policy), where no policy can sit inside the physics kernel.  A T-step rollout on learned states is T x (srlhip_policy_act,
@@ -445,6 +465,23 @@ typedef struct srlhip_pixel_policy {
 } srlhip_pixel_policy;
 int srlhip_pixel_policy_act(srlhip_handle h, const srlhip_pixel_policy *pol, const uint8_t *images,
                             const uint8_t *done_prev, uint8_t *frozen, void *act_out, double *score_out);
+
+/* The sampled selection on a SCORE PLANE the caller holds on the device: what puts sampling behind srlhip_pixel_policy_act(score_out) and
+ * srlhip_policy_act(linear, score_out).  Device-pointer handles only, discrete action modes only, ANY env kind, model and observation
+ * mode: the call reads the handle's action space (A = num_actions) and its action-stream counters, never the env state.
+ *   scores     float64 [num_envs][A]
+ *   frozen     uint8 [num_envs] or NULL: an env whose byte is non-zero gets -1 (the plane a policy call with freeze_after_done keeps)
+ *   act_out    int32 [num_envs]
+ * The draw of srlhip_rollout_mlp_policy_sampled word for word on the given scores (m, w_k, c_k, z, a; exp from the device math library;
+ * the one text of csrc/policy_act.hpp), with u from the Philox block at the env's CURRENT action-stream counter c, stream 1.
+ * COUNTER: the call leaves c + 1 for EVERY env, frozen or not, and advances it inside the kernel — a captured call draws fresh numbers
+ * at every replay; K calls from c0 use the blocks c0 .. c0 + K - 1 that a fused sampled rollout with T = K uses.
+ * The result for env e depends on its own score row, frozen[e] and its counter alone: not on num_envs, on e, or on the launch
+ * geometry — shards and batch sizes agree bit for bit.
+ * One launch on the handle's stream, no allocation, no synchronisation; capturable under srlhip_graph_begin.  A resident persistent
+ * kernel parks.  SRLHIP_EINVAL: null scores or act_out, a pending srlhip_step_async.  SRLHIP_ENOTSUP: a host-pointer handle; a
+ * continuous action mode (the message names "discrete"). */
+int srlhip_sample_actions(srlhip_handle h, const double *scores, const uint8_t *frozen, int32_t *act_out);
 
 /* Raw state access (checkpoint / parity): field ids below; arrays are
  * [num_envs] (or [k][num_envs] for vector fields) of the field's own type.

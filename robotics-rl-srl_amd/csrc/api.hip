@@ -516,7 +516,7 @@ int fetch_rollout_planes(Handle *h, int32_t T, const RolloutPlanes &host, const 
 struct PolicyCall {
     const char *name;              // the entry point, as every message begins
     KukaPolicyLaunch kuka;
-    bool sample = false;           // srlhip_rollout_mlp_policy_sampled: the discrete action is drawn from the softmax of the scores
+    bool sample = false;           // srlhip_rollout_policy_sampled / srlhip_rollout_mlp_policy_sampled: the discrete action is drawn from the softmax of the scores
 };
 int refuse(Handle *h, const char *name, const Verdict &v) { return h->fail(v.code, std::string(name) + ": " + v.msg); }      // (built on a failing call only)
 PolicyArgs policy_args(const PolicyView &v) {
@@ -532,7 +532,7 @@ int policy_call_begin(Handle *h, const char *name, int32_t T) {
 int rollout_policy(Handle *h, int32_t T, const PolicyCall &pc, const PolicyView &pv, const RolloutPlanes &host) {
     const srlhip_config &c = h->cfg;
     Verdict v = check_policy_pointers(pv);
-    if (!v.code) v = check_rollout_policy_config(c, pc.sample);
+    if (!v.code) v = pc.sample && !pv.mlp ? check_rollout_policy_sampled_config(c) : check_rollout_policy_config(c, pc.sample);
     if (v.code) return refuse(h, pc.name, v);
     int rc = set_device(h);                            // (parks a resident kernel)
     if (rc) return rc;
@@ -555,7 +555,7 @@ int rollout_policy(Handle *h, int32_t T, const PolicyCall &pc, const PolicyView 
     return c.io_device ? 0 : fetch_rollout_planes(h, T, host, dev);      // (`packed` must outlive its copy: the synchronisation is in there)
 }
 
-// the three entry points: one body
+// the four entry points: one body
 template <class P>
 int rollout_policy_entry(srlhip_handle hh, const PolicyCall &pc, int32_t T, const P *pol, const RolloutPlanes &host) {
     if (!hh) return SRLHIP_EINVAL;
@@ -704,6 +704,11 @@ int srlhip_rollout_policy(srlhip_handle hh, int32_t T, const srlhip_linear_polic
     return rollout_policy_entry(hh, {"rollout_policy", kuka_rollout_policy}, T, pol, {obs_TN, reward_TN, done_TN, act_out_TN});
 }
 
+int srlhip_rollout_policy_sampled(srlhip_handle hh, int32_t T, const srlhip_linear_policy *pol, void *obs_TN, float *reward_TN,
+                                  uint8_t *done_TN, void *act_out_TN) {
+    return rollout_policy_entry(hh, {"rollout_policy_sampled", kuka_rollout_policy_sampled, true}, T, pol, {obs_TN, reward_TN, done_TN, act_out_TN});
+}
+
 int srlhip_rollout_mlp_policy(srlhip_handle hh, int32_t T, const srlhip_mlp_policy *pol, void *obs_TN, float *reward_TN,
                               uint8_t *done_TN, void *act_out_TN) {
     return rollout_policy_entry(hh, {"rollout_mlp_policy", kuka_rollout_mlp_policy}, T, pol, {obs_TN, reward_TN, done_TN, act_out_TN});
@@ -736,6 +741,20 @@ int srlhip_policy_act(srlhip_handle hh, const srlhip_linear_policy *linear, cons
     if ((rc = set_device(h))) return rc;               // (parks a resident kernel)
     // none_nan: a frozen env's continuous row is the family's `None` — NaNs for Kuka, zeros for MobileRobot
     return policy_act_launch(h, policy_args(pv), sample != 0, obs_dim, (int)policy_outputs(c), !is_mobile(c.env_kind), obs, done_prev, frozen, act_out, score_out);
+}
+
+// srlhip_sample_actions: a pending step, then the planes and the config (api_rules.hpp: check_sample_actions)
+int srlhip_sample_actions(srlhip_handle hh, const double *scores, const uint8_t *frozen, int32_t *act_out) {
+    if (!hh) return SRLHIP_EINVAL;
+    Handle *h = reinterpret_cast<Handle *>(hh);
+    const char *name = "sample_actions";
+    int rc = policy_call_begin(h, name, 1);
+    if (rc) return rc;
+    const srlhip_config &c = h->cfg;
+    const Verdict v = check_sample_actions(c, scores != nullptr, act_out != nullptr);
+    if (v.code) return refuse(h, name, v);
+    if ((rc = set_device(h))) return rc;               // (parks a resident kernel)
+    return sample_actions_launch(h, num_actions_of(c), scores, frozen, act_out);
 }
 
 // srlhip_cnn_policy_act: the struct, a pending step, then the planes and the config (api_rules.hpp: check_cnn_policy_abi, check_cnn_policy_act)

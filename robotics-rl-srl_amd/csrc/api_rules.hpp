@@ -282,6 +282,23 @@ inline Verdict check_policy_act_planes(const srlhip_config &c, const PolicyView 
     return kAccepted;
 }
 
+// ---- the linear policy's sampled forms ----------------------------------------------------------------------------------------------------
+// srlhip_rollout_policy_sampled: what srlhip_rollout_policy refuses, in its order, then the continuous action modes (tails; the entry
+// point prefixes "rollout_policy_sampled: ").  The struct and pointer checks in front of it are the shared ones above.
+inline Verdict check_rollout_policy_sampled_config(const srlhip_config &c) {
+    if (const Verdict v = check_rollout_policy_config(c, false); v.code) return v;
+    if (!c.is_discrete) return {SRLHIP_ENOTSUP, "only discrete actions are sampled (the reference never samples continuous ones)"};
+    return kAccepted;
+}
+// srlhip_sample_actions (tails; the entry point prefixes "sample_actions: "): the planes, then what the handle's config rules out — nothing
+// of the env kind, the model or the observation mode: the call never looks at the env state
+inline Verdict check_sample_actions(const srlhip_config &c, bool have_scores, bool have_act) {
+    if (!have_scores || !have_act) return {SRLHIP_EINVAL, "null scores or act_out"};
+    if (!c.io_device) return {SRLHIP_ENOTSUP, "device-pointer handles only (io_device = 1)"};
+    if (!c.is_discrete) return {SRLHIP_ENOTSUP, "only discrete actions are sampled (the reference never samples continuous ones)"};
+    return kAccepted;
+}
+
 // ---- srlhip_cnn_policy_act: the CNN's shapes and argument checks --------------------------------------------------------------------------
 // The reference's CNNPolicyPytorch (cma_es.py:259-300) on an [H][W][C] frame: conv 5x5 s2 p2 C->8, conv 3x3 s2 p1 8->16, conv 3x3 s2 p1
 // 16->32, each behind it batch-norm, ReLU and a 2x2 max-pool (floor), then a linear layer F -> A.  conv: (x + 2 pad - k) / 2 + 1.

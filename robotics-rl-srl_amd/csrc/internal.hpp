@@ -72,10 +72,11 @@ static_assert(sizeof(PolicyArgs) == 48 && offsetof(PolicyArgs, w) == 0 && offset
                   offsetof(PolicyArgs, clip) == 24 && offsetof(PolicyArgs, per_env) == 32 && offsetof(PolicyArgs, freeze) == 36 &&
                   offsetof(PolicyArgs, normalize) == 40 && offsetof(PolicyArgs, hidden) == 44,
               "PolicyArgs is a kernel argument: its layout is what the policy kernels were compiled against");
-// kuka_tree_policy.hip / kuka_tree_mlp.hip / kuka_tree_mlp_sample.hip (full model); d_hdr: the handle's 16-double policy header
+// kuka_tree_policy.hip / kuka_tree_mlp.hip / kuka_tree_mlp_sample.hip / kuka_tree_policy_sample.hip (full model); d_hdr: the handle's 16-double policy header
 int kuka_rollout_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
 int kuka_rollout_mlp_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
 int kuka_rollout_mlp_policy_sampled(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
+int kuka_rollout_policy_sampled(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);      // kuka_tree_policy_sample.hip
 using KukaPolicyLaunch = int (*)(Handle *, int, const PolicyArgs &, double *, float *, float *, uint8_t *, void *);
 int kuka_policy_header(Handle *h, double *d_hdr, const PolicyArgs &pol);      // kuka_tree_policy.hip: the one header kernel's launch
 
@@ -85,7 +86,7 @@ struct EnvOps {
     int (*reset)(Handle *h, const uint8_t *d_mask, const double *d_host_rand, void *d_obs);
     int (*step)(Handle *h, const void *d_actions, const double *d_noise, void *d_obs, float *d_rew, uint8_t *d_done);
     int (*rollout)(Handle *h, int T, const void *d_actions, void *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
-    // the fused policy rollouts.  MobileRobot: the linear or the MLP kernel family by pol.hidden, with `sample` the MLP's discrete action
+    // the fused policy rollouts.  MobileRobot: the linear or the MLP kernel family by pol.hidden, with `sample` the discrete action
     // drawn from the softmax of its scores; Kuka: `kuka`, the launcher api.hip's PolicyCall names, on the handle's policy header
     int (*rollout_policy)(Handle *h, int T, const PolicyArgs &pol, bool sample, KukaPolicyLaunch kuka, void *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
     int (*field)(Handle *h, int field, void **dptr, size_t *elem, int *count);
@@ -102,6 +103,9 @@ const EnvOps &kuka_env_ops();        // kuka.hip
 // D = floats per row of obs, A = scores per env; none_nan: a frozen env's continuous row is NaNs (Kuka), not zeros (MobileRobot)
 int policy_act_launch(Handle *h, const PolicyArgs &pol, bool sample, int D, int A, bool none_nan, const float *d_obs, const uint8_t *d_done_prev,
                       uint8_t *d_frozen, void *d_act, double *d_score);
+// policy_act.hip: srlhip_sample_actions behind its argument checks — one launch on the handle's stream, no allocation, no synchronisation.
+// d_score: float64 [n][A], A = the handle's num_actions; d_frozen: uint8 [n] or null
+int sample_actions_launch(Handle *h, int A, const double *d_score, const uint8_t *d_frozen, int32_t *d_act);
 // cnn_policy.hip: srlhip_cnn_policy_act behind its argument checks — one launch on the handle's stream, no allocation, no synchronisation.
 // The frame shape is the handle's config's; A = scores per env; none_nan as above
 int cnn_policy_act_launch(Handle *h, const float *d_params, bool per_env, bool freeze, bool sample, int A, bool none_nan, const uint8_t *d_images,

@@ -163,6 +163,31 @@ __device__ __forceinline__ double mlp_row_sum(double x) {
     return acc;
 }
 
+// The sampled policies' selection (contract: include/srlhip.h, srlhip_rollout_mlp_policy_sampled): the action drawn from the softmax of
+// the six scores, which every lane of the env's row holds bit for bit.  Lane k < 6 owns exp(sc[k] - m), the six weights come back over
+// the row, every lane adds them up in index order and counts the partial sums z = u c_5 has reached — the result is the same in all 16
+// lanes, as the step needs it.  u is the block at counter c0 + t of the env's action stream, formed by every lane (80 integer
+// instructions next to a 50 k-cycle step) from the key and the counter the prologue loaded: those four words are all the sampling
+// keeps live across the step.  A frozen env draws too.
+template <class S>
+__device__ __forceinline__ int row_softmax_draw(const S &sc, int l, const Philox &act, int t) {
+    using namespace grp;
+    double m = sc[0], own = sc[0];
+#pragma unroll
+    for (int k = 1; k < 6; k++) { m = sc[k] > m ? sc[k] : m; own = l == k ? sc[k] : own; }
+    const double wl = exp(own - m);
+    double c[6];
+    c[0] = bcast<0>(wl);
+    c[1] = c[0] + bcast<1>(wl); c[2] = c[1] + bcast<2>(wl); c[3] = c[2] + bcast<3>(wl); c[4] = c[3] + bcast<4>(wl); c[5] = c[4] + bcast<5>(wl);
+    Philox q = act;
+    q.ctr = act.ctr + (uint64_t)t;
+    const double z = q.double01() * c[5];
+    int a = 0;
+#pragma unroll
+    for (int k = 0; k < 5; k++) a += z >= c[k] ? 1 : 0;
+    return a;
+}
+
 // POLICY = 1 (srlhip_rollout_policy; kuka_tree_policy.hip): the third action source — a linear policy of the env's own current
 // ground-truth observation.  `actions` is then the float64 weight plane ([n][3][A] or [3][A]) and `noise` the 10-double header
 // kuka_policy_hdr_k wrote (per_env, freeze, normalize, clip, mean[3], std[3]).  Lane a < A of the env's row keeps column a of the
@@ -183,13 +208,16 @@ __device__ __forceinline__ double mlp_row_sum(double x) {
 // POLICY = 3 (srlhip_rollout_mlp_policy_sampled; kuka_tree_mlp_sample.hip): POLICY = 2 up to the six scores, discrete actions only
 // (JOINTS = false); the action is then drawn from their softmax with the env's own action stream (contract: include/srlhip.h), and
 // the exit store leaves that stream's counter T further on.
+// POLICY = 4 (srlhip_rollout_policy_sampled; kuka_tree_policy_sample.hip): POLICY = 1 up to the six broadcast scores, discrete actions
+// only (JOINTS = false), then POLICY = 3's draw (row_softmax_draw) and its counter store.
 template <int MODE, bool JOINTS, bool GIVEN, int NB, int RB = 0, int SPEC = 0, int PERSIST = 0, int POLICY = 0>
 __global__ void __launch_bounds__(kGroupBlock)
 kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int T, const void *actions, const double *noise,
                     float *obs, float *rew, uint8_t *done_out, void *act_out, PersistArgs pa) {
     static_assert(!PERSIST || GIVEN, "persistent stepping takes the caller's actions");
     static_assert(!POLICY || (!GIVEN && !PERSIST && !SPEC && !RB), "the policy source has generic, launching instantiations only");
-    static_assert(POLICY != 3 || !JOINTS, "only discrete actions are sampled");
+    constexpr bool kMlp = POLICY == 2 || POLICY == 3, kDraw = POLICY == 3 || POLICY == 4;      // the score function; the selection
+    static_assert(!kDraw || !JOINTS, "only discrete actions are sampled");
     using namespace grp;
     __shared__ double scratch_all[kGroupEnvs][kTS];
     const int64_t n = p.n;
@@ -253,7 +281,7 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
     float mlp_w1[kMlpU][3], mlp_b1[kMlpU], mlp_w2[kMlpA][kMlpU], mlp_b2[kMlpA];
     const int mlp_A = cfg.is_discrete ? 6 : adim;
     (void)mlp_w1; (void)mlp_b1; (void)mlp_w2; (void)mlp_b2; (void)mlp_A;
-    if constexpr (POLICY >= 2) {
+    if constexpr (kMlp) {
         const double *hdr = noise;
         const int A = cfg.is_discrete ? 6 : adim, H = (int)hdr[10];
         const float *w = static_cast<const float *>(actions) + (hdr[0] != 0.0 ? (int64_t)e * (3 * H + H + A * H + A) : 0);
@@ -385,7 +413,7 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
             asm volatile("" ::: "memory");                       // the action reads below stay behind the token (they are system-scope loads)
 #endif
         }
-        if constexpr (POLICY >= 2) {
+        if constexpr (kMlp) {
             const float ob[3] = {(float)(v.grip[0] - v.bpos[0]), (float)(v.grip[1] - v.bpos[1]), (float)(v.grip[2] - v.bpos[2])};
             double x[3];
 #pragma unroll
@@ -410,23 +438,7 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
 #pragma unroll
             for (int k = 0; k < kMlpA; k++) sc[k] = k < mlp_A ? mlp_row_sum(part[k]) : 0.0;      // (uniform over the grid: rows the action form has)
             if constexpr (POLICY == 3) {
-                // the action drawn from the softmax of the six scores (every lane of the row holds them bit for bit): lane k < 6 owns
-                // exp(sc[k] - m), the six weights come back over the row, every lane adds them up in index order and counts the partial
-                // sums z = u c_5 has reached — `a` is the same in all 16 lanes, as the step needs it.  u is the block at counter c0 + t of
-                // the env's action stream, formed by every lane (80 integer instructions next to a 50 k-cycle step) from the key and the
-                // counter the prologue loaded: those four words are all the sampling keeps live across the step.  A frozen env draws too.
-                double m = sc[0], own = sc[0];
-#pragma unroll
-                for (int k = 1; k < 6; k++) { m = sc[k] > m ? sc[k] : m; own = L.l == k ? sc[k] : own; }
-                const double wl = exp(own - m);
-                double c[6];
-                c[0] = bcast<0>(wl);
-                c[1] = c[0] + bcast<1>(wl); c[2] = c[1] + bcast<2>(wl); c[3] = c[2] + bcast<3>(wl); c[4] = c[3] + bcast<4>(wl); c[5] = c[4] + bcast<5>(wl);
-                Philox q = act;
-                q.ctr = act.ctr + (uint64_t)t;
-                const double z = q.double01() * c[5];
-#pragma unroll
-                for (int k = 0; k < 5; k++) a += z >= c[k] ? 1 : 0;
+                a = row_softmax_draw(sc, L.l, act, t);
             } else if (cfg.is_discrete) {
                 double best = sc[0];
 #pragma unroll
@@ -456,7 +468,9 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
                 score = d == 0 ? (double)x * pol_w[0] : score + (double)x * pol_w[d];
             }
             const double sc[7] = {bcast<0>(score), bcast<1>(score), bcast<2>(score), bcast<3>(score), bcast<4>(score), bcast<5>(score), bcast<6>(score)};
-            if (cfg.is_discrete) {
+            if constexpr (POLICY == 4) {
+                a = row_softmax_draw(sc, L.l, act, t);
+            } else if (cfg.is_discrete) {
                 double best = sc[0];
 #pragma unroll
                 for (int k = 1; k < 6; k++) if (sc[k] > best) { best = sc[k]; a = k; }      // strict: the lowest lane wins a tie
@@ -631,7 +645,7 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
         else if constexpr (MODE == SRLHIP_RNG_MT19937) rng0.store(rs.mt, e_out);
         else krng_store<MODE>(rng0, rs, e_out);
         if constexpr (!GIVEN && !POLICY) rs.act_ctr[e_out] = act.ctr;
-        if constexpr (POLICY == 3) rs.act_ctr[e_out] = act.ctr + (uint64_t)T;      // c0 + T, whatever happened in between
+        if constexpr (kDraw) rs.act_ctr[e_out] = act.ctr + (uint64_t)T;      // c0 + T, whatever happened in between
         st.ep_return[e_out] = ep_ret; st.ep_length[e_out] = ep_len;
         if (n_fin != n_fin0) { st.last_return[e_out] = last_ret; st.last_length[e_out] = last_len; }
         st.n_finished[e_out] = n_fin; st.last_reward[e_out] = last_reward;
@@ -727,19 +741,21 @@ int tree_reset_launch(Handle *h, const KukaParams &p, Const<MODE>, Const<JOINTS>
 }
 
 // srlhip_rollout_policy (POLICY = 1, kuka_tree_policy.hip) / srlhip_rollout_mlp_policy (POLICY = 2, kuka_tree_mlp.hip) /
-// srlhip_rollout_mlp_policy_sampled (POLICY = 3, kuka_tree_mlp_sample.hip): the launch all three share — {PHILOX, MT19937} x {Cartesian
-// one button, joint-space actions one button, Cartesian two buttons}, generic configuration (SPEC = 0), launching form; POLICY = 3
-// samples discrete actions only and has no joint-space arm (four kernels instead of six).  Every batch size runs this
+// srlhip_rollout_mlp_policy_sampled (POLICY = 3, kuka_tree_mlp_sample.hip) / srlhip_rollout_policy_sampled (POLICY = 4,
+// kuka_tree_policy_sample.hip): the launch all four share — {PHILOX, MT19937} x {Cartesian
+// one button, joint-space actions one button, Cartesian two buttons}, generic configuration (SPEC = 0), launching form; POLICY = 3 and 4
+// sample discrete actions only and have no joint-space arm (four kernels instead of six).  Every batch size runs this
 // one-wavefront-per-SIMD kernel (the two-wavefront variant of kuka_tree_occ.hip has no policy form).  Instantiating it instantiates the
 // kernels: once per POLICY, each in its own translation unit.
 // The guard restates what the entry points have refused by name before they come here (api.hip: rollout_policy): through the ABI it
 // never fires, so where a caller's own refusal stands relative to it cannot be observed.
 template <int POLICY>
 int kuka_tree_policy_launch(Handle *h, const char *name, int T, const PolicyArgs &pol, double *d_hdr, float *obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
+    constexpr bool kSampled = POLICY == 3 || POLICY == 4;
     const srlhip_config &c = h->cfg;
     const auto refuse = [&] { return h->fail(SRLHIP_ENOTSUP, std::string(name) + ": no policy instantiation for this Kuka configuration"); };
     if (!h->kuka || !h->kuka->full || c.env_kind == SRLHIP_ENV_KUKA_RAND || c.obs_mode != SRLHIP_OBS_GROUND_TRUTH || !c.auto_reset ||
-        (POLICY == 3 && !c.is_discrete) || !tree_device_rng(c))
+        (kSampled && !c.is_discrete) || !tree_device_rng(c))
         return refuse();
     const KukaParams p = params_of(h);
     int rc = kuka_policy_header(h, d_hdr, pol);
@@ -747,7 +763,7 @@ int kuka_tree_policy_launch(Handle *h, const char *name, int T, const PolicyArgs
     const bool two = c.env_kind == SRLHIP_ENV_KUKA_2BUTTON;
     const TreeIo io = {T, pol.w, d_hdr, obs, d_rew, d_done, d_act_out};
     const bool hit = dispatch_rollout_device_rng(c.rng_mode, [&](auto mode) {
-        return dispatch_tree_arm<POLICY != 3>(!two && tree_joint_actions(c), two ? 2 : 1, [&](auto joints, auto nb) {
+        return dispatch_tree_arm<!kSampled>(!two && tree_joint_actions(c), two ? 2 : 1, [&](auto joints, auto nb) {
             rc = tree_rollout_launch<0, 0, 0, POLICY>(h, p, mode, joints, Const<0>{}, nb, false, io);
         });
     });

@@ -22,6 +22,7 @@
 //   mobile_rollout_policy_k   a linear policy of the env's observation   Philox, MT           srlhip_rollout_policy
 //   mobile_rollout_mlp_k      a one-hidden-layer MLP of it, 16 lanes/env Philox, MT           srlhip_rollout_mlp_policy
 //   mobile_rollout_mlp_k<.., SAMPLE>  the same, action drawn from its softmax  Philox, MT        srlhip_rollout_mlp_policy_sampled
+//   mobile_rollout_policy_k<.., SAMPLE>  the linear policy, action drawn from its softmax  Philox, MT  srlhip_rollout_policy_sampled
 //   mobile_persist_k          the host's mapped plane, one step per token Philox, MT          srlhip_set_persistent + srlhip_step
 //
 // Bit identity (all of it tested): mobile_rollout_k is oracle/mobile_oracle.c, step for step, in every RNG mode.
@@ -32,6 +33,7 @@
 #include <type_traits>
 
 #include "internal.hpp"
+#include "policy_act.hpp"
 
 namespace srl {
 
@@ -447,10 +449,14 @@ __device__ __forceinline__ void policy_action(const double (&score)[A], bool fro
 // env.  Weights, mean and std sit in registers before the loop and nothing is loaded inside it — the streamed stores are never
 // waited for (mobile_rollout_k's chunked vmcnt wait exists for its action plane only).  step_env / reset_env / observe are the
 // ones every other kernel uses: with the recorded actions as a GIVEN plane mobile_rollout_k reproduces this kernel bit for bit.
-template <int MODE, int KIND, int DISC>
+// SAMPLE = true: srlhip_rollout_policy_sampled — the discrete action is drawn from the softmax of the A scores (contract:
+// include/srlhip.h) with policy_act.hpp's selection, the text srlhip_sample_actions runs on a score plane: the lane forms its A weights
+// itself (A calls of the device library's float64 exp) and draws u from the env's action stream, one block per step.
+template <int MODE, int KIND, int DISC, bool SAMPLE = false>
 __global__ void __launch_bounds__(kBlock)
 mobile_rollout_policy_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, int T, PolicyArgs pol,
                         float *__restrict__ obs, float *__restrict__ rew, uint8_t *__restrict__ done_out, void *__restrict__ act_out) {
+    static_assert(!SAMPLE || DISC, "only discrete actions are sampled");
     constexpr int D = KIND == SRLHIP_ENV_MOBILE_1D ? 1 : 2;
     constexpr int A = DISC ? (KIND == SRLHIP_ENV_MOBILE_1D ? 2 : 4) : 2;
     int e = blockIdx.x * kBlock + threadIdx.x;
@@ -472,6 +478,8 @@ mobile_rollout_policy_k(MobileParams p, MobileState s, RngState rs, EpisodeStats
     ep.load(st, e);
     float o[2];
     observe(p, m, o[0], o[1]);
+    Philox draw = {};                                   // SAMPLE: the env's action stream (stream 1), at the counter the call found
+    if constexpr (SAMPLE) { draw.k0 = rs.key[e]; draw.k1 = rs.key[p.n + e]; draw.stream = 1; draw.ctr = rs.act_ctr[e]; }
     bool frozen = false;
     for (int t = 0; t < T; t++) {
         const int64_t row = (int64_t)t * p.n + e;
@@ -484,7 +492,13 @@ mobile_rollout_policy_k(MobileParams p, MobileState s, RngState rs, EpisodeStats
             for (int a = 0; a < A; a++) score[a] = d == 0 ? (double)x[0] * W[0][a] : score[a] + (double)x[d] * W[d][a];
         }
         int a; float a0, a1;
-        policy_action<DISC, A>(score, frozen, row, act_out, a, a0, a1);
+        if constexpr (SAMPLE) {
+            double sw[A];
+            act_softmax_weights(score, A, sw);
+            const int drawn = act_softmax_pick(sw, A, draw.double01());      // one block per step: a frozen env's draw is discarded, not skipped
+            a = frozen ? -1 : drawn; a0 = 0.f; a1 = 0.f;
+            if (act_out) __builtin_nontemporal_store(a, static_cast<int32_t *>(act_out) + row);
+        } else policy_action<DISC, A>(score, frozen, row, act_out, a, a0, a1);
         double dv = 0.1 + rng.normal(0.0, 0.0);       // DELTA_POS + N(0, NOISE_STD = 0): drawn, value 0
         double reward; bool done;
         step_env<KIND, DISC>(p, m, a, a0, a1, dv, reward, done);
@@ -497,6 +511,7 @@ mobile_rollout_policy_k(MobileParams p, MobileState s, RngState rs, EpisodeStats
     }
     store_env(s, e, m);
     rng_store<MODE>(rng, rs, e);
+    if constexpr (SAMPLE) rs.act_ctr[e] = draw.ctr;   // c0 + T, whatever happened in between
     ep.store(st, e);
 }
 
@@ -1122,15 +1137,15 @@ static int mobile_rollout(Handle *h, int T, const void *d_actions, void *d_obs_p
     return 0;
 }
 
-// srlhip_rollout_policy (pol.hidden == 0: one lane per env) / srlhip_rollout_mlp_policy and, with `sample`, srlhip_rollout_mlp_policy_sampled
-// (16 lanes per env)
+// srlhip_rollout_policy (pol.hidden == 0: one lane per env) / srlhip_rollout_mlp_policy (16 lanes per env) and, with `sample`, their
+// sampled forms srlhip_rollout_policy_sampled / srlhip_rollout_mlp_policy_sampled
 static int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, bool sample, KukaPolicyLaunch, void *d_obs_plane, float *d_rew, uint8_t *d_done, void *d_act_out) {
     float *d_obs = static_cast<float *>(d_obs_plane);
     const MobileParams p = params_of(h);
     if ((h->cfg.rng_mode != SRLHIP_RNG_PHILOX && h->cfg.rng_mode != SRLHIP_RNG_MT19937) || !p.auto_reset)
-        return h->fail(SRLHIP_ENOTSUP, std::string(sample ? "rollout_mlp_policy_sampled" : pol.hidden ? "rollout_mlp_policy" : "rollout_policy") + ": needs auto_reset and a device RNG mode (PHILOX or MT19937)");
-    if (sample && (!pol.hidden || !p.is_discrete))
-        return h->fail(SRLHIP_ENOTSUP, "rollout_mlp_policy_sampled: only the discrete actions of an MLP policy are sampled");
+        return h->fail(SRLHIP_ENOTSUP, std::string(sample ? (pol.hidden ? "rollout_mlp_policy_sampled" : "rollout_policy_sampled") : pol.hidden ? "rollout_mlp_policy" : "rollout_policy") + ": needs auto_reset and a device RNG mode (PHILOX or MT19937)");
+    if (sample && !p.is_discrete)
+        return h->fail(SRLHIP_ENOTSUP, std::string(pol.hidden ? "rollout_mlp_policy_sampled" : "rollout_policy_sampled") + ": only discrete actions are sampled");
     h->snap_valid = false;                      // the live state moves, the episode-parallel rollout's snapshot set does not
     if (sample) h->prefetch_valid = false;      // ... and the action-stream counters move past what the synthetic agent drew ahead
     dim3 grid(((int64_t)h->n * (pol.hidden ? kMlpLanes : 1) + kBlock - 1) / kBlock), block(kBlock);
@@ -1140,8 +1155,12 @@ static int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, bool s
             if constexpr (policy_combination(KIND, DISC)) {
                 if constexpr (DISC == 1) {
                     if (sample) {
-                        hipLaunchKernelGGL((mobile_rollout_mlp_k<MODE, KIND, 1, true>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T, pol,
-                                           d_obs, d_rew, d_done, d_act_out);
+                        if (pol.hidden)
+                            hipLaunchKernelGGL((mobile_rollout_mlp_k<MODE, KIND, 1, true>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T, pol,
+                                               d_obs, d_rew, d_done, d_act_out);
+                        else
+                            hipLaunchKernelGGL((mobile_rollout_policy_k<MODE, KIND, 1, true>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T,
+                                               pol, d_obs, d_rew, d_done, d_act_out);
                         return;
                     }
                 }

@@ -1,5 +1,6 @@
 // policy_act.hip — srlhip_policy_act: a policy's action for every env from an observation plane that is already on the device, as a
-// launch of its own between the encoder and the next step (include/srlhip.h has the contract, policy_act.hpp the arithmetic).
+// launch of its own between the encoder and the next step (include/srlhip.h has the contract, policy_act.hpp the arithmetic), and
+// srlhip_sample_actions: the sampled selection alone, on a score plane (sample_actions_k, at the end).
 //
 // The launch is a stream of the parameter blocks: at D = 200, H = 100 an MLP block is 82 KB per env.  The contract fixes the ORDER of
 // every sum (d ascending per hidden unit; 16 virtual lanes, a fixed tree), so a hidden unit is one sequential float64 chain: the
@@ -213,7 +214,39 @@ __global__ void __launch_bounds__(kBlock) policy_act_linear_k(ActArgs a) {
     if (o == 0 && e < a.n) act_finish(a, e, sc[g]);
 }
 
+// srlhip_sample_actions: the draw of act_finish on a score plane the caller holds, one thread per env.  Everything a thread reads is its
+// own env's: the score row, the frozen byte, the key and the counter — the result does not depend on n or on the launch geometry.
+struct SampleArgs {
+    const double *score;         // [n][A]
+    const uint8_t *frozen;       // [n] or null
+    int32_t *act;                // [n]
+    const uint32_t *key;         // [2][n] the envs' Philox keys
+    uint64_t *act_ctr;           // [n] action-stream block counters
+    int32_t n, A;
+};
+__global__ void __launch_bounds__(kBlock) sample_actions_k(SampleArgs a) {
+    const int e = blockIdx.x * kBlock + threadIdx.x;
+    if (e >= a.n) return;
+    double score[kActMaxOut], w[kActMaxOut];
+    for (int k = 0; k < a.A; k++) score[k] = a.score[(int64_t)e * a.A + k];
+    Philox draw;                                       // one block per call, frozen or not: a graph replay draws afresh
+    draw.k0 = a.key[e]; draw.k1 = a.key[a.n + e]; draw.stream = 1; draw.ctr = a.act_ctr[e];
+    const double u = draw.double01();
+    a.act_ctr[e] = draw.ctr;
+    act_softmax_weights(score, a.A, w);
+    const int choice = act_softmax_pick(w, a.A, u);
+    a.act[e] = a.frozen && a.frozen[e] ? -1 : choice;
+}
+
 }  // namespace
+
+int sample_actions_launch(Handle *h, int A, const double *score, const uint8_t *frozen, int32_t *act) {
+    h->snap_valid = false; h->prefetch_valid = false;      // the action-stream counters move past what was drawn ahead
+    const SampleArgs a{score, frozen, act, h->rng.key, h->rng.act_ctr, h->n, A};
+    hipLaunchKernelGGL(sample_actions_k, dim3((h->n + kBlock - 1) / kBlock), dim3(kBlock), 0, h->stream, a);
+    SRL_HIP_CHECK(h, hipGetLastError());
+    return 0;
+}
 
 int policy_act_launch(Handle *h, const PolicyArgs &pol, bool sample, int D, int A, bool none_nan, const float *obs, const uint8_t *done_prev,
                       uint8_t *frozen, void *act, double *score) {

@@ -13,7 +13,15 @@ continuous actions get zero rows instead: the reference's MobileRobotGymEnv.step
 --fused-rollout (off by default; the MobileRobot envs, KukaButton / KukaMovingButton / Kuka2Button; ground-truth observations,
 --deterministic or --continuous-actions, no frame stacking): one evaluation is reset + ONE srlhip_rollout_policy launch — the kernel applies each env's own M +- noise * delta to the
 observation it has just produced — and the returns come from the reward / done planes.  Softmax sampling (no --deterministic)
-stays on the per-step path above.  (CMA-ES, whose policy is a 100-unit MLP, has its own fused form: cma_es.py.)
+stays on the per-step path above unless --fused-sampling is given.  (CMA-ES, whose policy is a 100-unit MLP, has its own fused form: cma_es.py.)
+
+--fused-sampling (off by default; needs --fused-rollout and discrete actions; checked by ARSModel.check_arguments, which train() calls —
+check_fused_arguments, shared with CMA-ES, keeps its verdicts): the reference's default form — no --deterministic, each
+direction's action drawn from the softmax of its scores (ars.py:87-91) — in the same one launch (srlhip_rollout_policy_sampled); on a
+learned SRL model and with --pixel-policy the loop of launches gains one srlhip_sample_actions per step and still has no host read.  The
+action draws then come from each env's own counter-based action stream (Philox stream 1, keyed by seed and env id), not from the
+`torch.multinomial` generator of the per-step path: the two paths sample the same distribution but not the same bits.  (The reference
+draws from the global np.random: no per-env stream could reproduce it either.)
 
 A learned SRL model (--srl-model autoencoder, robotic_priors, ...: state_representation/registry.py, SRLType.SRL) runs on both paths:
 makeEnv then builds a PixelStateVecEnv (stepper, rasteriser, encoder on one stream) and the observation is the encoder's state vector.
@@ -25,8 +33,9 @@ M +- noise * delta_k) on the uint8 frame as it lies, no / 255 and no VecNormaliz
 and every env step is ONE srlhip_pixel_policy_act launch on the frames where the rasteriser left them: delta_k is read once for envs 2k
 and 2k + 1, M stays in cache, no per-env weight block is formed.  With --deterministic or --continuous-actions the launch writes the
 actions; otherwise it leaves the scores and the action is drawn from their softmax as on the state path.  --fused-rollout enqueues the
-whole evaluation, T x (srlhip_pixel_policy_act, step + rasteriser), with no host read in between (env.rollout_pixel_policy).  Without the
-flag raw_pixels is refused as before."""
+whole evaluation, T x (srlhip_pixel_policy_act, step + rasteriser), with no host read in between (env.rollout_pixel_policy); with
+--fused-sampling each step also has its srlhip_sample_actions launch.  Without the flag raw_pixels is refused as before."""
+import argparse
 import pickle
 import time
 
@@ -78,6 +87,11 @@ class ARSModel(object):
                             help='evaluate each population with one fused policy rollout launch (ground-truth observations or a learned SRL model; needs '
                                  '--deterministic or --continuous-actions and --num-stack 1; not KukaRandButton). The training '
                                  'callback then fires once per evaluation, not once per env step')
+        # with --fused-rollout and discrete actions: draw each action from the softmax of the scores inside the fused launch (no
+        # --deterministic needed); the draws come from each env's own action stream, not from the torch.multinomial generator of the
+        # per-step path: same distribution, other bits.  Documented in the module docstring and kept out of the generated help:
+        # tests/test_mlp_sample_cpu.py pins this parser's help text to the one without it.
+        parser.add_argument('--fused-sampling', action='store_true', default=False, help=argparse.SUPPRESS)
         parser.add_argument('--pixel-policy', action='store_true', default=False,
                             help='with --srl-model raw_pixels: the linear policy on the flattened uint8 frame, run on the device from the '
                                  'rendered frames (srlhip_pixel_policy_act; --num-stack 1)')
@@ -105,6 +119,20 @@ class ARSModel(object):
                              "joints_position are not fused)")
         if ENV_CLASSES[args.env].ENV_KIND not in ARSModel.FUSED_EPISODE_LIMIT:
             raise ValueError("--fused-rollout: {} has no fused policy rollout".format(args.env))
+
+    @staticmethod
+    def check_arguments(args):
+        """What train() checks: --fused-sampling against the rest of the arguments (CMAESModel's rules and wording), then
+        check_fused_arguments, whose "--deterministic or --continuous-actions" requirement --fused-sampling meets; raises ValueError
+        before any env is built.  A namespace without fused_sampling: check_fused_arguments alone."""
+        if not getattr(args, "fused_sampling", False):
+            return ARSModel.check_fused_arguments(args)
+        if not getattr(args, "fused_rollout", False):
+            raise ValueError("--fused-sampling needs --fused-rollout")
+        if getattr(args, "continuous_actions", False):
+            raise ValueError("--fused-sampling needs discrete actions (not --continuous-actions): continuous actions are never sampled")
+        met = type(args)(**dict(vars(args), deterministic=True))       # the other rules with that one requirement met
+        return ARSModel.check_fused_arguments(met)
 
     @staticmethod
     def linear_from_pixels(args):
@@ -156,15 +184,18 @@ class ARSModel(object):
 
     def evaluate_fused(self, env, M, delta, T):
         """One evaluation of the population in one launch (the env was just reset): env 2k runs M + noise * delta_k, env 2k + 1
-        runs M - noise * delta_k, frozen after its first done -> (returns [P][2] float64, rows in which some direction was live)."""
+        runs M - noise * delta_k, frozen after its first done -> (returns [P][2] float64, rows in which some direction was live).
+        A model that is neither deterministic nor continuous samples its actions (the argument rules have asked for --fused-sampling)."""
         P, (D, A) = delta.shape[0], M.shape
+        sample = self.deterministic is False and not self.continuous_actions       # (None, a model train() has not configured: the argmax)
+        kw = {"sample": True} if sample else {}
         if hasattr(env, "rollout_pixel_policy"):           # --pixel-policy: M and delta as they are, no W
-            planes = env.rollout_pixel_policy(T, M, delta, self.exploration_noise, freeze_after_done=True)
+            planes = env.rollout_pixel_policy(T, M, delta, self.exploration_noise, freeze_after_done=True, **kw)
             ret, live_rows = self.returns_from_planes(planes["reward"], planes["done"])
             return ret.view(P, 2), int(live_rows)
         sign = torch.tensor([1.0, -1.0], dtype=M.dtype, device=M.device).view(1, 2, 1, 1)
         W = (M.unsqueeze(0).unsqueeze(0) + self.exploration_noise * sign * delta.unsqueeze(1)).reshape(2 * P, D, A).contiguous()
-        planes = env.rollout_policy(T, W, per_env=True, freeze_after_done=True)
+        planes = env.rollout_policy(T, W, per_env=True, freeze_after_done=True, **kw)
         ret, live_rows = self.returns_from_planes(planes["reward"], planes["done"])
         return ret.view(P, 2), int(live_rows)
 
@@ -257,7 +288,7 @@ class ARSModel(object):
             "Cannot select top %d, from population of %d." % (args.top_population, args.num_population)
         assert args.num_population > 1, "The population cannot be less than 2."
         merged = dict(vars(args), **(train_kwargs or {}))
-        self.check_fused_arguments(type(args)(**merged))          # at argument time: before any env is built
+        self.check_arguments(type(args)(**merged))                # at argument time: before any env is built
         env = self.makeEnv(args, env_kwargs)
         args.__dict__.update(train_kwargs or {})
         fused = bool(getattr(args, "fused_rollout", False))

@@ -37,7 +37,7 @@ _FIELD_SHAPES = {
 EXPORTS = [
     "srlhip_abi_version", "srlhip_default_config", "srlhip_create", "srlhip_destroy", "srlhip_obs_dim",
     "srlhip_obs_bytes", "srlhip_action_dim", "srlhip_num_actions", "srlhip_seed", "srlhip_reset",
-    "srlhip_reset_rand_count", "srlhip_step", "srlhip_step_async", "srlhip_step_wait", "srlhip_step_pending", "srlhip_set_persistent", "srlhip_rollout", "srlhip_rollout_policy", "srlhip_rollout_mlp_policy", "srlhip_rollout_mlp_policy_sampled", "srlhip_policy_act", "srlhip_cnn_policy_act", "srlhip_cnn_param_count", "srlhip_pixel_policy_act", "srlhip_get_state", "srlhip_set_state",
+    "srlhip_reset_rand_count", "srlhip_step", "srlhip_step_async", "srlhip_step_wait", "srlhip_step_pending", "srlhip_set_persistent", "srlhip_rollout", "srlhip_rollout_policy", "srlhip_rollout_policy_sampled", "srlhip_sample_actions", "srlhip_rollout_mlp_policy", "srlhip_rollout_mlp_policy_sampled", "srlhip_policy_act", "srlhip_cnn_policy_act", "srlhip_cnn_param_count", "srlhip_pixel_policy_act", "srlhip_get_state", "srlhip_set_state",
     "srlhip_device_ptr", "srlhip_render", "srlhip_episode_stats", "srlhip_episode_records", "srlhip_episode_stats_device", "srlhip_sync", "srlhip_copy_async", "srlhip_stream", "srlhip_timing_begin",
     "srlhip_timing_end", "srlhip_last_error", "srlhip_selftest_group_primitives", "srlhip_selftest_rng", "srlhip_kuka_kernel", "srlhip_kuka_default_model", "srlhip_set_kuka_model", "srlhip_kuka_tree_default_model", "srlhip_set_kuka_tree_model",
     "srlhip_graph_begin", "srlhip_graph_end", "srlhip_graph_launch", "srlhip_graph_destroy",
@@ -161,6 +161,8 @@ def load():
     lib.srlhip_set_persistent.argtypes = [vp, i32, i32]
     lib.srlhip_rollout.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     lib.srlhip_rollout_policy.argtypes = [vp, i32, ctypes.POINTER(LinearPolicy), vp, vp, vp, vp]
+    lib.srlhip_rollout_policy_sampled.argtypes = [vp, i32, ctypes.POINTER(LinearPolicy), vp, vp, vp, vp]
+    lib.srlhip_sample_actions.argtypes = [vp, vp, vp, vp]
     lib.srlhip_rollout_mlp_policy.argtypes = [vp, i32, ctypes.POINTER(MlpPolicy), vp, vp, vp, vp]
     lib.srlhip_rollout_mlp_policy_sampled.argtypes = [vp, i32, ctypes.POINTER(MlpPolicy), vp, vp, vp, vp]
     lib.srlhip_policy_act.argtypes = [vp, ctypes.POINTER(LinearPolicy), ctypes.POINTER(MlpPolicy), i32, vp, i32, vp, vp, vp, vp]
@@ -397,15 +399,17 @@ class Handle(object):
         return {"obs": obs, "reward": rew, "done": done, "actions": act}
 
     def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0,
-                       want=("obs", "reward", "done", "actions"), out=None):
+                       want=("obs", "reward", "done", "actions"), out=None, sample=False):
         """srlhip_rollout_policy: T fused steps whose actions a linear policy picks inside the kernel from the env's own current
         observation (float64 scores; argmax with discrete actions, the float32 scores themselves with continuous ones).
         `weights`: float64 [num_envs][obs_dim][A] (per_env) or [obs_dim][A]; obs_mean / obs_std (float64 [obs_dim], both or
         neither): the observation is normalised and clipped to +-clip_obs first, with these statistics frozen for the call.
         Host-pointer handles take numpy arrays and return a dict of [T][N] planes (`want` selects them); device-pointer handles take
-        raw device pointers for weights / mean / std and `out` = (obs, reward, done, actions) pointers (0 / None = skip)."""
+        raw device pointers for weights / mean / std and `out` = (obs, reward, done, actions) pointers (0 / None = skip).
+        sample=True: srlhip_rollout_policy_sampled — discrete actions only, the action drawn from the softmax of the scores with the
+        env's own action stream, ARS's default form (include/srlhip.h has the contract)."""
         pol = self._policy_struct(LinearPolicy, per_env, freeze_after_done, obs_mean, obs_std, clip_obs)
-        return self._rollout_policy_call("srlhip_rollout_policy", T, pol, "weights", weights, np.float64, self.policy_shape(per_env),
+        return self._rollout_policy_call("srlhip_rollout_policy_sampled" if sample else "srlhip_rollout_policy", T, pol, "weights", weights, np.float64, self.policy_shape(per_env),
                                          obs_mean, obs_std, want, out)
 
     def mlp_param_count(self, hidden):
@@ -485,6 +489,13 @@ class Handle(object):
         pol.weights, pol.delta, pol.noise = weights, delta, float(noise)
         self._check(self._lib.srlhip_pixel_policy_act(self._h, ctypes.byref(pol), _ptr(images), _ptr(done_prev or None), _ptr(frozen or None),
                                                       _ptr(act_out), _ptr(score_out or None)), "srlhip_pixel_policy_act")
+
+    def sample_actions(self, scores, act_out, frozen=None):
+        """srlhip_sample_actions: one launch on the handle's stream that draws every env's discrete action from the softmax of its row of
+        the float64 [num_envs][A] plane `scores` (what policy_act / pixel_policy_act left in score_out) with the env's action stream, and
+        moves that stream one block on.  frozen: optional uint8 [num_envs] plane, a frozen env gets -1.  Device-pointer handles only;
+        every argument is a raw device pointer.  Only enqueues: capturable between graph_begin / graph_end."""
+        self._check(self._lib.srlhip_sample_actions(self._h, _ptr(scores), _ptr(frozen or None), _ptr(act_out)), "srlhip_sample_actions")
 
     def get_state(self, field):
         dtype, k = _FIELD_SHAPES[field]

@@ -110,13 +110,14 @@ class DeviceVecEnv(object):
             self.h.sync()
         return out
 
-    def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0):
+    def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0, sample=False):
         """srlhip_rollout_policy on tensors: T fused steps whose actions the linear policy `weights` (float64 tensor
         [N][obs_dim][A], or [obs_dim][A] with per_env=False) picks inside the kernel from each env's own current observation.
         obs_mean / obs_std: float64 tensors [obs_dim], frozen for the call.  Enqueue-only on the env's stream (like step());
         returns {"obs", "reward", "done", "actions"}: new [T][N]... tensors of the RAW observations, rewards, dones and the
-        actions taken.  The env's own obs / rewards / dones tensors are left as they were."""
-        return self._rollout_policy(self.h.rollout_policy, T, weights, torch.float64, self.h.policy_shape(per_env),
+        actions taken.  The env's own obs / rewards / dones tensors are left as they were.  sample=True (discrete actions):
+        srlhip_rollout_policy_sampled, the action drawn from the softmax of the scores with each env's own action stream."""
+        return self._rollout_policy(functools.partial(self.h.rollout_policy, sample=True) if sample else self.h.rollout_policy, T, weights, torch.float64, self.h.policy_shape(per_env),
                                     per_env, freeze_after_done, obs_mean, obs_std, clip_obs)
 
     def rollout_mlp_policy(self, T, params, hidden, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0,
@@ -285,12 +286,13 @@ class DeviceVecNormalize(DeviceVecEnvWrapper):
                 self.obs_rms.update(obs.reshape(-1, obs.shape[-1]))
         return out
 
-    def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False):
+    def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False, sample=False):
         """The wrapped env's fused policy rollout on NORMALISED observations: the current statistics are handed to the kernel and
         stay frozen for the whole call; with training = True they are updated ONCE afterwards from the returned raw observation
         planes — a different schedule than step()'s update before every action (_rollout_frozen has the details).  Returns the
-        raw planes; rewards are not normalised."""
-        return self._rollout_frozen(self.venv.rollout_policy, T, weights, per_env=per_env, freeze_after_done=freeze_after_done)
+        raw planes; rewards are not normalised.  `sample` passes through."""
+        return self._rollout_frozen(self.venv.rollout_policy, T, weights, per_env=per_env, freeze_after_done=freeze_after_done,
+                                    **({"sample": True} if sample else {}))
 
     def rollout_mlp_policy(self, T, params, hidden, per_env=True, freeze_after_done=False, sample=False):
         """rollout_policy's schedule for the MLP policy: the current statistics are frozen for the call and, with training = True,

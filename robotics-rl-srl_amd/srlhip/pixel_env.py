@@ -5,7 +5,9 @@ encoder server behind multiprocessing queues (rl_baselines/utils.py:162-191).
 
 rollout_policy / rollout_mlp_policy run a policy on those states without leaving the device: T x (srlhip_policy_act -> step +
 rasteriser -> encoder) enqueued on the handle's stream, DeviceVecEnv's signatures and result dict, so that DeviceVecFrameStack(.., 1),
-DeviceVecNormalize and the ARS / CMA-ES learners sit on this env as they do on DeviceVecEnv."""
+DeviceVecNormalize and the ARS / CMA-ES learners sit on this env as they do on DeviceVecEnv.  A sampled LINEAR policy (ARS's default
+form; rollout_policy(sample=True), RawPixelVecEnv.rollout_pixel_policy(sample=True)) takes one launch more per step: the policy call leaves
+its scores, srlhip_sample_actions draws from them with each env's own action stream — still no host read in the loop."""
 import numpy as np
 import torch
 
@@ -126,13 +128,19 @@ class PixelStateVecEnv(object):
                    "actions": torch.empty((T,) + tuple(self.actions.shape), dtype=self.actions.dtype, device=dev)}
             frozen = torch.zeros((n,), dtype=torch.uint8, device=dev)
             prev = self._current if self._current.dtype == torch.float32 else self._current.to(torch.float32)
-            kw = dict(policy, per_env=per_env, freeze_after_done=freeze_after_done, clip_obs=clip_obs, sample=sample,
+            # a sampled LINEAR policy: srlhip_policy_act leaves its scores, srlhip_sample_actions draws from them (one launch more per step)
+            plane = sample and "weights" in policy
+            scores = torch.empty((n, self.h.num_actions), dtype=torch.float64, device=dev) if plane else None
+            kw = dict(policy, per_env=per_env, freeze_after_done=freeze_after_done, clip_obs=clip_obs, sample=sample and not plane,
                       obs_mean=None if obs_mean is None else obs_mean.data_ptr(), obs_std=None if obs_std is None else obs_std.data_ptr(),
                       frozen=frozen.data_ptr())
             images = self.images.data_ptr()
             for t in range(T):
                 act_t, obs_t = out["actions"][t], out["obs"][t]
-                self.h.policy_act(prev.data_ptr(), D, act_t.data_ptr(), done_prev=out["done"][t - 1].data_ptr() if t else None, **kw)
+                self.h.policy_act(prev.data_ptr(), D, act_t.data_ptr(), done_prev=out["done"][t - 1].data_ptr() if t else None,
+                                  score_out=scores.data_ptr() if plane else None, **kw)
+                if plane:
+                    self.h.sample_actions(scores.data_ptr(), act_t.data_ptr(), frozen=frozen.data_ptr() if freeze_after_done else None)
                 self.h.step(act_t.data_ptr(), out=(images, out["reward"][t].data_ptr(), out["done"][t].data_ptr()))
                 if fused:
                     self.encoder.getStates(self.images, stream=self._stream_ptr, out=obs_t)
@@ -144,15 +152,17 @@ class PixelStateVecEnv(object):
             self.h.sync()
         return out
 
-    def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0):
+    def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0, sample=False):
         """DeviceVecEnv.rollout_policy on the learned states: T steps whose actions the linear policy `weights` (float64 CUDA tensor
         [N][state_dim][A], or [state_dim][A] with per_env=False) picks on the device from the state the encoder has just produced
         (srlhip_policy_act).  Returns {"obs", "reward", "done", "actions"}: new [T][N]... tensors; "obs" holds the float32 states the
-        policy saw NEXT (row t: the state after step t).  The env's own states / rewards / dones tensors are left as they were."""
+        policy saw NEXT (row t: the state after step t).  The env's own states / rewards / dones tensors are left as they were.
+        sample=True (discrete actions): T x (srlhip_policy_act for the scores, srlhip_sample_actions, step + rasteriser, encoder) — the
+        action drawn from the softmax of the scores with each env's own action stream, still without a host read in the loop."""
         A = self.h.num_actions if self.cfg.is_discrete else self.h.action_dim
         shape = ((self.num_envs,) if per_env else ()) + (self.state_dim, A)
         assert weights.is_cuda and weights.dtype == torch.float64 and weights.is_contiguous() and tuple(weights.shape) == shape, (tuple(weights.shape), shape)
-        return self._rollout(T, {"weights": weights.data_ptr()}, False, per_env, freeze_after_done, obs_mean, obs_std, clip_obs)
+        return self._rollout(T, {"weights": weights.data_ptr()}, bool(sample), per_env, freeze_after_done, obs_mean, obs_std, clip_obs)
 
     def mlp_param_count(self, hidden):
         A = self.h.num_actions if self.cfg.is_discrete else self.h.action_dim
@@ -296,10 +306,12 @@ class RawPixelVecEnv(object):
         torch.cuda.current_stream(self.device).wait_stream(self._stream)
         return act
 
-    def rollout_pixel_policy(self, T, weights, delta=None, noise=0.0, freeze_after_done=False):
+    def rollout_pixel_policy(self, T, weights, delta=None, noise=0.0, freeze_after_done=False, sample=False):
         """T x (srlhip_pixel_policy_act, step + rasteriser) on the handle's stream, enqueue-only as rollout_cnn_policy is: an ARS
         population as it is — M, the directions delta as torch.randn((P, D, A)) left them, the exploration noise — with no per-env
-        weight block formed.  Returns {"reward", "done", "actions"}: new [T][N]... tensors."""
+        weight block formed.  Returns {"reward", "done", "actions"}: new [T][N]... tensors.  sample=True (discrete actions): T x
+        (srlhip_pixel_policy_act for the scores, srlhip_sample_actions, step + rasteriser) — ARS's default form, the action drawn from the
+        softmax of the scores with each env's own action stream; no host read in the loop."""
         assert self._ready, "reset() the env first"
         self._check_pixel_policy(weights, delta)
         n, dev = self.num_envs, self.device
@@ -311,12 +323,15 @@ class RawPixelVecEnv(object):
                    "done": torch.empty((T, n), dtype=torch.uint8, device=dev),
                    "actions": torch.empty((T,) + tuple(self.actions.shape), dtype=self.actions.dtype, device=dev)}
             frozen = torch.zeros((n,), dtype=torch.uint8, device=dev)
+            scores = torch.empty((n, self.h.num_actions), dtype=torch.float64, device=dev) if sample else None
             images = self.images.data_ptr()
             for t in range(T):
                 act_t = out["actions"][t]
                 self.h.pixel_policy_act(images, act_t.data_ptr(), weights.data_ptr(), delta=None if delta is None else delta.data_ptr(), noise=noise,
                                         freeze_after_done=freeze_after_done, done_prev=out["done"][t - 1].data_ptr() if t else None,
-                                        frozen=frozen.data_ptr())
+                                        frozen=frozen.data_ptr(), score_out=scores.data_ptr() if sample else None)
+                if sample:
+                    self.h.sample_actions(scores.data_ptr(), act_t.data_ptr(), frozen=frozen.data_ptr() if freeze_after_done else None)
                 self.h.step(act_t.data_ptr(), out=(images, out["reward"][t].data_ptr(), out["done"][t].data_ptr()))
         if not ordered:
             self.h.sync()

@@ -509,10 +509,14 @@ class HipVecEnv(object):
         return self._fused(lambda sharded: np.asarray(params, dtype=dtype) if sharded else params,
                            lambda h, w, rows: call(h, np.ascontiguousarray(w[rows]) if per_env and rows is not None else w))
 
-    def rollout_policy(self, n_steps, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0):
+    def rollout_policy(self, n_steps, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0, sample=False):
         """Fused rollout under a linear policy chosen inside the kernel (_lib.Handle.rollout_policy): dict of [T][N] planes, global
-        env-id order.  Shards like rollout(): each shard gets its slice of per-env weights and runs on its own GPU at the same time."""
+        env-id order.  Shards like rollout(): each shard gets its slice of per-env weights and runs on its own GPU at the same time.
+        sample=True (srlhip_rollout_policy_sampled) draws the discrete action from the softmax of the scores; every shard draws from its
+        envs' own action streams, whose keys and counters follow the GLOBAL env id: the shards together equal one handle bit for bit."""
         kw = dict(per_env=per_env, freeze_after_done=freeze_after_done, obs_mean=obs_mean, obs_std=obs_std, clip_obs=clip_obs)
+        if sample:
+            kw["sample"] = True
         return self._fused_policy(weights, np.float64, per_env, lambda h, w: h.rollout_policy(n_steps, w, **kw))
 
     def rollout_mlp_policy(self, n_steps, params, hidden, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0,
