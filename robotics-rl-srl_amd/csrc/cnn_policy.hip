@@ -1,5 +1,6 @@
 // cnn_policy.hip — srlhip_cnn_policy_act: the action of every env's own three-layer CNN from the frame the rasteriser has just written,
-// as one launch between two steps (include/srlhip.h has the contract, cnn_policy.hpp the arithmetic).
+// as one launch between two steps (include/srlhip.h has the contract, cnn_policy.hpp the arithmetic, policy_act.hpp the finishing step
+// behind the scores: act_finish).
 //
 // One workgroup of 256 threads per env: N different networks on N frames share nothing but the code.  The frame is streamed once as
 // bytes (a 256-entry table in LDS turns a byte into (float)(b / 255.0)); a layer's weights are staged into LDS transposed, so that the
@@ -23,15 +24,14 @@ constexpr int kRedDoubles = 64;                           // per channel and 64-
 struct CnnArgs {
     const float *params;         // [n][P] or [P]
     const uint8_t *images;       // [n][H][W][C]
-    const uint8_t *done_prev;    // [n] or null
-    uint8_t *frozen;             // [n]
-    void *act;                   // int32 [n] / float [n][A]
     const uint32_t *key;         // [2][n] the envs' Philox keys
     uint64_t *act_ctr;           // [n] action-stream block counters
     float *score;                // [n][A] or null
     CnnShape s;
     CnnParamLayout L;
-    int32_t n, A, per_env, freeze, discrete, sample, none_nan;
+    int32_t n, per_env;
+    ActFinish fin;               // last: read once, by the finishing thread.  The kernel is at its register limit and the order of this block
+                                 // moves its allocation: with `fin` in front of `key` it reserved 36 bytes of scratch (profiles/NOTES.md AX)
 };
 
 // the workgroup's LDS: float64 first, then the float planes
@@ -122,32 +122,14 @@ __global__ void __launch_bounds__(kCnnBlock) cnn_policy_act_k(CnnArgs a) {
     const auto plane2 = [=](int ci, int r, int c) { return (r >= 0 && r < h2 && c >= 0 && c < w2) ? p2[(ci * h2 + r) * w2 + c] : 0.f; };
     cnn_layer<3, 1, kCnnCh3, kCnnCg3>(plane2, kCnnCh2, s.hc[2], s.wc[2], P + a.L.w3, P + a.L.g3, P + a.L.b3, l, l.p3);
 
-    if (tid < a.A) l.sc[tid] = cnn_fc(P + a.L.fcw + (int64_t)tid * s.F, P[a.L.fcb + tid], l.p3, s.F);
+    if (tid < a.fin.A) l.sc[tid] = cnn_fc(P + a.L.fcw + (int64_t)tid * s.F, P[a.L.fcb + tid], l.p3, s.F);
     __syncthreads();
     if (tid != 0) return;
-    // the env's one finishing thread: freeze bookkeeping, the draw, the action row (srlhip_policy_act's, on (double)score)
-    double score[kActMaxOut];
-    for (int k = 0; k < a.A; k++) score[k] = (double)l.sc[k];
-    bool frozen = false;
-    if (a.freeze) {
-        const uint8_t f = act_frozen(a.frozen[e], a.done_prev != nullptr, a.done_prev ? a.done_prev[e] : (uint8_t)0);
-        a.frozen[e] = f;
-        frozen = f != 0;
-    }
-    if (a.score)
-        for (int k = 0; k < a.A; k++) a.score[(int64_t)e * a.A + k] = l.sc[k];
-    int choice = 0;
-    if (a.sample) {
-        // one block of the env's action stream per call, frozen or not: the counter moves inside the kernel, a graph replay draws afresh
-        Philox draw;
-        draw.k0 = a.key[e]; draw.k1 = a.key[a.n + e]; draw.stream = 1; draw.ctr = a.act_ctr[e];
-        const double u = draw.double01();
-        a.act_ctr[e] = draw.ctr;
-        double w[kActMaxOut];
-        act_softmax_weights(score, a.A, w);
-        choice = act_softmax_pick(w, a.A, u);
-    } else if (a.discrete) choice = act_argmax(score, a.A);
-    act_store(a.act, e, a.A, a.discrete != 0, a.none_nan != 0, frozen, choice, score);
+    // the env's one finishing thread: the draw, then policy_act.hpp's finishing step on (double)score (the score plane stays float32).
+    // The float64 scores go where the layers' reduction block was: as a private array they cost the kernel 36 bytes of scratch (profiles/NOTES.md AX)
+    static_assert(kActMaxOut <= kRedDoubles, "the reduction block holds the float64 scores");
+    for (int k = 0; k < a.fin.A; k++) l.red[k] = (double)l.sc[k];
+    act_finish(a.fin, e, l.red, a.score, a.fin.sample ? act_draw(a.key, a.n, a.act_ctr, e) : 0.0);
 }
 
 }  // namespace
@@ -156,9 +138,8 @@ int cnn_policy_act_launch(Handle *h, const float *params, bool per_env, bool fre
                           const uint8_t *done_prev, uint8_t *frozen, void *act, float *score) {
     const srlhip_config &c = h->cfg;
     const int C = c.multi_view ? 6 : 3;
-    if (sample) { h->snap_valid = false; h->prefetch_valid = false; }      // the action-stream counters move past what was drawn ahead
-    CnnArgs a{params, images, done_prev, frozen, act, h->rng.key, h->rng.act_ctr, score, cnn_shape(C, c.img_h, c.img_w), cnn_param_layout(C, c.img_h, c.img_w, A),
-              h->n, A, per_env ? 1 : 0, freeze ? 1 : 0, c.is_discrete ? 1 : 0, sample ? 1 : 0, none_nan ? 1 : 0};
+    CnnArgs a{params, images, h->rng.key, h->rng.act_ctr, score, cnn_shape(C, c.img_h, c.img_w), cnn_param_layout(C, c.img_h, c.img_w, A), h->n, per_env ? 1 : 0,
+              act_finish_args(h, freeze, sample, A, none_nan, done_prev, frozen, act)};
     const size_t lds = lds_bytes(a.s);
     SRL_HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(cnn_policy_act_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(cnn_policy_act_k, dim3(h->n), dim3(kCnnBlock), lds, h->stream, a);

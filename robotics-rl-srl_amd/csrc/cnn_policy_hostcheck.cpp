@@ -12,22 +12,14 @@
 //   cnn_policy_hostcheck refusals    one line per argument case: the code and the message of the checks
 // The workgroup's threads are walked one after the other: thread u of group g takes the cells u, u + TG, ..., its partial sums are
 // combined by cnn_tree_sum over the TG threads — the kernel's butterfly, in thread order.
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <vector>
-
 #include "cnn_policy.hpp"
+#include "hostcheck_io.hpp"
 #include "policy_act.hpp"
 
 using namespace srl;
-
-template <class T> static bool rd(FILE *f, std::vector<T> &v, size_t count) {
-    v.resize(count);
-    return count == 0 || fread(v.data(), sizeof(T), count, f) == count;
-}
-template <class T> static bool wr(FILE *f, const std::vector<T> &v) { return v.empty() || fwrite(v.data(), sizeof(T), v.size(), f) == v.size(); }
 
 template <int K, int PAD, int CO, int CG, class In>
 static void layer(const In &in, int Cin, int hc, int wc, const float *w, const float *gamma, const float *beta, std::vector<float> &pooled) {
@@ -83,7 +75,6 @@ static int print_shapes() {
     return 0;
 }
 
-static void verdict(const char *what, const Verdict &v) { printf("%s: %d %s\n", what, v.code, v.msg ? v.msg : "accepted"); }
 static int print_refusals() {
     srlhip_cnn_policy pol;
     float dummy = 0.f;
@@ -134,18 +125,14 @@ int main(int argc, char **argv) {
     std::vector<double> wout((size_t)N * A, 0.0);
     std::vector<int32_t> act_i(discrete ? N : 0);
     std::vector<float> act_f(discrete ? 0 : (size_t)N * A);
+    const ActFinish fin{has_done ? done_prev.data() : nullptr, frozen.data(), discrete ? static_cast<void *>(act_i.data()) : static_cast<void *>(act_f.data()),
+                        A, freeze, discrete, sample, none_nan};
     for (int e = 0; e < N; e++) {
-        forward(s, L, params.data() + (per_env ? (size_t)e * L.total : 0), frames.data() + (size_t)e * fb, A, &score[(size_t)e * A]);
+        float sf[kActMaxOut];
+        forward(s, L, params.data() + (per_env ? (size_t)e * L.total : 0), frames.data() + (size_t)e * fb, A, sf);
         double sd[kActMaxOut];
-        for (int k = 0; k < A; k++) sd[k] = (double)score[(size_t)e * A + k];
-        bool fz = false;
-        if (freeze) { frozen[e] = act_frozen(frozen[e], has_done, done_prev[e]); fz = frozen[e] != 0; }
-        int choice = 0;
-        if (sample) {
-            act_softmax_weights(sd, A, &wout[(size_t)e * A]);
-            choice = act_softmax_pick(&wout[(size_t)e * A], A, u[e]);
-        } else if (discrete) choice = act_argmax(sd, A);
-        act_store(discrete ? static_cast<void *>(act_i.data()) : static_cast<void *>(act_f.data()), e, A, discrete, none_nan, fz, choice, sd);
+        for (int k = 0; k < A; k++) sd[k] = (double)sf[k];
+        act_finish(fin, e, sd, score.data(), u[e], &wout[(size_t)e * A]);
     }
     f = fopen(argv[2], "wb");
     if (!f) { perror(argv[2]); return 2; }

@@ -99,6 +99,10 @@ struct EnvOps {
 };
 const EnvOps &mobile_env_ops();      // mobile.hip
 const EnvOps &kuka_env_ops();        // kuka.hip
+// policy_act.hip: the finishing step's arguments (policy_act.hpp: ActFinish; its users include that header) as the three action launchers
+// below fill them.  A sampled call moves the action-stream counters past what was drawn ahead: snap_valid and prefetch_valid fall here
+struct ActFinish;
+ActFinish act_finish_args(Handle *h, bool freeze, bool sample, int A, bool none_nan, const uint8_t *d_done_prev, uint8_t *d_frozen, void *d_act);
 // policy_act.hip: srlhip_policy_act behind its argument checks — one launch on the handle's stream, no allocation, no synchronisation.
 // D = floats per row of obs, A = scores per env; none_nan: a frozen env's continuous row is NaNs (Kuka), not zeros (MobileRobot)
 int policy_act_launch(Handle *h, const PolicyArgs &pol, bool sample, int D, int A, bool none_nan, const float *d_obs, const uint8_t *d_done_prev,

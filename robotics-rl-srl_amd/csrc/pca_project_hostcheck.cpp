@@ -7,20 +7,13 @@
 //     result  float64 [n][S] | float32 [n][S] the states
 //   pca_project_hostcheck rules      one line per case of the shape and argument rules: the code and the message; then the launch's shape
 //                                    (chunks, padded S, frames of a tile, tiles, tiles of one launch) for a few (F, S, n)
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <vector>
-
+#include "hostcheck_io.hpp"
 #include "pca_project.hpp"
 
 using namespace srl;
-
-template <class T> static bool rd(FILE *f, std::vector<T> &v, size_t count) {
-    v.resize(count);
-    return count == 0 || fread(v.data(), sizeof(T), count, f) == count;
-}
 
 static void verdict(const char *what, long long a, long long b, const Verdict &v) { printf("%s %lld %lld: %d %s\n", what, a, b, v.code, v.msg ? v.msg : "accepted"); }
 
@@ -66,6 +59,6 @@ int main(int argc, char **argv) {
     pca_project_host(F, (int32_t)S, w.data(), b.data(), frames.data(), (int32_t)n, out.data(), f32);
     f = fopen(argv[2], "wb");
     if (!f) { perror(argv[2]); return 2; }
-    const bool wrote = out.empty() || fwrite(out.data(), 1, out.size(), f) == out.size();
+    const bool wrote = wr(f, out);
     return fclose(f) == 0 && wrote ? 0 : 2;
 }

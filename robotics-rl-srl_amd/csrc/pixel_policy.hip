@@ -1,6 +1,6 @@
 // pixel_policy.hip — srlhip_pixel_policy_act: ARS's linear policy on the raw frame, np.dot(obs.reshape(-1), M +- noise * delta_k), for every
 // env from the frame the rasteriser has just written, as one launch (include/srlhip.h has the contract, pixel_policy.hpp the arithmetic
-// and the summation order).
+// and the summation order, policy_act.hpp the finishing step behind the scores: act_finish).
 //
 // A memory-bound stream.  Envs 2k and 2k + 1 share delta_k and everyone shares M, so a workgroup takes a PAIR: delta_k's [D][A] block is
 // read from HBM once and applied to both frames, M comes from L2 / Infinity Cache, and nothing is written but A scores per env.  The
@@ -28,15 +28,13 @@ struct PixArgs {
     const double *weights;       // M [D][A]
     const double *delta;         // [items][D][A] or null
     const uint8_t *images;       // [n][D]
-    const uint8_t *done_prev;    // [n] or null
-    uint8_t *frozen;             // [n]
-    void *act;                   // int32 [n] / float [n][A]
+    ActFinish fin;               // (sample is never set: fin.A repeats the kernel's template argument)
     double *score;               // [n][A] or null
     double *part;                // split: [items][chunks][envs of an item][A] chunk sums
     uint32_t *ticket;            // split: [items], zero between launches (allocated zeroed; an item's last arriver puts the zero back)
     double noise;
     int64_t D;
-    int32_t chunks, split, freeze, discrete, none_nan;
+    int32_t chunks, split;
 };
 
 template <int VEC> __device__ __forceinline__ void pix_load(const double *p, double (&out)[VEC]) {
@@ -141,21 +139,14 @@ __global__ void __launch_bounds__(kPixLanes) pixel_policy_act_k(PixArgs a) {
     if (tid < ENVS * A) fin[tid] = score;
     __syncthreads();
     if (tid >= ENVS) return;
-    // an env's one finishing thread: freeze bookkeeping, the scores, the action row (srlhip_policy_act's functions)
-    const int64_t env = e0 + tid;
+    // an env's one finishing thread: policy_act.hpp's finishing step on the env's scores.  Never sampled, so no draw; said here as
+    // constants, with A, so that the instantiation carries neither the softmax nor a loop over a run-time A (the scores stay in registers)
+    ActFinish f = a.fin;
+    f.A = A; f.sample = 0;
     double sc[kPixMaxOut];
 #pragma unroll
     for (int k = 0; k < A; k++) sc[k] = fin[tid * A + k];
-    bool frozen = false;
-    if (a.freeze) {
-        const uint8_t f = act_frozen(a.frozen[env], a.done_prev != nullptr, a.done_prev ? a.done_prev[env] : (uint8_t)0);
-        a.frozen[env] = f;
-        frozen = f != 0;
-    }
-    if (a.score)
-#pragma unroll
-        for (int k = 0; k < A; k++) a.score[env * A + k] = sc[k];
-    act_store(a.act, env, A, a.discrete != 0, a.none_nan != 0, frozen, a.discrete ? act_argmax(sc, A) : 0, sc);
+    act_finish(f, e0 + tid, sc, a.score, 0.0);
 }
 
 }  // namespace
@@ -166,7 +157,7 @@ int pixel_policy_act_launch(Handle *h, const double *weights, const double *delt
     const int64_t D = (int64_t)frame_bytes(c);
     const int items = paired ? h->n / 2 : h->n, chunks = pix_chunks(D);
     const int split = pix_split(items, chunks) && h->pix_part && h->pix_ticket ? chunks : 1;
-    PixArgs a{weights, delta, images, done_prev, frozen, act, score, h->pix_part, h->pix_ticket, noise, D, chunks, split, freeze ? 1 : 0, c.is_discrete ? 1 : 0, none_nan ? 1 : 0};
+    PixArgs a{weights, delta, images, act_finish_args(h, freeze, false, A, none_nan, done_prev, frozen, act), score, h->pix_part, h->pix_ticket, noise, D, chunks, split};
     const bool launched = dispatch_int<2, 3, 4, 6, 7>(A, [&](auto ac) {
         return dispatch_int<0, 1>(paired ? 1 : 0, [&](auto pc) {
             hipLaunchKernelGGL((pixel_policy_act_k<decltype(ac)::value, decltype(pc)::value != 0>), dim3((unsigned)(items * split)), dim3(kPixLanes), 0, h->stream, a);

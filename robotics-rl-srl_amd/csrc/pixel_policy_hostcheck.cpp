@@ -10,22 +10,14 @@
 //   pixel_policy_hostcheck shapes      one line per frame shape: D, the chunks, and for which populations a launch is split over them
 //   pixel_policy_hostcheck refusals    one line per argument case: the code and the message of the checks
 // The virtual lanes of a chunk are walked one after the other, their partials combined by pix_tree_sum — the kernel's levels in LDS.
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <vector>
-
+#include "hostcheck_io.hpp"
 #include "pixel_policy.hpp"
 #include "policy_act.hpp"
 
 using namespace srl;
-
-template <class T> static bool rd(FILE *f, std::vector<T> &v, size_t count) {
-    v.resize(count);
-    return count == 0 || fread(v.data(), sizeof(T), count, f) == count;
-}
-template <class T> static bool wr(FILE *f, const std::vector<T> &v) { return v.empty() || fwrite(v.data(), sizeof(T), v.size(), f) == v.size(); }
 
 // one env's scores: sign +1 / -1 the env's side of its direction, 0 unpaired (delta is not read)
 static void forward(const uint8_t *x, const double *M, const double *delta, double noise, int sign, int64_t D, int A, double *score) {
@@ -71,7 +63,6 @@ static int print_shapes() {
     return 0;
 }
 
-static void verdict(const char *what, const Verdict &v) { printf("%s: %d %s\n", what, v.code, v.msg ? v.msg : "accepted"); }
 static int print_refusals() {
     srlhip_pixel_policy pol;
     double dummy = 0.0;
@@ -121,12 +112,12 @@ int main(int argc, char **argv) {
     std::vector<double> score((size_t)N * A);
     std::vector<int32_t> act_i(discrete ? N : 0);
     std::vector<float> act_f(discrete ? 0 : (size_t)N * A);
+    const ActFinish fin{has_done ? done_prev.data() : nullptr, frozen.data(), discrete ? static_cast<void *>(act_i.data()) : static_cast<void *>(act_f.data()),
+                        A, freeze, discrete, 0, none_nan};
     for (int e = 0; e < N; e++) {
-        double *sd = &score[(size_t)e * A];
+        double sd[kPixMaxOut];
         forward(frames.data() + (size_t)e * D, M.data(), paired ? delta.data() + (size_t)(e / 2) * D * A : nullptr, nu[0], paired ? (e % 2 ? -1 : 1) : 0, D, A, sd);
-        bool fz = false;
-        if (freeze) { frozen[e] = act_frozen(frozen[e], has_done, done_prev[e]); fz = frozen[e] != 0; }
-        act_store(discrete ? static_cast<void *>(act_i.data()) : static_cast<void *>(act_f.data()), e, A, discrete, none_nan, fz, discrete ? act_argmax(sd, A) : 0, sd);
+        act_finish(fin, e, sd, score.data(), 0.0);
     }
     f = fopen(argv[2], "wb");
     if (!f) { perror(argv[2]); return 2; }

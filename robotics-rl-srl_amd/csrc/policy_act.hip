@@ -1,5 +1,5 @@
 // policy_act.hip — srlhip_policy_act: a policy's action for every env from an observation plane that is already on the device, as a
-// launch of its own between the encoder and the next step (include/srlhip.h has the contract, policy_act.hpp the arithmetic), and
+// launch of its own between the encoder and the next step (include/srlhip.h has the contract, policy_act.hpp the arithmetic and the finishing step, act_finish), and
 // srlhip_sample_actions: the sampled selection alone, on a score plane (sample_actions_k, at the end).
 //
 // The launch is a stream of the parameter blocks: at D = 200, H = 100 an MLP block is 82 KB per env.  The contract fixes the ORDER of
@@ -29,39 +29,18 @@ constexpr int kLinEnvs = 32, kLinRows = 8, kLinStride = kLinRows * kActMaxOut + 
 struct ActArgs {
     PolicyArgs pol;
     const float *obs;            // [n][D]
-    const uint8_t *done_prev;    // [n] or null
-    uint8_t *frozen;             // [n]
-    void *act;                   // int32 [n] / float [n][A]
+    ActFinish fin;
     const uint32_t *key;         // [2][n] the envs' Philox keys
     uint64_t *act_ctr;           // [n] action-stream block counters
     double *score;               // [n][A] or null: the float64 scores as they stood in front of the selection
-    int32_t n, D, A, discrete, sample, none_nan;
+    int32_t n, D;
 };
 
 struct __attribute__((packed, aligned(4))) F4 { float v[4]; };      // 16 bytes at float alignment: a parameter block starts anywhere
 
-// the last step of both kernels, one thread per env: freeze bookkeeping, the draw, the action row
-__device__ __forceinline__ void act_finish(const ActArgs &a, int e, const double *score) {
-    bool frozen = false;
-    if (a.pol.freeze) {
-        const uint8_t f = act_frozen(a.frozen[e], a.done_prev != nullptr, a.done_prev ? a.done_prev[e] : (uint8_t)0);
-        a.frozen[e] = f;
-        frozen = f != 0;
-    }
-    if (a.score)
-        for (int k = 0; k < a.A; k++) a.score[(int64_t)e * a.A + k] = score[k];
-    int choice = 0;
-    if (a.sample) {
-        // one block of the env's action stream per call, frozen or not: the counter moves inside the kernel, a graph replay draws afresh
-        Philox draw;
-        draw.k0 = a.key[e]; draw.k1 = a.key[a.n + e]; draw.stream = 1; draw.ctr = a.act_ctr[e];
-        const double u = draw.double01();
-        a.act_ctr[e] = draw.ctr;
-        double w[kActMaxOut];
-        act_softmax_weights(score, a.A, w);
-        choice = act_softmax_pick(w, a.A, u);
-    } else if (a.discrete) choice = act_argmax(score, a.A);
-    act_store(a.act, e, a.A, a.discrete != 0, a.none_nan != 0, frozen, choice, score);
+// the last step of both kernels, one thread per env: the draw, then policy_act.hpp's finishing step
+__device__ __forceinline__ void finish_env(const ActArgs &a, int e, const double *score) {
+    act_finish(a.fin, e, score, a.score, a.fin.sample ? act_draw(a.key, a.n, a.act_ctr, e) : 0.0);
 }
 
 // E envs per workgroup: 1 with per-env parameter blocks, 4 with one shared block.  Thread t: unit j = t mod 128 of envs (t / 128) and
@@ -76,7 +55,7 @@ __global__ void __launch_bounds__(kBlock) policy_act_mlp_k(ActArgs a) {
     __shared__ double sc[E][kActMaxOut];
     const int tid = threadIdx.x, j = tid & (kActMaxHidden - 1), slot = tid >> 7;
     const int e0 = blockIdx.x * E;
-    const int H = a.pol.hidden, D = a.D, A = a.A;
+    const int H = a.pol.hidden, D = a.D, A = a.fin.A;
     const int64_t P = (int64_t)H * D + H + (int64_t)A * H + A;
     const float *w = static_cast<const float *>(a.pol.w) + (E == 1 && a.pol.per_env ? (int64_t)e0 * P : 0);
     const float *w2 = w + (int64_t)H * D + H;      // fc_out.weight [A][H], then fc_out.bias [A]
@@ -159,7 +138,7 @@ __global__ void __launch_bounds__(kBlock) policy_act_mlp_k(ActArgs a) {
     __syncthreads();
     if (tid < E * A) sc[tid / A][tid % A] = act_row_sum16(part[tid / A][tid % A]);
     __syncthreads();
-    if (tid < E && e0 + tid < a.n) act_finish(a, e0 + tid, sc[tid]);
+    if (tid < E && e0 + tid < a.n) finish_env(a, e0 + tid, sc[tid]);
 }
 
 // thread t: output slot o = t mod 8 of env t / 8 of the workgroup
@@ -169,7 +148,7 @@ __global__ void __launch_bounds__(kBlock) policy_act_linear_k(ActArgs a) {
     __shared__ double sc[kLinEnvs][kActMaxOut];
     const int tid = threadIdx.x, o = tid & (kActMaxOut - 1), g = tid >> 3;
     const int e0 = blockIdx.x * kLinEnvs, e = e0 + g;
-    const int D = a.D, A = a.A, chunk = kLinRows * A;                 // doubles per env and tile
+    const int D = a.D, A = a.fin.A, chunk = kLinRows * A;                 // doubles per env and tile
     const int64_t count = (int64_t)D * A;
     const double *W = static_cast<const double *>(a.pol.w);
     const bool per_env = a.pol.per_env != 0, normalize = a.pol.normalize != 0;
@@ -211,10 +190,11 @@ __global__ void __launch_bounds__(kBlock) policy_act_linear_k(ActArgs a) {
     }
     if (o < A) sc[g][o] = acc;
     __syncthreads();
-    if (o == 0 && e < a.n) act_finish(a, e, sc[g]);
+    if (o == 0 && e < a.n) finish_env(a, e, sc[g]);
 }
 
-// srlhip_sample_actions: the draw of act_finish on a score plane the caller holds, one thread per env.  Everything a thread reads is its
+// srlhip_sample_actions: act_finish's draw and selection on a score plane the caller holds, one thread per env — not act_finish itself:
+// this call only READS the frozen plane, and does so without a freeze flag.  Everything a thread reads is its
 // own env's: the score row, the frozen byte, the key and the counter — the result does not depend on n or on the launch geometry.
 struct SampleArgs {
     const double *score;         // [n][A]
@@ -229,16 +209,18 @@ __global__ void __launch_bounds__(kBlock) sample_actions_k(SampleArgs a) {
     if (e >= a.n) return;
     double score[kActMaxOut], w[kActMaxOut];
     for (int k = 0; k < a.A; k++) score[k] = a.score[(int64_t)e * a.A + k];
-    Philox draw;                                       // one block per call, frozen or not: a graph replay draws afresh
-    draw.k0 = a.key[e]; draw.k1 = a.key[a.n + e]; draw.stream = 1; draw.ctr = a.act_ctr[e];
-    const double u = draw.double01();
-    a.act_ctr[e] = draw.ctr;
+    const double u = act_draw(a.key, a.n, a.act_ctr, e);      // frozen or not
     act_softmax_weights(score, a.A, w);
     const int choice = act_softmax_pick(w, a.A, u);
     a.act[e] = a.frozen && a.frozen[e] ? -1 : choice;
 }
 
 }  // namespace
+
+ActFinish act_finish_args(Handle *h, bool freeze, bool sample, int A, bool none_nan, const uint8_t *done_prev, uint8_t *frozen, void *act) {
+    if (sample) { h->snap_valid = false; h->prefetch_valid = false; }      // the action-stream counters move past what was drawn ahead
+    return ActFinish{done_prev, frozen, act, A, freeze ? 1 : 0, h->cfg.is_discrete ? 1 : 0, sample ? 1 : 0, none_nan ? 1 : 0};
+}
 
 int sample_actions_launch(Handle *h, int A, const double *score, const uint8_t *frozen, int32_t *act) {
     h->snap_valid = false; h->prefetch_valid = false;      // the action-stream counters move past what was drawn ahead
@@ -250,8 +232,7 @@ int sample_actions_launch(Handle *h, int A, const double *score, const uint8_t *
 
 int policy_act_launch(Handle *h, const PolicyArgs &pol, bool sample, int D, int A, bool none_nan, const float *obs, const uint8_t *done_prev,
                       uint8_t *frozen, void *act, double *score) {
-    if (sample) { h->snap_valid = false; h->prefetch_valid = false; }      // the action-stream counters move past what was drawn ahead
-    const ActArgs a{pol, obs, done_prev, frozen, act, h->rng.key, h->rng.act_ctr, score, h->n, D, A, h->cfg.is_discrete ? 1 : 0, sample ? 1 : 0, none_nan ? 1 : 0};
+    const ActArgs a{pol, obs, act_finish_args(h, pol.freeze != 0, sample, A, none_nan, done_prev, frozen, act), h->rng.key, h->rng.act_ctr, score, h->n, D};
     if (!pol.hidden)
         hipLaunchKernelGGL(policy_act_linear_k, dim3((h->n + kLinEnvs - 1) / kLinEnvs), dim3(kBlock), 0, h->stream, a);
     else if (pol.per_env)

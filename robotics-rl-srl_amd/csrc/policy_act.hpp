@@ -1,8 +1,10 @@
 // policy_act.hpp — the per-env arithmetic of srlhip_policy_act (contract: include/srlhip.h), host + gfx950 device code.
 //
 // One definition of every step that fixes a bit of the result — the policy's input, the two score functions with their summation
-// ORDER, the action selection — called by the kernels of policy_act.hip and by the stand-alone host program policy_hostcheck.cpp
-// (make policyhostcheck), which tests/test_policy_act_cpu.py holds to the numpy restatement tests/policy_act_ref.py bit for bit.
+// ORDER, and the finishing step behind ANY score function (act_finish: freeze bookkeeping, score plane, selection, action row; act_draw:
+// the env's action-stream block) — called by the kernels of policy_act.hip, cnn_policy.hip and pixel_policy.hip and by the stand-alone
+// host programs policy_hostcheck.cpp, cnn_policy_hostcheck.cpp and pixel_policy_hostcheck.cpp, which tests/test_policy_act_cpu.py,
+// test_cnn_policy_cpu.py and test_pixel_policy_cpu.py hold to their numpy restatements bit for bit.
 // The same steps exist inside the fused rollout kernels (mobile.hip: policy_input, row_sum16, softmax_weights, softmax_pick; the Kuka
 // tree kernels): those keep their own text — moving it would change their code objects — and tests/test_gpu_policy_act.py holds
 // both copies to the one reference, closed loop.  Build every user with -ffp-contract=off: no product may fuse with its sum.
@@ -105,6 +107,47 @@ SRL_HD void act_store(void *act, int64_t row, int A, bool discrete, bool none_na
     }
     float *out = static_cast<float *>(act) + row * A;
     for (int k = 0; k < A; k++) out[k] = frozen ? (none_nan ? __builtin_nanf("") : 0.f) : (float)score[k];
+}
+
+// one block of env e's action stream (Philox stream 1; key: the [2][n] key plane, ctr: the [n] block counters): opened at the stored
+// counter, one block taken, the counter stored back — it moves inside the kernel, so a graph replay draws afresh.  A sampled call draws
+// for every env, frozen or not; a call that does not sample never comes here.
+SRL_HD double act_draw(const uint32_t *key, int n, uint64_t *ctr, int64_t e) {
+    Philox draw;
+    draw.k0 = key[e]; draw.k1 = key[n + e]; draw.stream = 1; draw.ctr = ctr[e];
+    const double u = draw.double01();
+    ctr[e] = draw.ctr;
+    return u;
+}
+
+// What the finishing step of an action call works on besides the scores.  Passed to kernels BY VALUE inside their argument blocks.
+struct ActFinish {
+    const uint8_t *done_prev;    // [n] or null
+    uint8_t *frozen;             // [n]: read and written only with freeze
+    void *act;                   // int32 [n] / float [n][A]
+    int32_t A, freeze, discrete, sample, none_nan;
+};
+
+// The finishing step of every action call, one thread per env, in this order: the freeze bookkeeping; the scores into row e of the
+// score plane (score_out null: none), for a frozen env too; the selection — sample: the softmax weights (also into w_out where the
+// caller wants them) and the inverse CDF at u, the caller's act_draw (unused otherwise); else, discrete, the arg-max — and the action row.
+template <class S>
+SRL_HD void act_finish(const ActFinish &f, int64_t e, const double *score, S *score_out, double u, double *w_out = nullptr) {
+    bool frozen = false;
+    if (f.freeze) {
+        const uint8_t b = act_frozen(f.frozen[e], f.done_prev != nullptr, f.done_prev ? f.done_prev[e] : (uint8_t)0);
+        f.frozen[e] = b;
+        frozen = b != 0;
+    }
+    if (score_out)
+        for (int k = 0; k < f.A; k++) score_out[e * f.A + k] = (S)score[k];
+    int choice = 0;
+    if (f.sample) {
+        double wl[kActMaxOut], *w = w_out ? w_out : wl;
+        act_softmax_weights(score, f.A, w);
+        choice = act_softmax_pick(w, f.A, u);
+    } else if (f.discrete) choice = act_argmax(score, f.A);
+    act_store(f.act, e, f.A, f.discrete != 0, f.none_nan != 0, frozen, choice, score);
 }
 
 }  // namespace srl

@@ -10,20 +10,12 @@
 //           float64     u [N]: the uniform draw of every env (sample)
 //   result  float64 score [N][A], float64 w [N][A] (the softmax weights; zeros without sample), int32 [N] | float32 [N][A] the action rows,
 //           uint8 frozen [N]
-#include <stdio.h>
 #include <stdlib.h>
 
-#include <vector>
-
+#include "hostcheck_io.hpp"
 #include "policy_act.hpp"
 
 using namespace srl;
-
-template <class T> static bool rd(FILE *f, std::vector<T> &v, size_t count) {
-    v.resize(count);
-    return count == 0 || fread(v.data(), sizeof(T), count, f) == count;
-}
-template <class T> static bool wr(FILE *f, const std::vector<T> &v) { return v.empty() || fwrite(v.data(), sizeof(T), v.size(), f) == v.size(); }
 
 int main(int argc, char **argv) {
     if (argc != 3) { fprintf(stderr, "usage: policy_hostcheck <case> <result>\n"); return 2; }
@@ -49,9 +41,11 @@ int main(int argc, char **argv) {
     std::vector<float> act_f(discrete ? 0 : (size_t)N * A);
     std::vector<float> x(D);
     std::vector<double> h(H ? H : 1);
+    const ActFinish fin{has_done ? done_prev.data() : nullptr, frozen.data(), discrete ? static_cast<void *>(act_i.data()) : static_cast<void *>(act_f.data()),
+                        A, freeze, discrete, sample, none_nan};
     for (int e = 0; e < N; e++) {
         for (int d = 0; d < D; d++) x[d] = act_input(obs[(size_t)e * D + d], normalize, normalize ? mean[d] : 0.0, normalize ? sd[d] : 1.0, clip);
-        double *s = &score[(size_t)e * A];
+        double s[kActMaxOut];
         if (!H) {
             const double *W = wd.data() + (per_env ? (size_t)e * P : 0);
             for (int a = 0; a < A; a++) {
@@ -73,14 +67,7 @@ int main(int argc, char **argv) {
                 s[a] = act_row_sum16(part);
             }
         }
-        bool fz = false;
-        if (freeze) { frozen[e] = act_frozen(frozen[e], has_done, done_prev[e]); fz = frozen[e] != 0; }
-        int choice = 0;
-        if (sample) {
-            act_softmax_weights(s, A, &wout[(size_t)e * A]);
-            choice = act_softmax_pick(&wout[(size_t)e * A], A, u[e]);
-        } else if (discrete) choice = act_argmax(s, A);
-        act_store(discrete ? static_cast<void *>(act_i.data()) : static_cast<void *>(act_f.data()), e, A, discrete, none_nan, fz, choice, s);
+        act_finish(fin, e, s, score.data(), u[e], &wout[(size_t)e * A]);
     }
     f = fopen(argv[2], "wb");
     if (!f) { perror(argv[2]); return 2; }

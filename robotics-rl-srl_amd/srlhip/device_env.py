@@ -9,6 +9,7 @@ Stream discipline: the handle owns a HIP stream (srlhip_stream).  `env.torch_str
 torch.cuda.ExternalStream; code that runs under `with torch.cuda.stream(env.torch_stream):` is ordered with the
 stepper's kernels and needs no host synchronisation at all.  When the caller is on another stream, step()/reset()
 fall back to two host-side stream synchronisations per call."""
+import contextlib
 import functools
 
 import numpy as np
@@ -19,6 +20,41 @@ from .envs import ENV_CLASSES, OBS_MODES
 from .gym_compat import Box, Discrete
 
 from .vec_env import RNG_MODES, default_rng_mode
+
+
+def _apply_env_kwargs(cfg, kw, int_keys):
+    """env_kwargs -> config, for the device-resident envs: the integer keys the caller lists and max_distance, each only where
+    `kw` has it (absent: the env's default stays)"""
+    for name in int_keys:
+        if name in kw:
+            setattr(cfg, name, int(kw[name]))
+    if "max_distance" in kw:
+        cfg.max_distance = float(kw["max_distance"])
+
+
+@contextlib.contextmanager
+def _rollout_frame(env):
+    """The frame of an enqueue-only rollout on `env` (its h, device, torch_stream): the body runs with the env's stream current,
+    so the planes it allocates live (and are later freed) on the stream that fills them.  A caller on that stream is not
+    synchronised at all; one on another stream is, before the body and after it."""
+    ordered = torch.cuda.current_stream(env.device).cuda_stream == env.torch_stream.cuda_stream
+    if not ordered:
+        torch.cuda.current_stream(env.device).synchronize()
+    with torch.cuda.stream(env.torch_stream):
+        yield
+    if not ordered:
+        env.h.sync()
+
+
+def _rollout_planes(env, T, obs_dim=None):
+    """the new [T][N]... planes a rollout returns: "reward", "done", "actions" and, with obs_dim, "obs" in front of them"""
+    n, dev = env.num_envs, env.device
+    out = {} if obs_dim is None else {"obs": torch.empty((T, n, obs_dim), dtype=torch.float32, device=dev)}
+    out["reward"] = torch.empty((T, n), dtype=torch.float32, device=dev)
+    out["done"] = torch.empty((T, n), dtype=torch.uint8, device=dev)
+    out["actions"] = (torch.empty((T, n), dtype=torch.int32, device=dev) if env.cfg.is_discrete
+                      else torch.empty((T, n, env.h.action_dim), dtype=torch.float32, device=dev))
+    return out
 
 
 def first_done_masks(done):
@@ -35,11 +71,7 @@ class DeviceVecEnv(object):
         rng_mode = rng_mode or default_rng_mode("device")
         cfg = _lib.default_config(ENV_CLASSES[env_id].ENV_KIND)
         cfg.num_envs, cfg.device_id, cfg.first_env_id, cfg.seed0 = int(num_envs), device_id, first_env_id, int(seed)
-        for name in ("is_discrete", "random_target", "shape_reward", "force_down", "action_repeat", "action_joints"):
-            if name in kw:
-                setattr(cfg, name, int(kw[name]))
-        if "max_distance" in kw:
-            cfg.max_distance = float(kw["max_distance"])
+        _apply_env_kwargs(cfg, kw, ("is_discrete", "random_target", "shape_reward", "force_down", "action_repeat", "action_joints"))
         srl_model = kw.get("srl_model", "ground_truth")
         if srl_model not in OBS_MODES or srl_model == "raw_pixels":
             raise NotImplementedError("DeviceVecEnv serves the state observations; use PixelStateVecEnv for raw_pixels")
@@ -88,26 +120,16 @@ class DeviceVecEnv(object):
     def _rollout_policy(self, call, T, params, dtype, shape, per_env, freeze_after_done, obs_mean, obs_std, clip_obs):
         """`call` (a bound Handle.rollout_policy / rollout_mlp_policy, less its leading T and parameter pointer) on tensors: `params`
         of `dtype` and `shape`, new output planes allocated on the env's stream, enqueue-only when the caller is on that stream"""
-        n, dev = self.num_envs, self.device
         assert params.is_cuda and params.dtype == dtype and params.is_contiguous(), (params.dtype, params.device)
         assert tuple(params.shape) == shape, (tuple(params.shape), shape)
         assert (obs_mean is None) == (obs_std is None), "obs_mean and obs_std come together"
         for x in (obs_mean, obs_std):
             assert x is None or (x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() and tuple(x.shape) == (self.h.obs_dim,))
-        ordered = self._on_env_stream()
-        if not ordered:
-            torch.cuda.current_stream(dev).synchronize()
-        with torch.cuda.stream(self.torch_stream):         # the planes are allocated (and later freed) on the stream that fills them
-            out = {"obs": torch.empty((T, n, self.h.obs_dim), dtype=torch.float32, device=dev),
-                   "reward": torch.empty((T, n), dtype=torch.float32, device=dev),
-                   "done": torch.empty((T, n), dtype=torch.uint8, device=dev),
-                   "actions": torch.empty((T, n), dtype=torch.int32, device=dev) if self.cfg.is_discrete
-                   else torch.empty((T, n, self.h.action_dim), dtype=torch.float32, device=dev)}
-        call(T, params.data_ptr(), per_env=per_env, freeze_after_done=freeze_after_done,
-             obs_mean=None if obs_mean is None else obs_mean.data_ptr(), obs_std=None if obs_std is None else obs_std.data_ptr(),
-             clip_obs=clip_obs, out=tuple(out[k].data_ptr() for k in ("obs", "reward", "done", "actions")))
-        if not ordered:
-            self.h.sync()
+        with _rollout_frame(self):
+            out = _rollout_planes(self, T, self.h.obs_dim)
+            call(T, params.data_ptr(), per_env=per_env, freeze_after_done=freeze_after_done,
+                 obs_mean=None if obs_mean is None else obs_mean.data_ptr(), obs_std=None if obs_std is None else obs_std.data_ptr(),
+                 clip_obs=clip_obs, out=tuple(out[k].data_ptr() for k in ("obs", "reward", "done", "actions")))
         return out
 
     def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0, sample=False):

@@ -8,31 +8,31 @@ rasteriser -> encoder) enqueued on the handle's stream, DeviceVecEnv's signature
 DeviceVecNormalize and the ARS / CMA-ES learners sit on this env as they do on DeviceVecEnv.  A sampled LINEAR policy (ARS's default
 form; rollout_policy(sample=True), RawPixelVecEnv.rollout_pixel_policy(sample=True)) takes one launch more per step: the policy call leaves
 its scores, srlhip_sample_actions draws from them with each env's own action stream — still no host read in the loop."""
+import functools
+
 import numpy as np
 import torch
 
 from . import _lib
+from .device_env import _apply_env_kwargs, _rollout_frame, _rollout_planes
 from .envs import ENV_CLASSES
 from .gym_compat import Box, Discrete
 
 
-class PixelStateVecEnv(object):
-    def __init__(self, env_id, num_envs, encoder, seed=0, img_shape=(64, 64), device_id=0, first_env_id=0,
-                 rng_mode=_lib.RNG_PHILOX, env_kwargs=None, use_graph=False):
+class _PixelHandleEnv(object):
+    """A raw_pixels, device-pointer handle with what every env on it holds: the frame, reward, done and action tensors the stepper
+    and the rasteriser write, the action space, the handle's stream as a torch stream — and the one loop behind every policy rollout."""
+
+    def __init__(self, env_id, num_envs, seed, img_shape, device_id, first_env_id, rng_mode, env_kwargs):
         kw = dict(env_kwargs or {})
         cfg = _lib.default_config(ENV_CLASSES[env_id].ENV_KIND)
         cfg.num_envs, cfg.device_id, cfg.first_env_id, cfg.seed0 = num_envs, device_id, first_env_id, seed
         cfg.random_target, cfg.multi_view = int(kw.get("random_target", False)), int(bool(kw.get("multi_view", False)) or bool(kw.get("fpv", False)))
         cfg.obs_mode, cfg.img_h, cfg.img_w = _lib.OBS_RAW_PIXELS, img_shape[0], img_shape[1]
         cfg.rng_mode, cfg.auto_reset, cfg.io_device = rng_mode, 1, 1
-        for name in ("is_discrete", "shape_reward", "force_down", "action_repeat"):      # as DeviceVecEnv; absent: the env's defaults
-            if name in kw:
-                setattr(cfg, name, int(kw[name]))
-        if "max_distance" in kw:
-            cfg.max_distance = float(kw["max_distance"])
+        _apply_env_kwargs(cfg, kw, ("is_discrete", "shape_reward", "force_down", "action_repeat"))
         self.h = _lib.Handle(cfg)
-        self.cfg, self.env_id = cfg, env_id
-        self.encoder, self.num_envs = encoder, num_envs
+        self.cfg, self.env_id, self.num_envs = cfg, env_id, num_envs
         self.device = torch.device("cuda", device_id)
         ch = 6 if cfg.multi_view else 3
         self.images = torch.zeros((num_envs, img_shape[0], img_shape[1], ch), dtype=torch.uint8, device=self.device)
@@ -44,6 +44,42 @@ class PixelStateVecEnv(object):
         else:
             self.actions = torch.zeros((num_envs, self.h.action_dim), dtype=torch.float32, device=self.device)
             self.action_space = Box(low=-1, high=1, shape=(self.h.action_dim,), dtype=np.float32)
+        self._stream_ptr = self.h.stream()
+        self._stream = self.torch_stream = torch.cuda.ExternalStream(self._stream_ptr, device=self.device)
+
+    def _rollout_loop(self, T, act, freeze_after_done, draw=False, obs_dim=None, after_step=None):
+        """T x (act [-> srlhip_sample_actions] -> step + rasteriser [-> after_step]) on the handle's stream: no host read, and no
+        synchronisation when the caller is on that stream.  Every kernel writes straight into row t of the new [T][N]... planes:
+        `act(act_t, done_prev=, frozen=, score_out=)` (raw device pointers) launches the policy's action kernel, which reads row t - 1
+        of the done plane (none at t = 0) and writes row t of the action plane; the stepper reads that row, writes row t of reward /
+        done and redraws the frame buffer in place.  draw: the action kernel leaves its float64 scores and srlhip_sample_actions draws
+        from them with each env's own action stream (one launch more per step); it sees the frozen plane only with
+        freeze_after_done, the action kernel always.  obs_dim: the result has an "obs" plane, and after_step(obs_t) fills its row t."""
+        with _rollout_frame(self):
+            out = _rollout_planes(self, T, obs_dim)
+            frozen = torch.zeros((self.num_envs,), dtype=torch.uint8, device=self.device)
+            scores = torch.empty((self.num_envs, self.h.num_actions), dtype=torch.float64, device=self.device) if draw else None
+            images = self.images.data_ptr()
+            for t in range(T):
+                act_t = out["actions"][t].data_ptr()
+                act(act_t, done_prev=out["done"][t - 1].data_ptr() if t else None, frozen=frozen.data_ptr(),
+                    score_out=scores.data_ptr() if draw else None)
+                if draw:
+                    self.h.sample_actions(scores.data_ptr(), act_t, frozen=frozen.data_ptr() if freeze_after_done else None)
+                self.h.step(act_t, out=(images, out["reward"][t].data_ptr(), out["done"][t].data_ptr()))
+                if after_step is not None:
+                    after_step(out["obs"][t])
+        return out
+
+    def episode_stats(self):
+        return self.h.episode_stats()
+
+
+class PixelStateVecEnv(_PixelHandleEnv):
+    def __init__(self, env_id, num_envs, encoder, seed=0, img_shape=(64, 64), device_id=0, first_env_id=0,
+                 rng_mode=_lib.RNG_PHILOX, env_kwargs=None, use_graph=False):
+        super(PixelStateVecEnv, self).__init__(env_id, num_envs, seed, img_shape, device_id, first_env_id, rng_mode, env_kwargs)
+        self.encoder = encoder
         self.state_dim = int(encoder.state_dim)
         self.observation_space = Box(low=-np.inf, high=np.inf, shape=(self.state_dim,), dtype=np.float32)
         self.states = torch.zeros((num_envs, encoder.state_dim), dtype=torch.float32, device=self.device)
@@ -52,8 +88,6 @@ class PixelStateVecEnv(object):
         # source.  Off by default: at 4096 envs the step is GPU-bound and the host already runs ahead of it (697 us eager
         # vs 702 us replayed, profiles/pixel_step_microbench.py); it pays when the host thread is the bottleneck.
         self.use_graph, self._graphs, self._warm = bool(use_graph), {}, {}
-        self._stream_ptr = self.h.stream()
-        self._stream = self.torch_stream = torch.cuda.ExternalStream(self._stream_ptr, device=self.device)
 
     def _encode(self):
         if self.encoder.hip is not None:
@@ -107,49 +141,34 @@ class PixelStateVecEnv(object):
 
     # ---- policy rollouts on the learned states: T x (srlhip_policy_act -> step + rasteriser -> encoder), enqueue-only ----------------
     def _rollout(self, T, policy, sample, per_env, freeze_after_done, obs_mean, obs_std, clip_obs):
-        """`policy`: the keyword arguments of Handle.policy_act that name the policy (raw device pointers).  The loop starts from the
-        states the env holds (after reset(), step() or an earlier rollout) and every kernel writes straight into row t of the new
-        [T][N]... planes: the action kernel reads row t - 1 of the state and done planes and writes row t of the action plane, the
-        stepper reads that row and writes row t of reward / done and the frame buffer, the encoder writes row t of the state plane.
-        All of it on the handle's stream; no host read, and no synchronisation when the caller is on that stream."""
+        """`policy`: the keyword arguments of Handle.policy_act that name the policy (raw device pointers).  _rollout_loop from the
+        states the env holds (after reset(), step() or an earlier rollout): the action kernel reads row t - 1 of the state plane,
+        the encoder writes row t."""
         assert self._current is not None, "reset() the env first"
-        n, dev, D = self.num_envs, self.device, self.state_dim
+        D = self.state_dim
         assert (obs_mean is None) == (obs_std is None), "obs_mean and obs_std come together"
         for x in (obs_mean, obs_std):
             assert x is None or (x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() and tuple(x.shape) == (D,))
-        ordered = torch.cuda.current_stream(dev).cuda_stream == self.torch_stream.cuda_stream
-        if not ordered:
-            torch.cuda.current_stream(dev).synchronize()
-        fused = self.encoder.hip is not None
-        with torch.cuda.stream(self.torch_stream):         # the planes are allocated (and later freed) on the stream that fills them
-            out = {"obs": torch.empty((T, n, D), dtype=torch.float32, device=dev),
-                   "reward": torch.empty((T, n), dtype=torch.float32, device=dev),
-                   "done": torch.empty((T, n), dtype=torch.uint8, device=dev),
-                   "actions": torch.empty((T,) + tuple(self.actions.shape), dtype=self.actions.dtype, device=dev)}
-            frozen = torch.zeros((n,), dtype=torch.uint8, device=dev)
-            prev = self._current if self._current.dtype == torch.float32 else self._current.to(torch.float32)
-            # a sampled LINEAR policy: srlhip_policy_act leaves its scores, srlhip_sample_actions draws from them (one launch more per step)
-            plane = sample and "weights" in policy
-            scores = torch.empty((n, self.h.num_actions), dtype=torch.float64, device=dev) if plane else None
-            kw = dict(policy, per_env=per_env, freeze_after_done=freeze_after_done, clip_obs=clip_obs, sample=sample and not plane,
-                      obs_mean=None if obs_mean is None else obs_mean.data_ptr(), obs_std=None if obs_std is None else obs_std.data_ptr(),
-                      frozen=frozen.data_ptr())
-            images = self.images.data_ptr()
-            for t in range(T):
-                act_t, obs_t = out["actions"][t], out["obs"][t]
-                self.h.policy_act(prev.data_ptr(), D, act_t.data_ptr(), done_prev=out["done"][t - 1].data_ptr() if t else None,
-                                  score_out=scores.data_ptr() if plane else None, **kw)
-                if plane:
-                    self.h.sample_actions(scores.data_ptr(), act_t.data_ptr(), frozen=frozen.data_ptr() if freeze_after_done else None)
-                self.h.step(act_t.data_ptr(), out=(images, out["reward"][t].data_ptr(), out["done"][t].data_ptr()))
-                if fused:
-                    self.encoder.getStates(self.images, stream=self._stream_ptr, out=obs_t)
-                else:                                      # no HIP backend (backend="torch", uncovered shapes): the torch forward, ordered on this stream
-                    obs_t.copy_(self.encoder.getStates(self.images))
-                prev = obs_t
-            self._current = prev
-        if not ordered:
-            self.h.sync()
+        # a sampled LINEAR policy: srlhip_policy_act leaves its scores, srlhip_sample_actions draws from them
+        draw = sample and "weights" in policy
+        kw = dict(policy, per_env=per_env, freeze_after_done=freeze_after_done, clip_obs=clip_obs, sample=sample and not draw,
+                  obs_mean=None if obs_mean is None else obs_mean.data_ptr(), obs_std=None if obs_std is None else obs_std.data_ptr())
+        state = [self._current]
+
+        def act(act_t, **planes):
+            if state[0].dtype != torch.float32:            # (the first step of a torch-backend encoder: converted on the env's stream, as the planes are)
+                state[0] = state[0].to(torch.float32)
+            self.h.policy_act(state[0].data_ptr(), D, act_t, **planes, **kw)
+
+        def encode(obs_t):
+            if self.encoder.hip is not None:
+                self.encoder.getStates(self.images, stream=self._stream_ptr, out=obs_t)
+            else:                                          # no HIP backend (backend="torch", uncovered shapes): the torch forward, ordered on this stream
+                obs_t.copy_(self.encoder.getStates(self.images))
+            state[0] = obs_t
+
+        out = self._rollout_loop(T, act, freeze_after_done, draw=draw, obs_dim=D, after_step=encode)
+        self._current = state[0]
         return out
 
     def rollout_policy(self, T, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0, sample=False):
@@ -178,9 +197,6 @@ class PixelStateVecEnv(object):
         return self._rollout(T, {"params": params.data_ptr(), "hidden": int(hidden)}, bool(sample), per_env, freeze_after_done,
                              obs_mean, obs_std, clip_obs)
 
-    def episode_stats(self):
-        return self.h.episode_stats()
-
     def close(self):
         for g in self._graphs.values():
             self.h.graph_destroy(g)
@@ -188,41 +204,16 @@ class PixelStateVecEnv(object):
         self.h.close()
 
 
-class RawPixelVecEnv(object):
+class RawPixelVecEnv(_PixelHandleEnv):
     """The raw_pixels form without an encoder: the observation IS the uint8 frame the rasteriser writes, and the policy is the
     reference's CNN-from-pixels (CMA-ES: CNNPolicyPytorch), one network per env, run by srlhip_cnn_policy_act on the frame where it
     lies.  Constructor arguments as PixelStateVecEnv's less the encoder; reset() / step(actions) return the image tensor
     ([N][H][W][C] uint8, overwritten by the next call), rewards and dones on the device."""
 
     def __init__(self, env_id, num_envs, seed=0, img_shape=(64, 64), device_id=0, first_env_id=0, rng_mode=_lib.RNG_PHILOX, env_kwargs=None):
-        kw = dict(env_kwargs or {})
-        cfg = _lib.default_config(ENV_CLASSES[env_id].ENV_KIND)
-        cfg.num_envs, cfg.device_id, cfg.first_env_id, cfg.seed0 = num_envs, device_id, first_env_id, seed
-        cfg.random_target, cfg.multi_view = int(kw.get("random_target", False)), int(bool(kw.get("multi_view", False)) or bool(kw.get("fpv", False)))
-        cfg.obs_mode, cfg.img_h, cfg.img_w = _lib.OBS_RAW_PIXELS, img_shape[0], img_shape[1]
-        cfg.rng_mode, cfg.auto_reset, cfg.io_device = rng_mode, 1, 1
-        for name in ("is_discrete", "shape_reward", "force_down", "action_repeat"):      # as DeviceVecEnv; absent: the env's defaults
-            if name in kw:
-                setattr(cfg, name, int(kw[name]))
-        if "max_distance" in kw:
-            cfg.max_distance = float(kw["max_distance"])
-        self.h = _lib.Handle(cfg)
-        self.cfg, self.env_id, self.num_envs = cfg, env_id, num_envs
-        self.device = torch.device("cuda", device_id)
-        ch = 6 if cfg.multi_view else 3
-        self.images = torch.zeros((num_envs, img_shape[0], img_shape[1], ch), dtype=torch.uint8, device=self.device)
-        self.rewards = torch.zeros((num_envs,), dtype=torch.float32, device=self.device)
-        self.dones = torch.zeros((num_envs,), dtype=torch.uint8, device=self.device)
-        if cfg.is_discrete:
-            self.actions = torch.zeros((num_envs,), dtype=torch.int32, device=self.device)
-            self.action_space = Discrete(self.h.num_actions)
-        else:
-            self.actions = torch.zeros((num_envs, self.h.action_dim), dtype=torch.float32, device=self.device)
-            self.action_space = Box(low=-1, high=1, shape=(self.h.action_dim,), dtype=np.float32)
-        self.observation_space = Box(low=0, high=255, shape=(img_shape[0], img_shape[1], ch), dtype=np.uint8)
+        super(RawPixelVecEnv, self).__init__(env_id, num_envs, seed, img_shape, device_id, first_env_id, rng_mode, env_kwargs)
+        self.observation_space = Box(low=0, high=255, shape=tuple(self.images.shape[1:]), dtype=np.uint8)
         self._ready = False               # the frame buffer holds the env's current frame (after reset / step / a rollout)
-        self._stream_ptr = self.h.stream()
-        self._stream = self.torch_stream = torch.cuda.ExternalStream(self._stream_ptr, device=self.device)
 
     def cnn_param_count(self):
         return self.h.cnn_param_count()
@@ -258,31 +249,16 @@ class RawPixelVecEnv(object):
         return act
 
     def rollout_cnn_policy(self, T, params, per_env=True, freeze_after_done=False, sample=False):
-        """T x (srlhip_cnn_policy_act, step + rasteriser) on the handle's stream, enqueue-only as PixelStateVecEnv._rollout is: the
+        """T x (srlhip_cnn_policy_act, step + rasteriser) on the handle's stream, enqueue-only (_rollout_loop): the
         action kernel reads the frame buffer and row t - 1 of the done plane and writes row t of the action plane, the stepper reads
         that row, writes row t of reward / done and redraws the frames in place.  `params`: float32 CUDA tensor [N][P] (or [P]),
         P = cnn_param_count() — a CMA-ES population as it is.  Returns {"reward", "done", "actions"}: new [T][N]... tensors (no
         observation plane: T frames per env is gigabytes)."""
         assert self._ready, "reset() the env first"
         self._check_params(params, per_env)
-        n, dev = self.num_envs, self.device
-        ordered = torch.cuda.current_stream(dev).cuda_stream == self.torch_stream.cuda_stream
-        if not ordered:
-            torch.cuda.current_stream(dev).synchronize()
-        with torch.cuda.stream(self.torch_stream):         # the planes are allocated (and later freed) on the stream that fills them
-            out = {"reward": torch.empty((T, n), dtype=torch.float32, device=dev),
-                   "done": torch.empty((T, n), dtype=torch.uint8, device=dev),
-                   "actions": torch.empty((T,) + tuple(self.actions.shape), dtype=self.actions.dtype, device=dev)}
-            frozen = torch.zeros((n,), dtype=torch.uint8, device=dev)
-            images = self.images.data_ptr()
-            for t in range(T):
-                act_t = out["actions"][t]
-                self.h.cnn_policy_act(images, act_t.data_ptr(), params.data_ptr(), per_env=per_env, freeze_after_done=freeze_after_done,
-                                      done_prev=out["done"][t - 1].data_ptr() if t else None, frozen=frozen.data_ptr(), sample=sample)
-                self.h.step(act_t.data_ptr(), out=(images, out["reward"][t].data_ptr(), out["done"][t].data_ptr()))
-        if not ordered:
-            self.h.sync()
-        return out
+        act = functools.partial(self.h.cnn_policy_act, self.images.data_ptr(), params=params.data_ptr(), per_env=per_env,
+                                freeze_after_done=freeze_after_done, sample=sample)
+        return self._rollout_loop(T, act, freeze_after_done)
 
     def _check_pixel_policy(self, weights, delta):
         D, A = int(np.prod(self.images.shape[1:])), self.h.num_actions if self.cfg.is_discrete else self.h.action_dim
@@ -314,31 +290,9 @@ class RawPixelVecEnv(object):
         softmax of the scores with each env's own action stream; no host read in the loop."""
         assert self._ready, "reset() the env first"
         self._check_pixel_policy(weights, delta)
-        n, dev = self.num_envs, self.device
-        ordered = torch.cuda.current_stream(dev).cuda_stream == self.torch_stream.cuda_stream
-        if not ordered:
-            torch.cuda.current_stream(dev).synchronize()
-        with torch.cuda.stream(self.torch_stream):         # the planes are allocated (and later freed) on the stream that fills them
-            out = {"reward": torch.empty((T, n), dtype=torch.float32, device=dev),
-                   "done": torch.empty((T, n), dtype=torch.uint8, device=dev),
-                   "actions": torch.empty((T,) + tuple(self.actions.shape), dtype=self.actions.dtype, device=dev)}
-            frozen = torch.zeros((n,), dtype=torch.uint8, device=dev)
-            scores = torch.empty((n, self.h.num_actions), dtype=torch.float64, device=dev) if sample else None
-            images = self.images.data_ptr()
-            for t in range(T):
-                act_t = out["actions"][t]
-                self.h.pixel_policy_act(images, act_t.data_ptr(), weights.data_ptr(), delta=None if delta is None else delta.data_ptr(), noise=noise,
-                                        freeze_after_done=freeze_after_done, done_prev=out["done"][t - 1].data_ptr() if t else None,
-                                        frozen=frozen.data_ptr(), score_out=scores.data_ptr() if sample else None)
-                if sample:
-                    self.h.sample_actions(scores.data_ptr(), act_t.data_ptr(), frozen=frozen.data_ptr() if freeze_after_done else None)
-                self.h.step(act_t.data_ptr(), out=(images, out["reward"][t].data_ptr(), out["done"][t].data_ptr()))
-        if not ordered:
-            self.h.sync()
-        return out
-
-    def episode_stats(self):
-        return self.h.episode_stats()
+        act = functools.partial(self.h.pixel_policy_act, self.images.data_ptr(), weights=weights.data_ptr(),
+                                delta=None if delta is None else delta.data_ptr(), noise=noise, freeze_after_done=freeze_after_done)
+        return self._rollout_loop(T, act, freeze_after_done, draw=bool(sample))
 
     def close(self):
         self.h.close()

@@ -103,8 +103,24 @@ def test_freeze_and_constant_frame(programs, tmp_path):
     env = make_env(45, 51, 3, n, A)
     try:
         r = act(env, frames, params, freeze=True, done_prev=done_prev, frozen=frozen)
+        off = act(env, frames, params, freeze=False, done_prev=done_prev, frozen=frozen)
+        sampled = [act(env, frames, params, sample=True, freeze=True, frozen=r["frozen"]) for _ in range(2)]
+        after = act(env, frames, params, sample=True)
     finally:
         env.close()
+    # without freeze_after_done both planes are ignored: the frozen plane stays as it was, every env acts
+    assert np.array_equal(off["frozen"], frozen) and np.array_equal(off["act"], off["score"].astype(np.float64).argmax(axis=1))
+    # sampled: a frozen env draws too — after two calls with frozen envs every env's third call uses block 2 of its stream
+    u = msr.draws(SEED + np.arange(n), 0, 3)
+    for k, smp in enumerate(sampled + [after]):
+        assert np.array_equal(smp["score"], r["score"])
+        for e in range(n):
+            if k < 2 and r["frozen"][e]:
+                assert smp["act"][e] == -1
+            else:
+                assert ref.sample_accepts(smp["score"][e], u[k][e], int(smp["act"][e]), 0.0), (k, e)
+    stale = [ref.sample_accepts(after["score"][e], u[0][e], int(after["act"][e]), 0.0) for e in range(n) if r["frozen"][e]]
+    assert not all(stale), "the check must tell block 2 from block 0 for a frozen env"
     assert r["frozen"].tolist() == [0, 1, 1, 1, 0] and np.array_equal(r["act"], host["act"])
     assert np.array_equal(r["score"].view(np.uint32), host["score"].view(np.uint32))
     live = r["frozen"] == 0

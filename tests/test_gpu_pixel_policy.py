@@ -120,6 +120,7 @@ def test_freeze_done_prev_and_the_frozen_plane(A, discrete):
     try:
         r = act(env, case["frames"], case["M"], case["delta"], case["noise"], freeze=True, done_prev=done_prev, frozen=frozen)
         plain = act(env, case["frames"], case["M"], case["delta"], case["noise"], freeze=True, frozen=np.zeros(10, np.uint8))
+        off = act(env, case["frames"], case["M"], case["delta"], case["noise"], freeze=False, done_prev=done_prev, frozen=frozen)
     finally:
         env.close()
     want = ref.scores(case["frames"], case["M"], case["delta"], case["noise"])
@@ -134,6 +135,8 @@ def test_freeze_done_prev_and_the_frozen_plane(A, discrete):
     else:
         assert (r["act"][gone] == 0).all()
     assert not plain["frozen"].any() and ref.same_bits(plain["act"], ref.select(want, discrete))
+    # without freeze_after_done both planes are ignored: the frozen plane stays as it was, every env acts
+    assert np.array_equal(off["frozen"], frozen) and ref.same_bits(off["score"], want) and ref.same_bits(off["act"], ref.select(want, discrete))
 
 
 def test_shards_agree_bit_for_bit():
