@@ -326,6 +326,39 @@ int srlhip_rollout_mlp_policy_sampled(srlhip_handle h, int32_t T, const srlhip_m
 int srlhip_rollout_policy_sampled(srlhip_handle h, int32_t T, const srlhip_linear_policy *pol,
                                   void *obs_TN, float *reward_TN, uint8_t *done_TN, void *act_out_TN);
 
+/* The four fused policy rollouts with the REDUCED result a learner keeps instead of the [T][num_envs] planes: per env the return up
+ * to its first done, the number of live steps and the first two moments of the live observations (what ARS, CMA-ES and
+ * DeviceVecNormalize otherwise form from the planes with a chain of reductions).  No plane is allocated or written.
+ * Exactly one of `linear` / `mlp` is non-null (as in srlhip_policy_act); sample != 0 selects the _sampled form of that policy.  The
+ * pointers of `out` follow cfg.io_device like every other pointer.
+ * THE CALL IS THE PLANE CALL WITH OTHER OUTPUTS: stepping, action selection, RNG consumption, action-stream counters, auto-resets,
+ * freeze_after_done and episode statistics are those of the corresponding plane call (srlhip_rollout_policy, srlhip_rollout_mlp_policy
+ * or their _sampled forms) with the same arguments; the env state after the call equals the plane call's bit for bit.  In terms of
+ * the rows reward[t][e], done[t][e] and o[t][e][d] (the raw float32 observation) that plane call would have written:
+ *   first(e)       the first row t of THIS call at which env e reports done (bit 0 of the done byte); T if there is none
+ *   ret[e]         sum over t < first(e) of (double)reward[t][e], added in ascending t from +0.0; the reporting step is not counted
+ *   length[e]      min(first(e) + 1, T)
+ *   obs_sum[e][d]  sum over t < length(e) of (double)o[t][e][d], ascending t from +0.0
+ *   obs_sqsum[e][d] the same sum of (double)o * (double)o: each product is rounded, then added (never fused with the sum) — a
+ *                  sequential float64 loop over the planes reproduces every output bit for bit (tests/rollout_summary_ref.py)
+ * PER-CALL SCOPE: the result depends on T and on nothing earlier — an episode that was running when the call began counts from the
+ * call's first row, and the result of two calls of T/2 steps is NOT the result of one call of T steps (first(e) restarts with every
+ * call).  It does not compose across chunked calls.
+ * Refusals: everything the corresponding plane call refuses, worded alike under the prefix "rollout_policy_summary:" (the
+ * discrete-only rule of `sample` and Kuka2Button's missing joint-space arm included).  SRLHIP_EINVAL: both or neither policy, a null
+ * `out` or out->ret, only one of the two moment pointers, a wrong struct_size (of `out` or of the policy), reserved != 0, T <= 0, a
+ * pending srlhip_step_async, the plane calls' pointer checks and, on host-pointer handles, their value checks.  A resident persistent
+ * kernel parks.  One launch on the handle's stream (Kuka: and the header kernel); on device-pointer handles no allocation and no
+ * synchronisation: capturable under srlhip_graph_begin. */
+typedef struct srlhip_rollout_summary {
+    int32_t struct_size, reserved;      /* sizeof(srlhip_rollout_summary), 0 */
+    double  *ret;                       /* [num_envs]            required */
+    int32_t *length;                    /* [num_envs]            or NULL  */
+    double  *obs_sum, *obs_sqsum;       /* [num_envs][obs_dim]   both or neither */
+} srlhip_rollout_summary;
+int srlhip_rollout_policy_summary(srlhip_handle h, int32_t T, const srlhip_linear_policy *linear, const srlhip_mlp_policy *mlp,
+                                  int32_t sample, const srlhip_rollout_summary *out);
+
 /* The policy's action as a call of its own: ONE step of the three fused rollouts' action selection, from an observation plane the
  * caller already holds on the device — the state vectors an SRL encoder made of the rendered frames (image -> encoder -> state ->
  * policy), where no policy can sit inside the physics kernel.  A T-step rollout on learned states is T x (srlhip_policy_act,

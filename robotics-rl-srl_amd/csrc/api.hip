@@ -529,7 +529,8 @@ int policy_call_begin(Handle *h, const char *name, int32_t T) {
     return 0;
 }
 
-int rollout_policy(Handle *h, int32_t T, const PolicyCall &pc, const PolicyView &pv, const RolloutPlanes &host) {
+// summary: null, or the reduced outputs of srlhip_rollout_policy_summary (host's planes are all null then)
+int rollout_policy(Handle *h, int32_t T, const PolicyCall &pc, const PolicyView &pv, const RolloutPlanes &host, const srlhip_rollout_summary *summary = nullptr) {
     const srlhip_config &c = h->cfg;
     Verdict v = check_policy_pointers(pv);
     if (!v.code) v = pc.sample && !pv.mlp ? check_rollout_policy_sampled_config(c) : check_rollout_policy_config(c, pc.sample);
@@ -551,8 +552,29 @@ int rollout_policy(Handle *h, int32_t T, const PolicyCall &pc, const PolicyView 
         if (pa.normalize) { pa.mean = blk; pa.std = blk + D; }
         if ((rc = stage_rollout_planes(h, T, dev))) return rc;
     }
-    if ((rc = env_ops(h).rollout_policy(h, T, pa, pc.sample, pc.kuka, dev.obs, dev.rew, dev.done, dev.act))) return rc;
-    return c.io_device ? 0 : fetch_rollout_planes(h, T, host, dev);      // (`packed` must outlive its copy: the synchronisation is in there)
+    if (!summary) {
+        if ((rc = env_ops(h).rollout_policy(h, T, pa, pc.sample, pc.kuka, dev.obs, dev.rew, dev.done, dev.act, nullptr))) return rc;
+        return c.io_device ? 0 : fetch_rollout_planes(h, T, host, dev);      // (`packed` must outlive its copy: the synchronisation is in there)
+    }
+    // the reduced outputs.  Host-pointer handles: one staged block — ret [n], obs_sum [n][D], obs_sqsum [n][D] doubles, then length [n]
+    const size_t n = (size_t)h->n;
+    SummaryOut so = {summary->ret, summary->length, summary->obs_sum, summary->obs_sqsum};
+    if (!c.io_device) {
+        if ((rc = ensure(h, h->st[ST_OBS], 8 * n * (1 + 2 * D) + 4 * n))) return rc;
+        double *blk = static_cast<double *>(h->st[ST_OBS].p);
+        so = {blk, summary->length ? reinterpret_cast<int32_t *>(blk + n * (1 + 2 * D)) : nullptr, summary->obs_sum ? blk + n : nullptr,
+              summary->obs_sum ? blk + n * (1 + D) : nullptr};
+    }
+    if ((rc = env_ops(h).rollout_policy(h, T, pa, pc.sample, pc.kuka, nullptr, nullptr, nullptr, nullptr, &so))) return rc;
+    if (c.io_device) return 0;
+    SRL_HIP_CHECK(h, hipMemcpyAsync(summary->ret, so.ret, 8 * n, hipMemcpyDeviceToHost, h->stream));
+    if (so.length) SRL_HIP_CHECK(h, hipMemcpyAsync(summary->length, so.length, 4 * n, hipMemcpyDeviceToHost, h->stream));
+    if (so.obs_sum) {
+        SRL_HIP_CHECK(h, hipMemcpyAsync(summary->obs_sum, so.obs_sum, 8 * n * D, hipMemcpyDeviceToHost, h->stream));
+        SRL_HIP_CHECK(h, hipMemcpyAsync(summary->obs_sqsum, so.obs_sqsum, 8 * n * D, hipMemcpyDeviceToHost, h->stream));
+    }
+    SRL_HIP_CHECK(h, hipStreamSynchronize(h->stream));      // (`packed` must outlive its copy)
+    return 0;
 }
 
 // the four entry points: one body
@@ -717,6 +739,25 @@ int srlhip_rollout_mlp_policy(srlhip_handle hh, int32_t T, const srlhip_mlp_poli
 int srlhip_rollout_mlp_policy_sampled(srlhip_handle hh, int32_t T, const srlhip_mlp_policy *pol, void *obs_TN, float *reward_TN,
                                       uint8_t *done_TN, void *act_out_TN) {
     return rollout_policy_entry(hh, {"rollout_mlp_policy_sampled", kuka_rollout_mlp_policy_sampled, true}, T, pol, {obs_TN, reward_TN, done_TN, act_out_TN});
+}
+
+// srlhip_rollout_policy_summary: the plane call the arguments name (its PolicyCall: the Kuka launcher, `sample`) behind the plane calls'
+// checks in their order, the new arguments' checks (api_rules.hpp: check_rollout_summary) right behind the ABI checks
+int srlhip_rollout_policy_summary(srlhip_handle hh, int32_t T, const srlhip_linear_policy *linear, const srlhip_mlp_policy *mlp, int32_t sample,
+                                  const srlhip_rollout_summary *out) {
+    if (!hh) return SRLHIP_EINVAL;
+    Handle *h = reinterpret_cast<Handle *>(hh);
+    const char *name = kSummaryName;
+    Verdict v = check_policy_act_which(linear != nullptr, mlp != nullptr);
+    if (!v.code) v = mlp ? check_policy_abi(mlp) : check_policy_abi(linear);
+    if (!v.code) v = check_rollout_summary(out);
+    if (v.code) return refuse(h, name, v);
+    int rc = policy_call_begin(h, name, T);
+    if (rc) return rc;
+    const PolicyView pv = mlp ? policy_view(*mlp) : policy_view(*linear);
+    if ((v = check_policy_shape(pv)).code) return refuse(h, name, v);
+    const KukaPolicyLaunch kuka = mlp ? (sample ? kuka_rollout_mlp_policy_sampled : kuka_rollout_mlp_policy) : (sample ? kuka_rollout_policy_sampled : kuka_rollout_policy);
+    return rollout_policy(h, T, {name, kuka, sample != 0}, pv, RolloutPlanes{}, out);
 }
 
 // srlhip_policy_act: the struct checks and messages of the fused rollouts in their order, its own argument checks between them, none

@@ -282,6 +282,18 @@ inline Verdict check_policy_act_planes(const srlhip_config &c, const PolicyView 
     return kAccepted;
 }
 
+// srlhip_rollout_policy_summary's own argument checks (tails; the entry point prefixes "rollout_policy_summary: "), in its order around
+// the shared ones: which policy — check_policy_act_which — before the ABI checks, the output struct right behind them; the config
+// rules are the plane calls' (check_rollout_policy_config / check_rollout_policy_sampled_config by `sample` and the policy kind)
+inline Verdict check_rollout_summary(const srlhip_rollout_summary *out) {
+    if (!out) return {SRLHIP_EINVAL, "null out"};
+    if (out->struct_size != (int32_t)sizeof(srlhip_rollout_summary)) return {SRLHIP_EINVAL, "srlhip_rollout_summary.struct_size mismatch (ABI)"};
+    if (out->reserved != 0) return {SRLHIP_EINVAL, "reserved must be 0"};
+    if (!out->ret) return {SRLHIP_EINVAL, "null ret"};
+    if ((out->obs_sum != nullptr) != (out->obs_sqsum != nullptr)) return {SRLHIP_EINVAL, "obs_sum and obs_sqsum come together (both or neither)"};
+    return kAccepted;
+}
+
 // ---- the linear policy's sampled forms ----------------------------------------------------------------------------------------------------
 // srlhip_rollout_policy_sampled: what srlhip_rollout_policy refuses, in its order, then the continuous action modes (tails; the entry
 // point prefixes "rollout_policy_sampled: ").  The struct and pointer checks in front of it are the shared ones above.

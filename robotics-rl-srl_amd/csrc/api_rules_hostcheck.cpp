@@ -15,6 +15,7 @@
 //   episodes n | block bytes, byte offset of the lengths
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <cmath>
 #include <limits>
@@ -260,6 +261,20 @@ static void policies() {
     }
 }
 
+// srlhip_rollout_policy_summary's own argument checks (`api_rules_hostcheck summary`: a table of its own, after the ones above were pinned
+// line by line); the config rules it shares with the plane calls are the policy-config rows above
+static void summary() {
+    double ret[1], sum[1], sq[1];
+    int32_t len[1];
+    printf("summary null | "); verdict(check_rollout_summary(nullptr));
+    for (int32_t size : {(int32_t)sizeof(srlhip_rollout_summary), (int32_t)sizeof(srlhip_rollout_summary) - 8, 0}) for (int32_t reserved : {0, 1})
+    for (int r = 0; r < 2; r++) for (int l = 0; l < 2; l++) for (int a = 0; a < 2; a++) for (int b = 0; b < 2; b++) {
+        const srlhip_rollout_summary o = {size, reserved, r ? ret : nullptr, l ? len : nullptr, a ? sum : nullptr, b ? sq : nullptr};
+        printf("summary %d %d %d %d %d %d | ", size, reserved, r, l, a, b); verdict(check_rollout_summary(&o));
+    }
+    printf("summary-size | %zu\n", sizeof(srlhip_rollout_summary));
+}
+
 static void scratch() {
     for (int side : {8, 9, 224}) for (int mv = 0; mv < 2; mv++) for (size_t n : {(size_t)1, (size_t)5}) for (int64_t blob_cap : {(int64_t)0, (int64_t)1000, (int64_t)65536}) {
         srlhip_config c;
@@ -277,7 +292,8 @@ static void scratch() {
 }
 
 int main(int argc, char **argv) {
-    if (argc != 2) { fprintf(stderr, "usage: api_rules_hostcheck TABLES\n"); return 2; }
+    if (argc != 2) { fprintf(stderr, "usage: api_rules_hostcheck TABLES | summary\n"); return 2; }
+    if (!strcmp(argv[1], "summary")) { summary(); return fflush(stdout) == 0 && !ferror(stdout) ? 0 : 2; }
     defaults();
     configs();
     layouts();

@@ -72,13 +72,22 @@ static_assert(sizeof(PolicyArgs) == 48 && offsetof(PolicyArgs, w) == 0 && offset
                   offsetof(PolicyArgs, clip) == 24 && offsetof(PolicyArgs, per_env) == 32 && offsetof(PolicyArgs, freeze) == 36 &&
                   offsetof(PolicyArgs, normalize) == 40 && offsetof(PolicyArgs, hidden) == 44,
               "PolicyArgs is a kernel argument: its layout is what the policy kernels were compiled against");
+// srlhip_rollout_policy_summary: the reduced outputs of a fused policy rollout (device pointers; include/srlhip.h has the contract).  The
+// launchers below take a pointer to one: null is the plane call, non-null the summary call — no plane is written then, and a refusal
+// carries the summary entry's name.  length, and obs_sum with obs_sqsum, may be null.
+struct SummaryOut {
+    double *ret;
+    int32_t *length;
+    double *obs_sum, *obs_sqsum;
+};
+constexpr const char *kSummaryName = "rollout_policy_summary";
 // kuka_tree_policy.hip / kuka_tree_mlp.hip / kuka_tree_mlp_sample.hip / kuka_tree_policy_sample.hip (full model); d_hdr: the handle's 16-double policy header
-int kuka_rollout_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
-int kuka_rollout_mlp_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
-int kuka_rollout_mlp_policy_sampled(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
-int kuka_rollout_policy_sampled(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);      // kuka_tree_policy_sample.hip
-using KukaPolicyLaunch = int (*)(Handle *, int, const PolicyArgs &, double *, float *, float *, uint8_t *, void *);
-int kuka_policy_header(Handle *h, double *d_hdr, const PolicyArgs &pol);      // kuka_tree_policy.hip: the one header kernel's launch
+int kuka_rollout_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out, const SummaryOut *sum);
+int kuka_rollout_mlp_policy(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out, const SummaryOut *sum);
+int kuka_rollout_mlp_policy_sampled(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out, const SummaryOut *sum);
+int kuka_rollout_policy_sampled(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out, const SummaryOut *sum);      // kuka_tree_policy_sample.hip
+using KukaPolicyLaunch = int (*)(Handle *, int, const PolicyArgs &, double *, float *, float *, uint8_t *, void *, const SummaryOut *);
+int kuka_policy_header(Handle *h, double *d_hdr, const PolicyArgs &pol, const SummaryOut *sum);      // kuka_tree_policy.hip: the one header kernel's launch
 
 // What api.hip asks of an env family, one table per family (mobile.hip, kuka.hip); every pointer is a device pointer.
 struct EnvOps {
@@ -88,7 +97,9 @@ struct EnvOps {
     int (*rollout)(Handle *h, int T, const void *d_actions, void *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
     // the fused policy rollouts.  MobileRobot: the linear or the MLP kernel family by pol.hidden, with `sample` the discrete action
     // drawn from the softmax of its scores; Kuka: `kuka`, the launcher api.hip's PolicyCall names, on the handle's policy header
-    int (*rollout_policy)(Handle *h, int T, const PolicyArgs &pol, bool sample, KukaPolicyLaunch kuka, void *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out);
+    // sum: null, or the outputs of srlhip_rollout_policy_summary (the four planes are null then)
+    int (*rollout_policy)(Handle *h, int T, const PolicyArgs &pol, bool sample, KukaPolicyLaunch kuka, void *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out,
+                          const SummaryOut *sum);
     int (*field)(Handle *h, int field, void **dptr, size_t *elem, int *count);
     // persistent stepping: the real workgroups of the resident kernel (0: this handle has no persistent form); capacity: how many
     // workgroups of it the device holds at once; eighths: which of the 8 `done` words it writes; grid: the workgroups it launches

@@ -377,8 +377,9 @@ static int kuka_step(Handle *h, const void *d_actions, const double *d_noise, vo
 }
 
 // the policy launcher api.hip's PolicyCall selected, on the handle's policy header
-static int kuka_rollout_policy_with(Handle *h, int T, const PolicyArgs &pol, bool, KukaPolicyLaunch launch, void *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
-    return launch(h, T, pol, h->policy_hdr, static_cast<float *>(d_obs), d_rew, d_done, d_act_out);
+static int kuka_rollout_policy_with(Handle *h, int T, const PolicyArgs &pol, bool, KukaPolicyLaunch launch, void *d_obs, float *d_rew, uint8_t *d_done, void *d_act_out,
+                                    const SummaryOut *sum) {
+    return launch(h, T, pol, h->policy_hdr, static_cast<float *>(d_obs), d_rew, d_done, d_act_out, sum);
 }
 
 // persistent stepping: the full model's resident kernel; its grid is the contiguous one (step_signal.hpp), padding workgroups included

@@ -210,6 +210,12 @@ __device__ __forceinline__ int row_softmax_draw(const S &sc, int l, const Philox
 // the exit store leaves that stream's counter T further on.
 // POLICY = 4 (srlhip_rollout_policy_sampled; kuka_tree_policy_sample.hip): POLICY = 1 up to the six broadcast scores, discrete actions
 // only (JOINTS = false), then POLICY = 3's draw (row_softmax_draw) and its counter store.
+// POLICY != 0, srlhip_rollout_policy_summary (contract: include/srlhip.h): words 11 .. 14 of the header are the call's four output pointers,
+// all null in a plane call — tested at run time, so that the summary form adds no instantiation to kernels that compile for minutes
+// and the argument block stays the one the POLICY = 0 kernels share.  The sums are spread over the env's 16-lane row, two float64
+// accumulators per lane: lane d < 3 holds dimension d's obs_sum and obs_sqsum (every lane can form the observation: the env scalars
+// are replicated over the row), lane 3 the return; the row-uniform length and the latched done flag sit in every lane.  Each sum
+// takes its terms in ascending t and every product is rounded before it is added (contract(off): this unit lets products fuse).
 template <int MODE, bool JOINTS, bool GIVEN, int NB, int RB = 0, int SPEC = 0, int PERSIST = 0, int POLICY = 0>
 __global__ void __launch_bounds__(kGroupBlock)
 kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int T, const void *actions, const double *noise,
@@ -310,6 +316,17 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
 #pragma unroll
         for (int d = 0; d < 3; d++) { pol_w[d] = L.l < A ? w[d * A + col] : 0.0; pol_mean[d] = hdr[4 + d]; pol_std[d] = hdr[7 + d]; }
         pol_freeze = hdr[1] != 0.0; pol_norm = hdr[2] != 0.0; pol_clip = hdr[3];
+    }
+    double *sum_ret = nullptr, *sum_obs = nullptr, *sum_sq = nullptr;
+    int32_t *sum_len = nullptr;
+    double sum_a = 0.0, sum_b = 0.0;                 // this lane's two accumulators (see above)
+    int32_t sum_n = 0;
+    bool sum_seen = false;
+    (void)sum_ret; (void)sum_obs; (void)sum_sq; (void)sum_len; (void)sum_a; (void)sum_b; (void)sum_n; (void)sum_seen;
+    if constexpr (POLICY) {
+        const uint64_t *words = reinterpret_cast<const uint64_t *>(noise);
+        sum_ret = reinterpret_cast<double *>(words[11]); sum_len = reinterpret_cast<int32_t *>(words[12]);
+        sum_obs = reinterpret_cast<double *>(words[13]); sum_sq = reinterpret_cast<double *>(words[14]);
     }
     // Every load of the prologue retires HERE.  Otherwise the compiler's wait for them sits at their first use INSIDE the loop, as
     // `s_waitcnt vmcnt(0)` — and gfx9 counts stores on the same counter, so from the second step on that wait drains the previous
@@ -590,6 +607,19 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
             }
 #endif
         } else {
+            if constexpr (POLICY) {
+                if (sum_ret && !sum_seen && L.l < 4) {   // a live row of this call: none before it reported done; lanes 4 .. 15 hold no sum
+#pragma clang fp contract(off)
+                    // the row's observation as observe() writes it (ground truth: the host refuses the other modes), after the auto-reset
+                    const float own = L.l == 0 ? (float)(v.grip[0] - v.bpos[0]) : L.l == 1 ? (float)(v.grip[1] - v.bpos[1]) : (float)(v.grip[2] - v.bpos[2]);
+                    const double x = L.l < 3 ? (double)own : done ? 0.0 : (double)(float)reward;      // lane 3: the reporting step's reward is not counted
+                    const double xx = x * x;
+                    sum_a = sum_a + x;
+                    sum_b = sum_b + xx;
+                    sum_n += 1;
+                    sum_seen = done;                     // (done is uniform over the row: lanes 0 .. 3 latch together)
+                }
+            }
             if (lead) {
                 if (obs_p) observe(v, cfg, obs_p, 1);
                 if (rew_p) *rew_p = (float)reward;
@@ -649,6 +679,13 @@ kuka_tree_rollout_k(KukaParams p, KukaState s, RngState rs, EpisodeStats st, int
         st.ep_return[e_out] = ep_ret; st.ep_length[e_out] = ep_len;
         if (n_fin != n_fin0) { st.last_return[e_out] = last_ret; st.last_length[e_out] = last_len; }
         st.n_finished[e_out] = n_fin; st.last_reward[e_out] = last_reward;
+    }
+    if constexpr (POLICY) {
+        if (sum_ret && valid) {
+            if (L.l < 3 && sum_obs) { sum_obs[(int64_t)e_out * 3 + L.l] = sum_a; sum_sq[(int64_t)e_out * 3 + L.l] = sum_b; }
+            if (L.l == 3) sum_ret[e_out] = sum_a;
+            if (L.l == 0 && sum_len) sum_len[e_out] = sum_n;
+        }
     }
 }
 
@@ -750,7 +787,8 @@ int tree_reset_launch(Handle *h, const KukaParams &p, Const<MODE>, Const<JOINTS>
 // The guard restates what the entry points have refused by name before they come here (api.hip: rollout_policy): through the ABI it
 // never fires, so where a caller's own refusal stands relative to it cannot be observed.
 template <int POLICY>
-int kuka_tree_policy_launch(Handle *h, const char *name, int T, const PolicyArgs &pol, double *d_hdr, float *obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
+int kuka_tree_policy_launch(Handle *h, const char *name, int T, const PolicyArgs &pol, double *d_hdr, float *obs, float *d_rew, uint8_t *d_done, void *d_act_out,
+                            const SummaryOut *sum) {
     constexpr bool kSampled = POLICY == 3 || POLICY == 4;
     const srlhip_config &c = h->cfg;
     const auto refuse = [&] { return h->fail(SRLHIP_ENOTSUP, std::string(name) + ": no policy instantiation for this Kuka configuration"); };
@@ -758,7 +796,7 @@ int kuka_tree_policy_launch(Handle *h, const char *name, int T, const PolicyArgs
         (kSampled && !c.is_discrete) || !tree_device_rng(c))
         return refuse();
     const KukaParams p = params_of(h);
-    int rc = kuka_policy_header(h, d_hdr, pol);
+    int rc = kuka_policy_header(h, d_hdr, pol, sum);
     if (rc) return rc;
     const bool two = c.env_kind == SRLHIP_ENV_KUKA_2BUTTON;
     const TreeIo io = {T, pol.w, d_hdr, obs, d_rew, d_done, d_act_out};

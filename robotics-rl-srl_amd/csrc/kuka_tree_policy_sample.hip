@@ -6,8 +6,8 @@
 namespace srl {
 using namespace kuka;
 
-int kuka_rollout_policy_sampled(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *obs, float *d_rew, uint8_t *d_done, void *d_act_out) {
-    return kuka_tree_policy_launch<4>(h, "rollout_policy_sampled", T, pol, d_hdr, obs, d_rew, d_done, d_act_out);
+int kuka_rollout_policy_sampled(Handle *h, int T, const PolicyArgs &pol, double *d_hdr, float *obs, float *d_rew, uint8_t *d_done, void *d_act_out, const SummaryOut *sum) {
+    return kuka_tree_policy_launch<4>(h, sum ? kSummaryName : "rollout_policy_sampled", T, pol, d_hdr, obs, d_rew, d_done, d_act_out, sum);
 }
 
 }  // namespace srl

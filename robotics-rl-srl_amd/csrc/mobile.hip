@@ -444,6 +444,44 @@ __device__ __forceinline__ void policy_action(const double (&score)[A], bool fro
     }
 }
 
+// srlhip_rollout_policy_summary (contract: include/srlhip.h): what a learner keeps of a fused policy rollout, formed where each step's
+// outputs are — the return up to the env's first done of the call, the live-step count and the first two moments of the live
+// observations.  One env's whole call runs in one lane of either policy kernel (the MLP kernel's lead lane), so the sums live in that
+// lane and take their terms in ascending t.  Every product is rounded before it is added (this unit is built with -ffp-contract=off;
+// the pragma says so here too): a sequential float64 loop over the planes reproduces the bits.
+template <int D>
+struct SummaryLane {
+    double ret = 0.0, s[D], q[D];
+    int32_t len = 0;
+    bool seen = false;                                   // latched: a row of this call reported done
+    __device__ __forceinline__ SummaryLane() {
+#pragma unroll
+        for (int d = 0; d < D; d++) { s[d] = 0.0; q[d] = 0.0; }
+    }
+    // row t as the plane call would have written it: o after the step (and its auto-reset), the float32 reward, done
+    __device__ __forceinline__ void add(const float *o, double reward, bool done) {
+#pragma clang fp contract(off)
+        if (seen) return;
+        if (!done) ret = ret + (double)(float)reward;   // the reporting step is not counted
+#pragma unroll
+        for (int d = 0; d < D; d++) {
+            const double x = (double)o[d], xx = x * x;
+            s[d] = s[d] + x;
+            q[d] = q[d] + xx;
+        }
+        len += 1;
+        seen = done;
+    }
+    __device__ __forceinline__ void store(const SummaryOut &out, int e) const {
+        out.ret[e] = ret;
+        if (out.length) out.length[e] = len;
+        if (out.obs_sum) {
+#pragma unroll
+            for (int d = 0; d < D; d++) { out.obs_sum[(int64_t)e * D + d] = s[d]; out.obs_sqsum[(int64_t)e * D + d] = q[d]; }
+        }
+    }
+};
+
 // srlhip_rollout_policy: the third action source.  The action of every step is a linear map of the env's own current observation
 // (the ARS policy: one env per perturbed policy), so the recurrence cannot be cut into segments: the sequential form, one lane per
 // env.  Weights, mean and std sit in registers before the loop and nothing is loaded inside it — the streamed stores are never
@@ -452,10 +490,11 @@ __device__ __forceinline__ void policy_action(const double (&score)[A], bool fro
 // SAMPLE = true: srlhip_rollout_policy_sampled — the discrete action is drawn from the softmax of the A scores (contract:
 // include/srlhip.h) with policy_act.hpp's selection, the text srlhip_sample_actions runs on a score plane: the lane forms its A weights
 // itself (A calls of the device library's float64 exp) and draws u from the env's action stream, one block per step.
-template <int MODE, int KIND, int DISC, bool SAMPLE = false>
+// SUMMARY = true: srlhip_rollout_policy_summary — the same steps, no plane written, `sum` stored once after the last step.
+template <int MODE, int KIND, int DISC, bool SAMPLE = false, bool SUMMARY = false>
 __global__ void __launch_bounds__(kBlock)
 mobile_rollout_policy_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, int T, PolicyArgs pol,
-                        float *__restrict__ obs, float *__restrict__ rew, uint8_t *__restrict__ done_out, void *__restrict__ act_out) {
+                        float *__restrict__ obs, float *__restrict__ rew, uint8_t *__restrict__ done_out, void *__restrict__ act_out, SummaryOut sum) {
     static_assert(!SAMPLE || DISC, "only discrete actions are sampled");
     constexpr int D = KIND == SRLHIP_ENV_MOBILE_1D ? 1 : 2;
     constexpr int A = DISC ? (KIND == SRLHIP_ENV_MOBILE_1D ? 2 : 4) : 2;
@@ -481,6 +520,8 @@ mobile_rollout_policy_k(MobileParams p, MobileState s, RngState rs, EpisodeStats
     Philox draw = {};                                   // SAMPLE: the env's action stream (stream 1), at the counter the call found
     if constexpr (SAMPLE) { draw.k0 = rs.key[e]; draw.k1 = rs.key[p.n + e]; draw.stream = 1; draw.ctr = rs.act_ctr[e]; }
     bool frozen = false;
+    SummaryLane<D> sl;
+    (void)sl;
     for (int t = 0; t < T; t++) {
         const int64_t row = (int64_t)t * p.n + e;
         float x[D];
@@ -507,12 +548,14 @@ mobile_rollout_policy_k(MobileParams p, MobileState s, RngState rs, EpisodeStats
             if (pol.freeze) frozen = true;            // from the NEXT step on
         });
         observe(p, m, o[0], o[1]);
-        store_step<true>(p, row, o[0], o[1], reward, done, obs, rew, done_out);
+        if constexpr (SUMMARY) sl.add(o, reward, done);
+        else store_step<true>(p, row, o[0], o[1], reward, done, obs, rew, done_out);
     }
     store_env(s, e, m);
     rng_store<MODE>(rng, rs, e);
     if constexpr (SAMPLE) rs.act_ctr[e] = draw.ctr;   // c0 + T, whatever happened in between
     ep.store(st, e);
+    if constexpr (SUMMARY) sl.store(sum, e);
 }
 
 // srlhip_rollout_mlp_policy: the action of every step is a one-hidden-layer ReLU MLP of the env's own current observation (the CMA-ES
@@ -575,10 +618,11 @@ __device__ __forceinline__ int softmax_pick(const double (&w)[A], double u) {
 }
 
 // SAMPLE = false: srlhip_rollout_mlp_policy (the strict argmax / the continuous row); true: srlhip_rollout_mlp_policy_sampled
-template <int MODE, int KIND, int DISC, bool SAMPLE = false>
+// SUMMARY = true: srlhip_rollout_policy_summary — the sums sit in the lead lane, which alone steps the env (SummaryLane)
+template <int MODE, int KIND, int DISC, bool SAMPLE = false, bool SUMMARY = false>
 __global__ void __launch_bounds__(kBlock)
 mobile_rollout_mlp_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st, int T, PolicyArgs pol,
-                     float *__restrict__ obs, float *__restrict__ rew, uint8_t *__restrict__ done_out, void *__restrict__ act_out) {
+                     float *__restrict__ obs, float *__restrict__ rew, uint8_t *__restrict__ done_out, void *__restrict__ act_out, SummaryOut sum) {
     static_assert(!SAMPLE || DISC, "only discrete actions are sampled");
     constexpr int D = KIND == SRLHIP_ENV_MOBILE_1D ? 1 : 2;
     constexpr int A = DISC ? (KIND == SRLHIP_ENV_MOBILE_1D ? 2 : 4) : 2;
@@ -618,6 +662,8 @@ mobile_rollout_mlp_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st
         if constexpr (SAMPLE) { draw.k0 = rs.key[e]; draw.k1 = rs.key[p.n + e]; draw.stream = 1; draw.ctr = rs.act_ctr[e]; }
     }
     bool frozen = false;
+    SummaryLane<D> sl;
+    (void)sl;
     for (int t = 0; t < T; t++) {
         double score[A];
 #pragma unroll
@@ -656,7 +702,8 @@ mobile_rollout_mlp_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st
                 if (pol.freeze) frozen = true;            // from the NEXT step on
             });
             observe(p, m, o[0], o[1]);
-            store_step<true>(p, row, o[0], o[1], reward, done, obs, rew, done_out);
+            if constexpr (SUMMARY) sl.add(o, reward, done);
+            else store_step<true>(p, row, o[0], o[1], reward, done, obs, rew, done_out);
         }
     }
     if (!lead) return;
@@ -664,6 +711,7 @@ mobile_rollout_mlp_k(MobileParams p, MobileState s, RngState rs, EpisodeStats st
     rng_store<MODE>(rng, rs, e);
     if constexpr (SAMPLE) rs.act_ctr[e] = draw.ctr;   // c0 + T, whatever happened in between
     ep.store(st, e);
+    if constexpr (SUMMARY) sl.store(sum, e);
 }
 
 // Persistent stepping (srlhip_set_persistent; the protocol is step_signal.hpp's): ONE launch stays resident with every env's state in
@@ -1139,40 +1187,47 @@ static int mobile_rollout(Handle *h, int T, const void *d_actions, void *d_obs_p
 
 // srlhip_rollout_policy (pol.hidden == 0: one lane per env) / srlhip_rollout_mlp_policy (16 lanes per env) and, with `sample`, their
 // sampled forms srlhip_rollout_policy_sampled / srlhip_rollout_mlp_policy_sampled
-static int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, bool sample, KukaPolicyLaunch, void *d_obs_plane, float *d_rew, uint8_t *d_done, void *d_act_out) {
+static int mobile_rollout_policy(Handle *h, int T, const PolicyArgs &pol, bool sample, KukaPolicyLaunch, void *d_obs_plane, float *d_rew, uint8_t *d_done, void *d_act_out,
+                                 const SummaryOut *sum) {
     float *d_obs = static_cast<float *>(d_obs_plane);
     const MobileParams p = params_of(h);
+    const std::string name = sum ? kSummaryName : sample ? (pol.hidden ? "rollout_mlp_policy_sampled" : "rollout_policy_sampled") : pol.hidden ? "rollout_mlp_policy" : "rollout_policy";
     if ((h->cfg.rng_mode != SRLHIP_RNG_PHILOX && h->cfg.rng_mode != SRLHIP_RNG_MT19937) || !p.auto_reset)
-        return h->fail(SRLHIP_ENOTSUP, std::string(sample ? (pol.hidden ? "rollout_mlp_policy_sampled" : "rollout_policy_sampled") : pol.hidden ? "rollout_mlp_policy" : "rollout_policy") + ": needs auto_reset and a device RNG mode (PHILOX or MT19937)");
+        return h->fail(SRLHIP_ENOTSUP, name + ": needs auto_reset and a device RNG mode (PHILOX or MT19937)");
     if (sample && !p.is_discrete)
-        return h->fail(SRLHIP_ENOTSUP, std::string(pol.hidden ? "rollout_mlp_policy_sampled" : "rollout_policy_sampled") + ": only discrete actions are sampled");
+        return h->fail(SRLHIP_ENOTSUP, name + ": only discrete actions are sampled");
     h->snap_valid = false;                      // the live state moves, the episode-parallel rollout's snapshot set does not
     if (sample) h->prefetch_valid = false;      // ... and the action-stream counters move past what the synthetic agent drew ahead
     dim3 grid(((int64_t)h->n * (pol.hidden ? kMlpLanes : 1) + kBlock - 1) / kBlock), block(kBlock);
-    dispatch_device_rng(h->cfg.rng_mode, [&](auto mode) {
-        dispatch_env(p, [&](auto kind, auto disc) {
-            constexpr int MODE = decltype(mode)::value, KIND = decltype(kind)::value, DISC = decltype(disc)::value;
-            if constexpr (policy_combination(KIND, DISC)) {
-                if constexpr (DISC == 1) {
-                    if (sample) {
-                        if (pol.hidden)
-                            hipLaunchKernelGGL((mobile_rollout_mlp_k<MODE, KIND, 1, true>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T, pol,
-                                               d_obs, d_rew, d_done, d_act_out);
-                        else
-                            hipLaunchKernelGGL((mobile_rollout_policy_k<MODE, KIND, 1, true>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T,
-                                               pol, d_obs, d_rew, d_done, d_act_out);
-                        return;
+    const SummaryOut so = sum ? *sum : SummaryOut{};
+    const auto launch = [&](auto summary) {
+        constexpr bool SUMMARY = decltype(summary)::value != 0;
+        dispatch_device_rng(h->cfg.rng_mode, [&](auto mode) {
+            dispatch_env(p, [&](auto kind, auto disc) {
+                constexpr int MODE = decltype(mode)::value, KIND = decltype(kind)::value, DISC = decltype(disc)::value;
+                if constexpr (policy_combination(KIND, DISC)) {
+                    if constexpr (DISC == 1) {
+                        if (sample) {
+                            if (pol.hidden)
+                                hipLaunchKernelGGL((mobile_rollout_mlp_k<MODE, KIND, 1, true, SUMMARY>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T, pol,
+                                                   d_obs, d_rew, d_done, d_act_out, so);
+                            else
+                                hipLaunchKernelGGL((mobile_rollout_policy_k<MODE, KIND, 1, true, SUMMARY>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T,
+                                                   pol, d_obs, d_rew, d_done, d_act_out, so);
+                            return;
+                        }
                     }
+                    if (pol.hidden)
+                        hipLaunchKernelGGL((mobile_rollout_mlp_k<MODE, KIND, DISC, false, SUMMARY>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T, pol,
+                                           d_obs, d_rew, d_done, d_act_out, so);
+                    else
+                        hipLaunchKernelGGL((mobile_rollout_policy_k<MODE, KIND, DISC, false, SUMMARY>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T,
+                                           pol, d_obs, d_rew, d_done, d_act_out, so);
                 }
-                if (pol.hidden)
-                    hipLaunchKernelGGL((mobile_rollout_mlp_k<MODE, KIND, DISC>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T, pol,
-                                       d_obs, d_rew, d_done, d_act_out);
-                else
-                    hipLaunchKernelGGL((mobile_rollout_policy_k<MODE, KIND, DISC>), grid, block, 0, h->stream, p, h->mobile, h->rng, h->stats, T,
-                                       pol, d_obs, d_rew, d_done, d_act_out);
-            }
+            });
         });
-    });
+    };
+    if (sum) launch(Const<1>{}); else launch(Const<0>{});
     SRL_HIP_CHECK(h, hipGetLastError());
     return 0;
 }

@@ -25,6 +25,13 @@ draws from the global np.random: no per-env stream could reproduce it either.)
 
 A learned SRL model (--srl-model autoencoder, robotic_priors, ...: state_representation/registry.py, SRLType.SRL) runs on both paths:
 makeEnv then builds a PixelStateVecEnv (stepper, rasteriser, encoder on one stream) and the observation is the encoder's state vector.
+--fused-returns (off by default; needs --fused-rollout on the env's own ground-truth observations): the launch returns each
+direction's return and live-step count itself (srlhip_rollout_policy_summary) instead of the [T][N] planes the returns were then
+reduced from — the same steps, the same returns bit for bit, no planes allocated.  With v2's normalisation the statistics are updated
+from the launch's sums of the live observations (sum / n, sqsum / n - mean^2) where the planes path takes the two-pass variance: equal
+up to float64 rounding.  Refused by check_returns_arguments (CMA-ES's too) where no fused kernel stands behind the rollout: learned SRL
+models, --pixel-policy, --cnn-policy.
+
 With --fused-rollout an evaluation is T x (srlhip_policy_act, step + rasteriser, encoder) enqueued by env.rollout_policy — the same
 action selection as a kernel of its own, no host read in the loop.
 
@@ -92,6 +99,9 @@ class ARSModel(object):
         # per-step path: same distribution, other bits.  Documented in the module docstring and kept out of the generated help:
         # tests/test_mlp_sample_cpu.py pins this parser's help text to the one without it.
         parser.add_argument('--fused-sampling', action='store_true', default=False, help=argparse.SUPPRESS)
+        parser.add_argument('--fused-returns', action='store_true', default=False,
+                            help='with --fused-rollout on ground-truth observations: the launch returns each direction\'s return and live steps '
+                                 'itself instead of the reward / done planes (same returns; not with a learned SRL model or --pixel-policy)')
         parser.add_argument('--pixel-policy', action='store_true', default=False,
                             help='with --srl-model raw_pixels: the linear policy on the flattened uint8 frame, run on the device from the '
                                  'rendered frames (srlhip_pixel_policy_act; --num-stack 1)')
@@ -121,10 +131,27 @@ class ARSModel(object):
             raise ValueError("--fused-rollout: {} has no fused policy rollout".format(args.env))
 
     @staticmethod
+    def check_returns_arguments(args):
+        """--fused-returns against the rest of the arguments (check_fused_arguments' sibling; CMAESModel's too): it needs
+        --fused-rollout and a rollout that IS one kernel — with a learned SRL model, --pixel-policy or --cnn-policy the rollout is a
+        sequence of launches per step and there is nothing to return the sums from.  Raises ValueError before any env is built."""
+        if not getattr(args, "fused_returns", False):
+            return
+        if not getattr(args, "fused_rollout", False):
+            raise ValueError("--fused-returns needs --fused-rollout")
+        if getattr(args, "pixel_policy", False) or getattr(args, "cnn_policy", False):
+            raise ValueError("--fused-returns: --pixel-policy / --cnn-policy rollouts are per-step launch sequences, not one fused kernel")
+        if getattr(args, "srl_model", "ground_truth") != "ground_truth":
+            raise ValueError("--fused-returns needs --srl-model ground_truth: a rollout on a learned SRL model is a per-step launch "
+                             "sequence, not one fused kernel")
+
+    @staticmethod
     def check_arguments(args):
-        """What train() checks: --fused-sampling against the rest of the arguments (CMAESModel's rules and wording), then
-        check_fused_arguments, whose "--deterministic or --continuous-actions" requirement --fused-sampling meets; raises ValueError
-        before any env is built.  A namespace without fused_sampling: check_fused_arguments alone."""
+        """What train() checks: --fused-returns first (check_returns_arguments), then --fused-sampling against the rest of the
+        arguments (CMAESModel's rules and wording), then check_fused_arguments, whose "--deterministic or --continuous-actions"
+        requirement --fused-sampling meets; raises ValueError before any env is built.  A namespace without fused_sampling:
+        check_returns_arguments and check_fused_arguments alone."""
+        ARSModel.check_returns_arguments(args)
         if not getattr(args, "fused_sampling", False):
             return ARSModel.check_fused_arguments(args)
         if not getattr(args, "fused_rollout", False):
@@ -195,6 +222,9 @@ class ARSModel(object):
             return ret.view(P, 2), int(live_rows)
         sign = torch.tensor([1.0, -1.0], dtype=M.dtype, device=M.device).view(1, 2, 1, 1)
         W = (M.unsqueeze(0).unsqueeze(0) + self.exploration_noise * sign * delta.unsqueeze(1)).reshape(2 * P, D, A).contiguous()
+        if getattr(self, "fused_returns", False):          # --fused-returns: the launch reduces; moments only where a wrapper wants them
+            out = env.rollout_policy_summary(T, W, per_env=True, freeze_after_done=True, moments=False, **kw)
+            return out["ret"].view(P, 2), int(out["length"].max())
         planes = env.rollout_policy(T, W, per_env=True, freeze_after_done=True, **kw)
         ret, live_rows = self.returns_from_planes(planes["reward"], planes["done"])
         return ret.view(P, 2), int(live_rows)
@@ -302,6 +332,7 @@ class ARSModel(object):
         self.step_size, self.exploration_noise = args.step_size, args.exploration_noise
         self.continuous_actions, self.max_step_amplitude = continuous, args.max_step_amplitude
         self.deterministic = bool(getattr(args, "deterministic", False))
+        self.fused_returns = bool(getattr(args, "fused_returns", False))
         self.M = np.zeros((obs_dim, action_space))
         num_updates = int(args.num_timesteps) // args.num_population * 2
         P, dev = self.n_population, env.device

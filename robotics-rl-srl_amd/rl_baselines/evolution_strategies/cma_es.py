@@ -19,6 +19,9 @@ stacking): one generation is reset + ONE srlhip_rollout_mlp_policy launch — th
 parameters are, is the kernel's parameter plane as it is, member k's MLP picks env k's actions inside the kernel — and the returns
 come from the reward / done planes.  Softmax sampling (no --deterministic) stays on the per-step path unless --fused-sampling is given.
 
+--fused-returns (off by default; needs --fused-rollout on ground-truth observations; ARS's rules: ARSModel.check_returns_arguments):
+the launch returns each member's return and live-step count itself (srlhip_rollout_policy_summary) — the same generation, no planes.
+
 --fused-sampling (off by default; needs --fused-rollout and discrete actions): the reference's default form — no --deterministic, each
 member's action drawn from the softmax of its scores (cma_es.py:228-232) — in the same one launch (srlhip_rollout_mlp_policy_sampled).
 The action draws then come from each env's own counter-based action stream (Philox stream 1, keyed by seed and env id), not from the
@@ -207,6 +210,9 @@ class CMAESModel(object):
                             help='with --fused-rollout and discrete actions: draw each action from the softmax of the scores inside '
                                  'the fused launch (no --deterministic needed). The draws come from each env\'s own action stream, not '
                                  'from the torch.multinomial generator of the per-step path: same distribution, other bits')
+        parser.add_argument('--fused-returns', action='store_true', default=False,
+                            help='with --fused-rollout on ground-truth observations: the launch returns each member\'s return and live steps '
+                                 'itself instead of the reward / done planes (same returns; not with a learned SRL model or --cnn-policy)')
         parser.add_argument('--cnn-policy', action='store_true', default=False,
                             help='with --srl-model raw_pixels: the reference\'s CNN-from-pixels policy, one network per member, run on '
                                  'the device from the rendered frames (srlhip_cnn_policy_act; --num-stack 1, frames of 43..224 a side)')
@@ -220,7 +226,9 @@ class CMAESModel(object):
     @staticmethod
     def check_fused_arguments(args):
         """--fused-sampling against the rest of the arguments, then ARS's rules for --fused-rollout, whose "--deterministic or
-        --continuous-actions" requirement --fused-sampling meets; raises ValueError before any env is built."""
+        --continuous-actions" requirement --fused-sampling meets; raises ValueError before any env is built.  --fused-returns is
+        checked first (ARSModel.check_returns_arguments)."""
+        ARSModel.check_returns_arguments(args)
         if CMAESModel.cnn_from_pixels(args):
             # the CNN-from-pixels path: every action selection has a fused form (the loop of launches samples as the per-step path does)
             if int(getattr(args, "num_stack", 1)) != 1:
@@ -261,6 +269,10 @@ class CMAESModel(object):
         if isinstance(self.policy, BatchedCNN):
             planes = env.rollout_cnn_policy(T, population.to(torch.float32).contiguous(), per_env=True, freeze_after_done=True, sample=sample)
             return self.returns_from_planes(planes["reward"], planes["done"])
+        if getattr(self, "fused_returns", False):          # --fused-returns: the launch reduces; moments only where a wrapper wants them
+            out = env.rollout_mlp_policy_summary(T, population.to(torch.float32).contiguous(), self.policy.H, per_env=True, freeze_after_done=True,
+                                                 moments=False, **kw)
+            return out["ret"], out["length"].to(torch.int64)
         planes = env.rollout_mlp_policy(T, population.to(torch.float32).contiguous(), self.policy.H, per_env=True, freeze_after_done=True, **kw)
         return self.returns_from_planes(planes["reward"], planes["done"])
 
@@ -339,6 +351,7 @@ class CMAESModel(object):
             self.policy = BatchedMLP(int(np.prod(env.observation_space.shape)), action_space, self.HIDDEN)
         self.n_population, self.mu, self.sigma = args.num_population, args.mu, args.sigma
         self.continuous_actions, self.deterministic = continuous, bool(getattr(args, "deterministic", False))
+        self.fused_returns = bool(getattr(args, "fused_returns", False))
         P, dev = self.n_population, env.device
         self.es = CMAES(self.policy.n_params * [self.mu], self.sigma, P, dev, seed=int(args.seed))
         self.best_model = np.array(self.policy.n_params * [self.mu], dtype=np.float64)

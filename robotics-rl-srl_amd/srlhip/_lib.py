@@ -37,7 +37,7 @@ _FIELD_SHAPES = {
 EXPORTS = [
     "srlhip_abi_version", "srlhip_default_config", "srlhip_create", "srlhip_destroy", "srlhip_obs_dim",
     "srlhip_obs_bytes", "srlhip_action_dim", "srlhip_num_actions", "srlhip_seed", "srlhip_reset",
-    "srlhip_reset_rand_count", "srlhip_step", "srlhip_step_async", "srlhip_step_wait", "srlhip_step_pending", "srlhip_set_persistent", "srlhip_rollout", "srlhip_rollout_policy", "srlhip_rollout_policy_sampled", "srlhip_sample_actions", "srlhip_rollout_mlp_policy", "srlhip_rollout_mlp_policy_sampled", "srlhip_policy_act", "srlhip_cnn_policy_act", "srlhip_cnn_param_count", "srlhip_pixel_policy_act", "srlhip_get_state", "srlhip_set_state",
+    "srlhip_reset_rand_count", "srlhip_step", "srlhip_step_async", "srlhip_step_wait", "srlhip_step_pending", "srlhip_set_persistent", "srlhip_rollout", "srlhip_rollout_policy", "srlhip_rollout_policy_sampled", "srlhip_sample_actions", "srlhip_rollout_mlp_policy", "srlhip_rollout_mlp_policy_sampled", "srlhip_rollout_policy_summary", "srlhip_policy_act", "srlhip_cnn_policy_act", "srlhip_cnn_param_count", "srlhip_pixel_policy_act", "srlhip_get_state", "srlhip_set_state",
     "srlhip_device_ptr", "srlhip_render", "srlhip_episode_stats", "srlhip_episode_records", "srlhip_episode_stats_device", "srlhip_sync", "srlhip_copy_async", "srlhip_stream", "srlhip_timing_begin",
     "srlhip_timing_end", "srlhip_last_error", "srlhip_selftest_group_primitives", "srlhip_selftest_rng", "srlhip_kuka_kernel", "srlhip_kuka_default_model", "srlhip_set_kuka_model", "srlhip_kuka_tree_default_model", "srlhip_set_kuka_tree_model",
     "srlhip_graph_begin", "srlhip_graph_end", "srlhip_graph_launch", "srlhip_graph_destroy",
@@ -103,6 +103,14 @@ class MlpPolicy(ctypes.Structure):
     ]
 
 
+class RolloutSummary(ctypes.Structure):
+    """struct srlhip_rollout_summary"""
+    _fields_ = [
+        ("struct_size", ctypes.c_int32), ("reserved", ctypes.c_int32), ("ret", ctypes.c_void_p), ("length", ctypes.c_void_p),
+        ("obs_sum", ctypes.c_void_p), ("obs_sqsum", ctypes.c_void_p),
+    ]
+
+
 class CnnPolicy(ctypes.Structure):
     """struct srlhip_cnn_policy"""
     _fields_ = [
@@ -165,6 +173,7 @@ def load():
     lib.srlhip_sample_actions.argtypes = [vp, vp, vp, vp]
     lib.srlhip_rollout_mlp_policy.argtypes = [vp, i32, ctypes.POINTER(MlpPolicy), vp, vp, vp, vp]
     lib.srlhip_rollout_mlp_policy_sampled.argtypes = [vp, i32, ctypes.POINTER(MlpPolicy), vp, vp, vp, vp]
+    lib.srlhip_rollout_policy_summary.argtypes = [vp, i32, ctypes.POINTER(LinearPolicy), ctypes.POINTER(MlpPolicy), i32, ctypes.POINTER(RolloutSummary)]
     lib.srlhip_policy_act.argtypes = [vp, ctypes.POINTER(LinearPolicy), ctypes.POINTER(MlpPolicy), i32, vp, i32, vp, vp, vp, vp]
     lib.srlhip_cnn_policy_act.argtypes = [vp, ctypes.POINTER(CnnPolicy), i32, vp, vp, vp, vp, vp]
     lib.srlhip_pixel_policy_act.argtypes = [vp, ctypes.POINTER(PixelPolicy), vp, vp, vp, vp, vp]
@@ -431,6 +440,54 @@ class Handle(object):
             shape = ((self.num_envs,) if per_env else ()) + (self.mlp_param_count(int(hidden)),)
         return self._rollout_policy_call("srlhip_rollout_mlp_policy_sampled" if sample else "srlhip_rollout_mlp_policy", T, pol, "params", params, np.float32, shape,
                                          obs_mean, obs_std, want, out)
+
+    def rollout_policy_summary(self, T, weights=None, params=None, hidden=None, sample=False, moments=True, per_env=True, freeze_after_done=False,
+                               obs_mean=None, obs_std=None, clip_obs=10.0, out=None):
+        """srlhip_rollout_policy_summary: rollout_policy (`weights`) or rollout_mlp_policy (`params` + `hidden`), with sample=True their
+        sampled forms, returning what a learner keeps instead of the [T][N] planes: per env the return up to its first done of the
+        call ("ret", float64 [N]), the live-step count ("length", int32 [N]) and, with `moments`, the sums of the live observations
+        and of their squares ("obs_sum", "obs_sqsum", float64 [N][obs_dim]) — include/srlhip.h has the contract.  The env ends in the
+        state the plane call leaves.  Host-pointer handles take numpy arrays and return a dict of new arrays; device-pointer handles
+        take raw device pointers and `out` = (ret, length, obs_sum, obs_sqsum) pointers (0 / None = skip) and only enqueue."""
+        assert (weights is None) != (params is None), "pass weights (linear policy) or params and hidden (MLP)"
+        lin = mlp = None
+        if params is None:
+            pol = lin = self._policy_struct(LinearPolicy, per_env, freeze_after_done, obs_mean, obs_std, clip_obs)
+            field, block, dtype, shape = "weights", weights, np.float64, self.policy_shape(per_env)
+        else:
+            pol = mlp = self._policy_struct(MlpPolicy, per_env, freeze_after_done, obs_mean, obs_std, clip_obs)
+            pol.hidden, pol.reserved = int(hidden), 0
+            field, block, dtype, shape = "params", params, np.float32, None      # (hidden outside 1..128: the library refuses by name)
+            if 1 <= int(hidden) <= 128:
+                shape = ((self.num_envs,) if per_env else ()) + (self.mlp_param_count(int(hidden)),)
+        summ = RolloutSummary()
+        summ.struct_size, summ.reserved = ctypes.sizeof(RolloutSummary), 0
+        keep = []
+        if self.cfg.io_device:
+            setattr(pol, field, block)
+            pol.obs_mean, pol.obs_std = obs_mean, obs_std
+            summ.ret, summ.length, summ.obs_sum, summ.obs_sqsum = [p or None for p in out]
+            result = out
+        else:
+            w = np.ascontiguousarray(block, dtype=dtype)
+            assert shape is None or w.shape == shape, (w.shape, shape)
+            keep.append(w)
+            setattr(pol, field, w.ctypes.data)
+            if obs_mean is not None:
+                mean, std = np.ascontiguousarray(obs_mean, dtype=np.float64), np.ascontiguousarray(obs_std, dtype=np.float64)
+                assert mean.shape == (self.obs_dim,) and std.shape == (self.obs_dim,), (mean.shape, std.shape)
+                keep += [mean, std]
+                pol.obs_mean, pol.obs_std = mean.ctypes.data, std.ctypes.data
+            n = self.num_envs
+            result = {"ret": np.zeros(n, np.float64), "length": np.zeros(n, np.int32)}
+            if moments:
+                result["obs_sum"], result["obs_sqsum"] = np.zeros((n, self.obs_dim), np.float64), np.zeros((n, self.obs_dim), np.float64)
+            for k, a in result.items():
+                setattr(summ, k, a.ctypes.data)
+        self._check(self._lib.srlhip_rollout_policy_summary(self._h, T, None if lin is None else ctypes.byref(lin), None if mlp is None else ctypes.byref(mlp),
+                                                            int(bool(sample)), ctypes.byref(summ)), "srlhip_rollout_policy_summary")
+        del keep
+        return result
 
     def policy_act(self, obs, obs_dim, act_out, weights=None, params=None, hidden=None, per_env=True, freeze_after_done=False,
                    obs_mean=None, obs_std=None, clip_obs=10.0, done_prev=None, frozen=None, sample=False, score_out=None):

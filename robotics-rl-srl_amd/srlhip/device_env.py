@@ -152,6 +152,44 @@ class DeviceVecEnv(object):
         return self._rollout_policy(functools.partial(self.h.rollout_mlp_policy, hidden=hidden, sample=sample), T, params, torch.float32, shape,
                                     per_env, freeze_after_done, obs_mean, obs_std, clip_obs)
 
+    def _rollout_summary(self, T, block, dtype, shape, per_env, freeze_after_done, obs_mean, obs_std, clip_obs, moments, **which):
+        """Handle.rollout_policy_summary on tensors (`block`: the parameter tensor; `which`: its pointer as weights= / params= and
+        hidden=, and sample=), as _rollout_policy: the four small result tensors are allocated on the env's stream, the call only
+        enqueues when the caller is on that stream"""
+        assert block.is_cuda and block.dtype == dtype and block.is_contiguous(), (block.dtype, block.device)
+        assert tuple(block.shape) == shape, (tuple(block.shape), shape)
+        assert (obs_mean is None) == (obs_std is None), "obs_mean and obs_std come together"
+        for x in (obs_mean, obs_std):
+            assert x is None or (x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() and tuple(x.shape) == (self.h.obs_dim,))
+        n, D, dev = self.num_envs, self.h.obs_dim, self.device
+        with _rollout_frame(self):
+            out = {"ret": torch.empty((n,), dtype=torch.float64, device=dev), "length": torch.empty((n,), dtype=torch.int32, device=dev)}
+            if moments:
+                out["obs_sum"] = torch.empty((n, D), dtype=torch.float64, device=dev)
+                out["obs_sqsum"] = torch.empty((n, D), dtype=torch.float64, device=dev)
+            self.h.rollout_policy_summary(T, per_env=per_env, freeze_after_done=freeze_after_done, moments=moments,
+                                          obs_mean=None if obs_mean is None else obs_mean.data_ptr(), obs_std=None if obs_std is None else obs_std.data_ptr(),
+                                          clip_obs=clip_obs, out=tuple(out[k].data_ptr() if k in out else None for k in ("ret", "length", "obs_sum", "obs_sqsum")),
+                                          **which)
+        return out
+
+    def rollout_policy_summary(self, T, weights, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0, sample=False,
+                               moments=True):
+        """srlhip_rollout_policy_summary with a linear policy: rollout_policy's T fused steps (same arguments, same env state
+        afterwards), returning what a learner keeps instead of the planes — {"ret" [N] float64: the rewards before each env's first
+        done of the call, "length" [N] int32: its live steps, "obs_sum", "obs_sqsum" [N][obs_dim] float64 (with `moments`): the sums
+        of its live raw observations and of their squares}, new tensors.  Enqueue-only on the env's stream; per-call scope (a call
+        does not continue the sums of the one before it)."""
+        return self._rollout_summary(T, weights, torch.float64, self.h.policy_shape(per_env), per_env, freeze_after_done, obs_mean, obs_std, clip_obs, moments,
+                                     weights=weights.data_ptr(), sample=sample)
+
+    def rollout_mlp_policy_summary(self, T, params, hidden, per_env=True, freeze_after_done=False, obs_mean=None, obs_std=None, clip_obs=10.0,
+                                   sample=False, moments=True):
+        """rollout_policy_summary with rollout_mlp_policy's one-hidden-layer ReLU MLP (`params`, `hidden`: as there)."""
+        shape = ((self.num_envs,) if per_env else ()) + (self.h.mlp_param_count(int(hidden)),)
+        return self._rollout_summary(T, params, torch.float32, shape, per_env, freeze_after_done, obs_mean, obs_std, clip_obs, moments,
+                                     params=params.data_ptr(), hidden=hidden, sample=sample)
+
     def episode_stats(self):
         return self.h.episode_stats()
 
@@ -214,6 +252,14 @@ class DeviceVecFrameStack(DeviceVecEnvWrapper):
         """As rollout_policy: only the trivial stack passes through."""
         return self._pass_through("rollout_mlp_policy", T, params, hidden, **kw)
 
+    def rollout_policy_summary(self, T, weights, **kw):
+        """As rollout_policy: only the trivial stack passes through."""
+        return self._pass_through("rollout_policy_summary", T, weights, **kw)
+
+    def rollout_mlp_policy_summary(self, T, params, hidden, **kw):
+        """As rollout_policy: only the trivial stack passes through."""
+        return self._pass_through("rollout_mlp_policy_summary", T, params, hidden, **kw)
+
 
 class RunningMeanStd(object):
     """stable_baselines.common.running_mean_std.RunningMeanStd (parallel-variance batch update) on tensors"""
@@ -237,6 +283,17 @@ class RunningMeanStd(object):
         bcount = torch.clamp(w.sum(), min=1.0)
         bmean = (w * x).sum(0) / bcount
         bvar = (w * (x - bmean) ** 2).sum(0) / bcount
+        delta, tot = bmean - self.mean, self.count + bcount
+        m2 = self.var * self.count + bvar * bcount + delta * delta * (self.count * bcount / tot)
+        self.mean, self.var, self.count = self.mean + delta * (bcount / tot), m2 / tot, tot
+
+    def update_from_sums(self, count, sum, sqsum):
+        """The same update from a batch given as its row count and the sums of its rows and of their squares (0-d / [shape]
+        float64 tensors): batch mean = sum / n, batch variance = sqsum / n - mean^2 (clamped at 0), then the merge above.  No
+        device-to-host read; `count` becomes a 0-d tensor."""
+        bcount = torch.clamp(count.to(torch.float64), min=1.0)
+        bmean = sum / bcount
+        bvar = torch.clamp(sqsum / bcount - bmean * bmean, min=0.0)
         delta, tot = bmean - self.mean, self.count + bcount
         m2 = self.var * self.count + bvar * bcount + delta * delta * (self.count * bcount / tot)
         self.mean, self.var, self.count = self.mean + delta * (bcount / tot), m2 / tot, tot
@@ -321,6 +378,40 @@ class DeviceVecNormalize(DeviceVecEnvWrapper):
         updated once afterwards from the live rows of the returned raw observation planes.  `sample` passes through."""
         return self._rollout_frozen(self.venv.rollout_mlp_policy, T, params, hidden, per_env=per_env, freeze_after_done=freeze_after_done,
                                     **({"sample": True} if sample else {}))
+
+    def _summary_frozen(self, call, *args, **more):
+        """`call` (the wrapped env's rollout_policy_summary / rollout_mlp_policy_summary) as _rollout_frozen: the current statistics
+        go to the kernel, frozen for the call; with training = True they are updated ONCE afterwards from the summary's sums of the
+        LIVE rows (up to and including each env's first done: _rollout_frozen's update with freeze_after_done), added over the envs
+        on the device — no host read.  Returns the summary; its moments are of the RAW observations.
+        Two differences from the planes methods, both because the kernel sums live rows only: with training = True and
+        freeze_after_done = False, _rollout_frozen updates from ALL T rows of every env, this method still from the live rows alone;
+        and with training = True the moments are always computed and returned, whatever `moments` says (the update needs them)."""
+        if not self.norm_obs:
+            return call(*args, **more)
+        mean = self.obs_rms.mean.reshape(-1).contiguous()
+        std = torch.sqrt(self.obs_rms.var + self.epsilon).reshape(-1).contiguous()
+        out = call(*args, obs_mean=mean, obs_std=std, clip_obs=self.clip_obs, **dict(more, moments=True if self.training else more.get("moments", True)))
+        if self.training:
+            shape = self.obs_rms.mean.shape
+            self.obs_rms.update_from_sums(out["length"].sum(), out["obs_sum"].sum(0).reshape(shape), out["obs_sqsum"].sum(0).reshape(shape))
+        return out
+
+    def rollout_policy_summary(self, T, weights, per_env=True, freeze_after_done=False, sample=False, moments=True):
+        """The wrapped env's rollout_policy_summary on NORMALISED observations: the current statistics are frozen for the call and,
+        with training = True, updated ONCE afterwards from the sums of the live rows (up to and including each env's first done).
+        That is rollout_policy's update with freeze_after_done = True; WITHOUT freeze_after_done rollout_policy updates from all T
+        rows and this method does not (the kernel sums live rows only).  With training = True the returned dict holds "obs_sum" and
+        "obs_sqsum" even with moments=False: the update needs them."""
+        return self._summary_frozen(self.venv.rollout_policy_summary, T, weights, per_env=per_env, freeze_after_done=freeze_after_done, sample=sample,
+                                    moments=moments)
+
+    def rollout_mlp_policy_summary(self, T, params, hidden, per_env=True, freeze_after_done=False, sample=False, moments=True):
+        """rollout_policy_summary's schedule for the MLP policy: statistics frozen for the call; with training = True one update
+        afterwards from the live rows' sums — rollout_mlp_policy's update with freeze_after_done = True, NOT its all-rows update
+        without it — and the moments are then returned even with moments=False."""
+        return self._summary_frozen(self.venv.rollout_mlp_policy_summary, T, params, hidden, per_env=per_env, freeze_after_done=freeze_after_done,
+                                    sample=sample, moments=moments)
 
     def reset(self):
         obs = self.venv.reset()
