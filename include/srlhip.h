@@ -862,6 +862,32 @@ int srlhip_pca_project_host(int64_t n_features, int32_t state_dim, const double 
 int srlhip_pca_destroy(srlhip_pca_handle p);
 const char *srlhip_pca_last_error(srlhip_pca_handle p);
 
+/* ---- fitting the PCA baseline: the Gram matrix of recorded frames ----------------------------------------
+ * The hot part of state_representation/pca_fit.py (the closed-form fit of the model the calls above apply).  frames is
+ * uint8 [n][F] row-major, as srlhip_render leaves them:
+ *     gram[i][j] = sum_f frames[i][f] frames[j][f]   int64 [n][n], full and symmetric
+ *     rowsum[i]  = sum_f frames[i][f]                int64 [n]
+ * EXACT integers: every summation order gives the same bits, so the device and the host twin agree bit for bit and the
+ * result does not depend on split.  On the device (csrc/pca_gram.hip) one wavefront per 32 x 32 tile of the upper
+ * triangle runs v_mfma_i32_32x32x32_i8 on the signed bytes x - 128 (gram = S + 128 (rowsum_i + rowsum_j) - 16384 F, padding
+ * masked to a signed 0 after the xor, no byte outside [0, n F) read), an int32 accumulator takes at most 65536 features
+ * before it is added into int64, and the K dimension is cut into slices over workgroups: split = 0 chooses their number,
+ * split >= 1 asks for that many (slices that would be empty are not launched).  With one slice the plane is stored;
+ * with several it is zeroed on the stream and every slice adds its share with 64-bit atomic adds.
+ * Shapes: 1 <= n <= 8192, n_features >= 1, 2 n^2 n_features 65025 < 2^63 (which keeps the fit's integer centring in int64);
+ * srlhip_pca_gram_supported tells beforehand, anything else -> SRLHIP_ENOTSUP.  A negative split or a null pointer ->
+ * SRLHIP_EINVAL.  A refused call touches neither plane.  srlhip_pca_gram only enqueues on hip_stream (NULL = the default
+ * stream): the zeroes (several slices), the row sums, the tiles, three kernels at most; all pointers are DEVICE pointers on device_id and
+ * frames_dev needs no alignment (16-byte loads when it and n_features are multiples of 16, guarded bytes otherwise).
+ * srlhip_pca_gram_host is the host twin (host pointers, plain int64 loops, no GPU).  The message of a failed call of
+ * either is the calling thread's srlhip_pca_gram_last_error. */
+int srlhip_pca_gram_supported(int32_t n, int64_t n_features);                 /* host only */
+int srlhip_pca_gram(int32_t device_id, const uint8_t *frames_dev, int32_t n, int64_t n_features, int32_t split,
+                    int64_t *gram_dev /* [n][n] */, int64_t *rowsum_dev /* [n] */, void *hip_stream);  /* enqueue-only */
+int srlhip_pca_gram_host(const uint8_t *frames, int32_t n, int64_t n_features,
+                         int64_t *gram, int64_t *rowsum);                     /* host only */
+const char *srlhip_pca_gram_last_error(void);
+
 
 #ifdef __cplusplus
 }

@@ -46,6 +46,7 @@ EXPORTS = [
     "srlhip_encoder_destroy", "srlhip_encoder_last_error", "srlhip_encoder_pack_bytes", "srlhip_encoder_pack", "srlhip_encoder_pack_i8_bytes", "srlhip_encoder_pack_i8", "srlhip_encoder_pack_first_layer",
     "srlhip_jpeg_encode", "srlhip_render_jpeg", "srlhip_jpeg_header_bytes", "srlhip_jpeg_encode_host",
     "srlhip_pca_supported", "srlhip_pca_create", "srlhip_pca_forward", "srlhip_pca_project_host", "srlhip_pca_destroy", "srlhip_pca_last_error",
+    "srlhip_pca_gram_supported", "srlhip_pca_gram", "srlhip_pca_gram_host", "srlhip_pca_gram_last_error",
 ]
 
 
@@ -217,6 +218,11 @@ def load():
     lib.srlhip_pca_destroy.argtypes = [vp]
     lib.srlhip_pca_last_error.restype = ctypes.c_char_p
     lib.srlhip_pca_last_error.argtypes = [vp]
+    lib.srlhip_pca_gram_supported.argtypes = [i32, ctypes.c_int64]
+    lib.srlhip_pca_gram.argtypes = [i32, vp, i32, ctypes.c_int64, i32, vp, vp, vp]
+    lib.srlhip_pca_gram_host.argtypes = [vp, i32, ctypes.c_int64, vp, vp]
+    lib.srlhip_pca_gram_last_error.restype = ctypes.c_char_p
+    lib.srlhip_pca_gram_last_error.argtypes = []
     lib.srlhip_encoder_pack_bytes.restype = ctypes.c_size_t
     lib.srlhip_encoder_pack_bytes.argtypes = []
     lib.srlhip_encoder_pack.argtypes = [vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
@@ -941,3 +947,37 @@ class PcaProjector(object):
             self.close()
         except Exception:
             pass
+
+
+GRAM_MAX_FRAMES, GRAM_CHUNK = 8192, 65536
+
+
+def pca_gram_supported(n, n_features):
+    """host only: does srlhip_pca_gram take this shape (1 <= n <= 8192, n_features >= 1, 2 n^2 n_features 65025 < 2^63)"""
+    return bool(load().srlhip_pca_gram_supported(int(n), int(n_features)))
+
+
+def _gram_fail(what, rc):
+    raise SrlHipError("{} failed ({}): {}".format(what, rc, load().srlhip_pca_gram_last_error().decode()))
+
+
+def pca_gram(device_id, frames_ptr, n, n_features, gram_ptr, rowsum_ptr, split=0, stream=None):
+    """srlhip_pca_gram: gram int64 [n][n] = X X^T and rowsum int64 [n] of the device-resident uint8 frames [n][n_features], exactly
+    (csrc/pca_gram.hip).  Raw device pointers (e.g. torch.Tensor.data_ptr()); enqueue-only on `stream`; split 0 = automatic."""
+    rc = load().srlhip_pca_gram(int(device_id), _ptr(frames_ptr), int(n), int(n_features), int(split), _ptr(gram_ptr), _ptr(rowsum_ptr),
+                                ctypes.c_void_p(stream) if stream else None)
+    if rc:
+        _gram_fail("srlhip_pca_gram", rc)
+
+
+def pca_gram_host(frames):
+    """srlhip_pca_gram_host: the same two planes on the CPU, plain int64 loops.  frames uint8 [n][...] (flattened to [n][F]) ->
+    (gram int64 [n][n], rowsum int64 [n]); raises SrlHipError on a refusal."""
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    n = frames.shape[0]
+    frames = frames.reshape(n, int(np.prod(frames.shape[1:])))
+    gram, rowsum = np.zeros((n, n), np.int64), np.zeros(n, np.int64)
+    rc = load().srlhip_pca_gram_host(_ptr(frames), n, frames.shape[1], _ptr(gram), _ptr(rowsum))
+    if rc:
+        _gram_fail("srlhip_pca_gram_host", rc)
+    return gram, rowsum
