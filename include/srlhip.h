@@ -622,6 +622,76 @@ size_t srlhip_jpeg_header_bytes(void);
 int srlhip_jpeg_encode_host(const uint8_t *image, int32_t img_h, int32_t img_w, int32_t pix_stride, int32_t quality, uint8_t *out,
                             size_t cap, size_t *len);
 
+/* ---- JPEG decoding of the library's own streams where they lie on the device (reading a recorded dataset) --------------------
+ * The inverse of srlhip_jpeg_encode, for exactly the streams it writes; every other JPEG is refused, never mis-decoded (Pillow stays
+ * the reader for those).  blob_dev / offsets_dev [n_streams + 1] have srlhip_jpeg_encode's layout: stream s is
+ * blob_dev[offsets_dev[s] .. offsets_dev[s + 1]).  images_dev uint8 [n_streams * 3 / C][H][W][C]: C = 3 -> one frame per stream, C = 6 ->
+ * streams 2i and 2i + 1 become channels 0..2 and 3..5 of frame i (n_streams even).  workspace_dev: 16-byte aligned,
+ * srlhip_jpeg_decode_workspace_bytes(n_streams, H, W) bytes (0 = these sizes are refused), contents undefined afterwards.  The call only
+ * enqueues (five launches) on hip_stream (NULL = the default stream), allocates nothing and may be captured into a graph.
+ * SRLHIP_EINVAL: C not 3 or 6, a side outside 8..1024, n_streams negative, odd with C = 6 or with more than 2^31 / 6 MCUs in all, a
+ * null buffer, a misaligned workspace.
+ *
+ * status_dev[s]: 0 decoded; 1 the first 629 bytes are not the accepted layout for this H, W; 2 empty stream (the length 0 an overflowed
+ * encode leaves); 3 entropy-coded data malformed.  A frame (C = 6: a view) whose status is not 0 is written as zeros.
+ *
+ * ACCEPTED LAYOUT: the 629 bytes srlhip_jpeg_encode writes in front of the data for sides H, W — SOI, APP0 (JFIF 1.01), two 8-bit DQT
+ * (ids 0, 1), SOF0 (8 bits, 3 components, Y 2x2 table 0, Cb and Cr 1x1 table 1), the four Annex K.3 DHT, DRI = 1, SOS — compared byte
+ * for byte, EXCEPT the 2 x 64 table values (bytes 25..88 and 94..157), which are read and used, whatever they are.  Behind them the
+ * data: a byte 0xFF whose successor is not 0x00 (or is missing) is a marker; there must be exactly n_mcus = ceil(H / 16) ceil(W / 16) of
+ * them, the k-th being RST(k mod 8) and the last EOI as the stream's final two bytes — else status 3.  MCU k is the bytes between
+ * marker k - 1 (the header for k = 0) and marker k.  Streams of 2^30 bytes or more: status 3.
+ *
+ * SAFETY: every read of blob_dev lies inside the stream's own [offsets_dev[s], offsets_dev[s + 1]) and, while an MCU is decoded, inside
+ * that MCU's bytes; every write inside images_dev's n_streams / (C / 3) frames, status_dev's n_streams words and the workspace.  An MCU
+ * reads at most 6 x 64 symbols whatever its bytes hold.
+ *
+ * ARITHMETIC CONTRACT (integers only; csrc/jpeg_decode.hpp is its one implementation for device and host, tests/jpeg_decode_ref.py
+ * restates it in numpy; >> is an arithmetic shift).  It restates what libjpeg does by default, so that Pillow and this decoder give
+ * the same frame:
+ *   bits      most significant first; the 0x00 behind an 0xFF is dropped.  Blocks per MCU: Y0 Y1 (top) Y2 Y3 (bottom), Cb, Cr; Y uses
+ *             DC / AC table 0 and DQT 0, Cb and Cr table 1 and DQT 1.  Bits past the MCU's last byte: status 3 once one is consumed.
+ *   DC        category n (0..11), then n bits v: diff = v when v >= 2^(n - 1), else v - 2^n + 1 (the encoder's rule inverted);
+ *             DC = previous block's DC of the component INSIDE the MCU (Y0 -> Y1 -> Y2 -> Y3 from 0; Cb, Cr from 0) + diff
+ *   AC        k = 1; symbol (run, size): size 0, run 15 -> k += 16, and k > 63 is status 3 (a coefficient must follow a ZRL); size 0,
+ *             other run -> the block ends (EOB); else k += run, k > 63 is status 3, coefficient k of the zigzag scan = size bits
+ *             extended as above, k += 1; the block also ends at k = 64.  Sixteen bits that are no code: status 3.
+ *   dequant   coefficient * the DQT's k-th value, kept in 16 bits (two's complement wrap; exact for every stream the encoder writes)
+ *   IDCT      libjpeg's slow-integer inverse DCT.  One 8-point pass on x0..x7, constants round(c 2^13):
+ *               z = (x2 + x6) 4433;  t2 = z - x6 15137;  t3 = z + x2 6270;  t0 = (x0 + x4) << 13;  t1 = (x0 - x4) << 13
+ *               t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2
+ *               z5 = (x7 + x3 + x5 + x1) 9633;  z1 = -(x7 + x1) 7373;  z2 = -(x5 + x3) 20995
+ *               z3 = z5 - (x7 + x3) 16069;  z4 = z5 - (x5 + x1) 3196
+ *               o0 = x7 2446 + z1 + z3;  o1 = x5 16819 + z2 + z4;  o2 = x3 25172 + z2 + z3;  o3 = x1 12299 + z1 + z4
+ *               y0, y7 = t10 +- o3;  y1, y6 = t11 +- o2;  y2, y5 = t12 +- o1;  y3, y4 = t13 +- o0;  each (y + 2^(S - 1)) >> S
+ *             first down every column with S = 11 (two extra bits kept), then along every row with S = 18.  Sums are 32-bit two's
+ *             complement (they wrap; on the encoder's streams none does).  sample = libjpeg's range-limit table on the low 10 bits t
+ *             of the result: t + 128 for t < 128, 255 for t < 512, 0 for t < 896, else t - 896 — that is clamp(value + 128, 0, 255)
+ *             for every value in -512..511.
+ *   upsample  libjpeg's "fancy" 2x2 upsampling of the ceil(H / 2) x ceil(W / 2) REAL chroma samples (what lies past them in the padded
+ *             MCUs is not used; rows and columns past the edge repeat the edge).  For pixel (y, x): r = y >> 1, c = x >> 1, the farther
+ *             row f = r - 1 for even y, r + 1 for odd y (clamped); column sums s[j] = 3 p[r][j] + p[f][j];
+ *             even x: (3 s[c] + s[c - 1] + 8) >> 4, at c = 0 (4 s[c] + 8) >> 4;  odd x: (3 s[c] + s[c + 1] + 7) >> 4, at the last
+ *             column (4 s[c] + 7) >> 4
+ *   colour    with cb = Cb - 128, cr = Cr - 128:  R = clamp(Y + ((91881 cr + 32768) >> 16)),
+ *             G = clamp(Y + ((-22554 cb - 46802 cr + 32768) >> 16)),  B = clamp(Y + ((116130 cb + 32768) >> 16)), clamp to 0..255
+ *   crop      pixel (y, x) for y < H, x < W
+ * AGAINST PILLOW (12.2, libjpeg-turbo; tests/test_jpeg_decode_cpu.py, on the CPU): over 74 streams of the encoder (8x8 .. 224x224, six
+ * kinds of frame, quality 10 / 50 / 95 / 100; 441 600 samples) the maximum |difference| to Image.open(...).convert("RGB") is 0 and 0
+ * samples differ: equality is reached. */
+int srlhip_jpeg_decode(int32_t device_id, const uint8_t *blob_dev, const int64_t *offsets_dev, int32_t n_streams, int32_t img_h,
+                       int32_t img_w, int32_t n_channels, uint8_t *images_dev, int32_t *status_dev, void *workspace_dev, void *hip_stream);
+/* Host only: the bytes of workspace srlhip_jpeg_decode needs; 0 for sizes it refuses. */
+size_t srlhip_jpeg_decode_workspace_bytes(int32_t n_streams, int32_t img_h, int32_t img_w);
+/* Host only, no GPU needed: 0 and the sides when stream[0 .. len) starts with the accepted layout (only the 629 header bytes are
+ * read; img_h / img_w may be NULL), else SRLHIP_ENOTSUP. */
+int srlhip_jpeg_probe(const uint8_t *stream, size_t len, int32_t *img_h, int32_t *img_w);
+/* Host only, no GPU needed: ONE stream through the same source on the CPU, the sides taken from its header; pixel (y, x) is written at
+ * out + (y * W + x) * pix_stride, three bytes R G B (pix_stride >= 3: a view of a 6-channel frame is written in place); out_cap = the
+ * bytes available at out, at least (H W - 1) pix_stride + 3, else SRLHIP_ENOMEM.  Returns 0 with *status = 0 (decoded) or 3 (zeros
+ * written); SRLHIP_ENOTSUP with *status = 1 or 2 when the header is not accepted (nothing is written).  status may be NULL. */
+int srlhip_jpeg_decode_host(const uint8_t *stream, size_t len, uint8_t *out, int32_t pix_stride, size_t out_cap, int32_t *status);
+
 /* Per-env statistics of the most recently FINISHED episode and the number of
  * finished episodes: what stable_baselines.bench.Monitor records
  * (environments/utils.py:54).  HOST pointers, any may be NULL. */

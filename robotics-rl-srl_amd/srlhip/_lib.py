@@ -45,6 +45,7 @@ EXPORTS = [
     "srlhip_encoder_phase_cycles",
     "srlhip_encoder_destroy", "srlhip_encoder_last_error", "srlhip_encoder_pack_bytes", "srlhip_encoder_pack", "srlhip_encoder_pack_i8_bytes", "srlhip_encoder_pack_i8", "srlhip_encoder_pack_first_layer",
     "srlhip_jpeg_encode", "srlhip_render_jpeg", "srlhip_jpeg_header_bytes", "srlhip_jpeg_encode_host",
+    "srlhip_jpeg_probe", "srlhip_jpeg_decode_host", "srlhip_jpeg_decode_workspace_bytes", "srlhip_jpeg_decode",
     "srlhip_pca_supported", "srlhip_pca_create", "srlhip_pca_forward", "srlhip_pca_project_host", "srlhip_pca_destroy", "srlhip_pca_last_error",
     "srlhip_pca_gram_supported", "srlhip_pca_gram", "srlhip_pca_gram_host", "srlhip_pca_gram_last_error",
 ]
@@ -235,6 +236,11 @@ def load():
     lib.srlhip_jpeg_header_bytes.restype = ctypes.c_size_t
     lib.srlhip_jpeg_header_bytes.argtypes = []
     lib.srlhip_jpeg_encode_host.argtypes = [vp, i32, i32, i32, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    lib.srlhip_jpeg_probe.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    lib.srlhip_jpeg_decode_host.argtypes = [vp, ctypes.c_size_t, vp, i32, ctypes.c_size_t, ctypes.POINTER(i32)]
+    lib.srlhip_jpeg_decode_workspace_bytes.restype = ctypes.c_size_t
+    lib.srlhip_jpeg_decode_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.srlhip_jpeg_decode.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -781,6 +787,55 @@ def jpeg_encode_host(frame, quality, cap=None):
     if rc:
         raise SrlHipError("srlhip_jpeg_encode_host failed ({}), stream size {}".format(rc, n.value))
     return out[:n.value].tobytes()
+
+
+JPEG_OK, JPEG_BAD_HEADER, JPEG_EMPTY, JPEG_BAD_DATA = 0, 1, 2, 3          # status_dev of srlhip_jpeg_decode
+
+
+def jpeg_probe(data):
+    """srlhip_jpeg_probe: (h, w) when `data` (bytes) has the layout the library's encoder writes, else None; no GPU needed"""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    h, w = ctypes.c_int32(0), ctypes.c_int32(0)
+    rc = load().srlhip_jpeg_probe(ctypes.c_void_p(buf.ctypes.data if len(buf) else None), len(buf), ctypes.byref(h), ctypes.byref(w))
+    return (int(h.value), int(w.value)) if rc == 0 else None
+
+
+def jpeg_decode_host(data, out=None, return_status=False):
+    """srlhip_jpeg_decode_host: one stream through the kernels' own source on the CPU -> uint8 [h][w][3].  `out`: a uint8 [h][w][3] view
+    to write into (any pixel stride: channels 0..2 or 3..5 of a 6-channel frame).  Raises ValueError when the stream is not in the
+    accepted format, SrlHipError when its data is malformed — or, with return_status, returns (frame, status) for statuses 0 and 3."""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    hw = jpeg_probe(data)
+    if hw is None:
+        raise ValueError("not a stream of the library's encoder")
+    h, w = hw
+    if out is None:
+        out = np.zeros((h, w, 3), np.uint8)
+    assert out.dtype == np.uint8 and out.shape == (h, w, 3) and out.strides[2] == 1 and out.strides[0] == w * out.strides[1]
+    stride = int(out.strides[1])
+    status = ctypes.c_int32(-1)
+    rc = load().srlhip_jpeg_decode_host(ctypes.c_void_p(buf.ctypes.data), len(buf), ctypes.c_void_p(out.ctypes.data), stride,
+                                        (h * w - 1) * stride + 3, ctypes.byref(status))
+    if rc:
+        raise SrlHipError("srlhip_jpeg_decode_host failed ({})".format(rc))
+    if return_status:
+        return out, int(status.value)
+    if status.value:
+        raise SrlHipError("srlhip_jpeg_decode_host: malformed entropy-coded data (status {})".format(status.value))
+    return out
+
+
+def jpeg_decode_workspace_bytes(n_streams, h, w):
+    return int(load().srlhip_jpeg_decode_workspace_bytes(int(n_streams), int(h), int(w)))
+
+
+def jpeg_decode(blob_dev_ptr, offsets_dev_ptr, n_streams, h, w, c, images_dev_ptr, status_dev_ptr, workspace_dev_ptr, device_id=0, stream=0):
+    """srlhip_jpeg_decode, raw: device pointers (the blob and int64 offsets [n_streams + 1] of srlhip_jpeg_encode in; uint8
+    [n_streams * 3 / c][h][w][c] frames and int32 status [n_streams] out; jpeg_decode_workspace_bytes of scratch); only enqueues on
+    `stream`.  Returns the library's status code."""
+    return load().srlhip_jpeg_decode(int(device_id), _ptr(blob_dev_ptr), _ptr(offsets_dev_ptr), int(n_streams), int(h), int(w), int(c),
+                                     _ptr(images_dev_ptr), _ptr(status_dev_ptr), _ptr(workspace_dev_ptr),
+                                     ctypes.c_void_p(stream) if stream else None)
 
 
 def encoder_supported(img_h, img_w, n_channels):

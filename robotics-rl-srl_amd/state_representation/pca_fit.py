@@ -19,6 +19,7 @@ Step a is bit-identical between the backends because it is integer arithmetic, s
 bit for bit, and everything else is the same numpy code: fit_pca(backend="hip") and fit_pca(backend="host") give the same bits.
 
     python -m state_representation.pca_fit --data-folder <recorded dataset> --state-dim K [--max-frames 4096] [--device-id 0] --log-folder <out>
+        [--decode-backend hip]    (datasets of `dataset_generator --device-jpeg`: the files are decoded on the GPU and never exist decoded on the host)
 """
 import argparse
 import glob
@@ -171,15 +172,27 @@ def fit_pca_from_env(env, n_steps, state_dim, seed=0):
     return fit_pca(collect_frames(env, n_steps, seed=seed), state_dim, backend="hip")
 
 
-def load_dataset_frames(data_folder, max_frames=4096):
-    """the record_*/frame*.jpg of a dataset `dataset_generator` wrote, subsampled evenly down to max_frames -> uint8 [N][H][W][3]"""
-    from PIL import Image
+def load_dataset_frames(data_folder, max_frames=4096, backend="pillow", device_id=None):
+    """the record_*/frame*.jpg of a dataset `dataset_generator` wrote, subsampled evenly down to max_frames -> uint8 [N][H][W][3].
+    backend "pillow": decoded on the host, a numpy array; "hip": the files' bytes are uploaded and decoded on the GPU
+    (srlhip.jpeg_io.decode_files: only streams of this library's encoder, `dataset_generator --device-jpeg`; ValueError names the first
+    file that is not one), a device tensor; "auto": hip when a GPU is visible and every selected file is such a stream, else pillow."""
+    if backend not in ("pillow", "hip", "auto"):
+        raise ValueError("backend must be pillow, hip or auto")
     paths = sorted(glob.glob(os.path.join(data_folder, "record_*", "frame*.jpg")))
     if not paths:
         raise ValueError("no record_*/frame*.jpg under {}".format(data_folder))
     max_frames = min(int(max_frames), MAX_FRAMES)
     if len(paths) > max_frames:
         paths = [paths[i] for i in np.linspace(0, len(paths) - 1, max_frames).round().astype(int)]
+    if backend != "pillow":
+        import torch
+        from srlhip import jpeg_io
+        if backend == "hip" and not torch.cuda.is_available():
+            raise RuntimeError("load_dataset_frames(backend='hip') needs a GPU")
+        if backend == "hip" or (torch.cuda.is_available() and jpeg_io.all_accepted(paths)):
+            return jpeg_io.decode_files(paths, torch.device("cuda", torch.cuda.current_device() if device_id is None else device_id))
+    from PIL import Image
     return np.stack([np.asarray(Image.open(p).convert("RGB"), dtype=np.uint8) for p in paths])
 
 
@@ -190,9 +203,11 @@ def main(argv=None):
     parser.add_argument("--max-frames", type=int, default=4096)
     parser.add_argument("--device-id", type=int, default=0)
     parser.add_argument("--backend", default="auto", choices=("auto", "hip", "host"))
+    parser.add_argument("--decode-backend", default="pillow", choices=("pillow", "hip", "auto"),
+                        help="who decodes the recorded JPEG files: Pillow on the host, or the GPU (streams of --device-jpeg datasets only)")
     parser.add_argument("--log-folder", required=True, help="the model goes to <log-folder>/baselines/pca_ST_DIM<k>/pca.pkl")
     args = parser.parse_args(argv)
-    frames = load_dataset_frames(args.data_folder, args.max_frames)
+    frames = load_dataset_frames(args.data_folder, args.max_frames, backend=args.decode_backend, device_id=args.device_id)
     model = fit_pca(frames, args.state_dim, backend=args.backend, device_id=args.device_id)
     path = model.save(args.log_folder)
     print("fitted {} components on {} frames of {} ({}): explained variance ratio {:.4f} -> {}".format(
