@@ -692,6 +692,65 @@ int srlhip_jpeg_probe(const uint8_t *stream, size_t len, int32_t *img_h, int32_t
  * written); SRLHIP_ENOTSUP with *status = 1 or 2 when the header is not accepted (nothing is written).  status may be NULL. */
 int srlhip_jpeg_decode_host(const uint8_t *stream, size_t len, uint8_t *out, int32_t pix_stride, size_t out_cap, int32_t *status);
 
+/* ---- JPEG decoding of baseline streams as libjpeg writes them by default (reading a dataset any recorder wrote) ---------------
+ * What srlhip_jpeg_decode refuses: the files of Pillow's save() (srlhip/recorder.py) and of cv2.imwrite (the reference's
+ * state_representation/episode_saver.py) — 4:2:0 or 4:4:4, the Annex K.3 Huffman tables, any restart interval or none.  Everything
+ * not named differently here is srlhip_jpeg_decode's: the layout of blob_dev / offsets_dev / images_dev, the pairing of streams 2i,
+ * 2i + 1 for C = 6, sides 8..1024, status 0 / 1 (header not accepted, or its sides are not the call's H, W) / 2 (empty stream) / 3
+ * (entropy-coded data malformed; also streams of 2^30 bytes or more), zeros for a frame or view whose status is not 0, the
+ * SRLHIP_EINVAL rules (the bound on the call's size is n_streams * blocks < 2^31 with blocks as below), the 16-byte aligned workspace
+ * of srlhip_jpeg_decode_baseline_workspace_bytes(n_streams, H, W) bytes (0 = these sizes are refused).  The call only enqueues (five
+ * launches) on hip_stream, allocates nothing, does no host synchronisation and may be captured into a graph.  The workspace is sized
+ * for the worse of the two sampling modes — blocks = max(6 ceil(H / 16) ceil(W / 16), 3 ceil(H / 8) ceil(W / 8)) per stream, 192 bytes
+ * per block, 272 bytes of descriptor per stream — so that one call may mix them.
+ * TUNING OVERRIDE: the entropy launch gives a stream to the first L lanes of every wavefront; L = 4 is built in (profiles/NOTES.md BB has
+ * the measurement).  The environment variable SRLHIP_JPEG_BASELINE_LANES = 64, 16 or 4, read at every call, replaces L for that call
+ * (any other value is ignored); the frames and status words do not depend on it.  profiles/jpeg_baseline_decode_microbench.py uses it.
+ *
+ * ACCEPTED LAYOUT: SOI, then marker segments (FF, marker, 16-bit length, body) up to SOS; at most 64 segments, more is status 1.
+ *   APP0..APP13, APP15, COM   skipped by their length.  APP14 (Adobe) is status 1: it can change the colour transform.
+ *   DQT    8-bit precision only, ids 0..3, several tables per segment allowed, a later definition replaces an earlier one.
+ *   SOF0   only, once: 8 bits, 3 components with ids 1, 2, 3 in that order, sampling (2x2, 1x1, 1x1) or (1x1, 1x1, 1x1), Tq 0..3;
+ *          every Tq refers to a table defined before SOS.
+ *   DHT    class 0 / 1, id 0 / 1, several tables per segment allowed; every table must be, byte for byte, the Annex K.3 luminance or
+ *          chrominance table of its class (either may stand under either id).  Optimised tables are status 1.
+ *   DRI    any interval Ri, 0 = none.
+ *   SOS    3 components in frame order, every table selector 0 / 1 and defined, Ss = 0, Se = 63, Ah = Al = 0.
+ *   Any other marker in front of SOS is status 1: SOF1 / 2 / .., DAC, DNL, a second SOF, RST, EOI, a fill byte.
+ * Behind SOS lies one interleaved scan of ceil(H / 16) ceil(W / 16) MCUs of 6 blocks (4:2:0: Y0 Y1 Y2 Y3 Cb Cr) or ceil(H / 8) ceil(W / 8)
+ * MCUs of 3 blocks (4:4:4: Y Cb Cr), rows top to bottom, left to right.
+ *   bits      most significant first; the 0x00 behind an 0xFF is dropped.  An 0xFF followed by anything but 0x00, or by nothing, ends
+ *             the data there: bits past it, or past the stream's end, are status 3 once one is consumed.  Bytes behind the last MCU
+ *             are not read.
+ *   DC        prediction runs per component ACROSS MCUs, from 0 at the start of the scan and after each restart
+ *   restart   with Ri > 0, after every Ri MCUs except behind the last one: the remaining bits of the current byte are dropped and the
+ *             next two bytes must be FF D0+(k mod 8) for the k-th restart (k from 0); anything else is status 3
+ *   symbols   category, extension, ZRL, EOB and k > 63 rules are srlhip_jpeg_decode's (DC, AC above); a component uses the K.3 tables
+ *             its SOS selectors name and the DQT its Tq names.  A stream is decoded with at most blocks x 64 symbols.
+ * Dequantisation (16-bit wrap), IDCT, range limit, fancy upsampling over the real ceil(H / 2) x ceil(W / 2) chroma samples, colour and
+ * crop are srlhip_jpeg_decode's ARITHMETIC CONTRACT.  For 4:4:4 there is no upsampling: Cb and Cr are taken at the pixel.
+ * csrc/jpeg_baseline.hpp is the one implementation for device and host, tests/jpeg_baseline_ref.py restates it in numpy.
+ * The library's own streams are baseline streams with Ri = 1 and decode through this call to the same frames.
+ *
+ * SAFETY: every read of blob_dev lies inside the stream's own [offsets_dev[s], offsets_dev[s + 1]) (the data is fetched in aligned
+ * 16-byte pieces; a piece that reaches across the stream's first or last byte is read byte by byte instead); every write inside
+ * images_dev's n_streams / (C / 3) frames, status_dev's n_streams words and the workspace.
+ *
+ * AGAINST PILLOW (12.2, libjpeg-turbo; tests/test_jpeg_baseline_cpu.py, on the CPU): over the streams of
+ * tests/golden/jpeg_baseline_pillow.npz, written by Pillow (sizes 8x8 .. 224x224 with odd ones, six kinds of frame, quality 10 / 50 /
+ * 95 / 100, 4:2:0 and 4:4:4, with and without restart markers), 0 samples differ from Image.open(...).convert("RGB"). */
+int srlhip_jpeg_decode_baseline(int32_t device_id, const uint8_t *blob_dev, const int64_t *offsets_dev, int32_t n_streams, int32_t img_h,
+                                int32_t img_w, int32_t n_channels, uint8_t *images_dev, int32_t *status_dev, void *workspace_dev,
+                                void *hip_stream);
+/* Host only: the bytes of workspace srlhip_jpeg_decode_baseline needs; 0 for sizes it refuses. */
+size_t srlhip_jpeg_decode_baseline_workspace_bytes(int32_t n_streams, int32_t img_h, int32_t img_w);
+/* Host only, no GPU needed: 0, the sides and the sampling (420 or 444) when the segments of stream[0 .. len) up to SOS are the accepted
+ * layout (nothing behind SOS is read; any of the three may be NULL), else SRLHIP_ENOTSUP. */
+int srlhip_jpeg_probe_baseline(const uint8_t *stream, size_t len, int32_t *img_h, int32_t *img_w, int32_t *sampling);
+/* Host only, no GPU needed: ONE stream through the same source on the CPU; arguments, return values and *status as
+ * srlhip_jpeg_decode_host. */
+int srlhip_jpeg_decode_baseline_host(const uint8_t *stream, size_t len, uint8_t *out, int32_t pix_stride, size_t out_cap, int32_t *status);
+
 /* Per-env statistics of the most recently FINISHED episode and the number of
  * finished episodes: what stable_baselines.bench.Monitor records
  * (environments/utils.py:54).  HOST pointers, any may be NULL. */

@@ -137,8 +137,9 @@ struct BitSource {
     JPEG_HD bool overrun() const { return bad || nbits < fake; }
 };
 
-// one symbol of table k; -1 for sixteen bits that are no code
-JPEG_HD int decode_symbol(BitSource &b, const DecTables &t, int k) {
+// one symbol of table k; -1 for sixteen bits that are no code.  Bits: BitSource, or another source with its refill / peek16 / skip / take
+template <class Bits>
+JPEG_HD int decode_symbol(Bits &b, const DecTables &t, int k) {
     b.refill();
     const uint32_t v = b.peek16();
     const uint32_t e = t.look[k][v >> (16 - kLookBits)];
@@ -157,7 +158,8 @@ JPEG_HD int decode_symbol(BitSource &b, const DecTables &t, int k) {
 }
 
 // the n bits behind a category code (the encoder's rule inverted: a value below 2^(n - 1) stands for v - 2^n + 1)
-JPEG_HD int extend_bits(BitSource &b, int n) {
+template <class Bits>
+JPEG_HD int extend_bits(Bits &b, int n) {
     b.refill();
     const int v = (int)b.take(n);
     return v < (1 << (n - 1)) ? v - (1 << n) + 1 : v;

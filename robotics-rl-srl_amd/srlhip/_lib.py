@@ -46,6 +46,7 @@ EXPORTS = [
     "srlhip_encoder_destroy", "srlhip_encoder_last_error", "srlhip_encoder_pack_bytes", "srlhip_encoder_pack", "srlhip_encoder_pack_i8_bytes", "srlhip_encoder_pack_i8", "srlhip_encoder_pack_first_layer",
     "srlhip_jpeg_encode", "srlhip_render_jpeg", "srlhip_jpeg_header_bytes", "srlhip_jpeg_encode_host",
     "srlhip_jpeg_probe", "srlhip_jpeg_decode_host", "srlhip_jpeg_decode_workspace_bytes", "srlhip_jpeg_decode",
+    "srlhip_jpeg_probe_baseline", "srlhip_jpeg_decode_baseline_host", "srlhip_jpeg_decode_baseline_workspace_bytes", "srlhip_jpeg_decode_baseline",
     "srlhip_pca_supported", "srlhip_pca_create", "srlhip_pca_forward", "srlhip_pca_project_host", "srlhip_pca_destroy", "srlhip_pca_last_error",
     "srlhip_pca_gram_supported", "srlhip_pca_gram", "srlhip_pca_gram_host", "srlhip_pca_gram_last_error",
 ]
@@ -241,6 +242,11 @@ def load():
     lib.srlhip_jpeg_decode_workspace_bytes.restype = ctypes.c_size_t
     lib.srlhip_jpeg_decode_workspace_bytes.argtypes = [i32, i32, i32]
     lib.srlhip_jpeg_decode.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
+    lib.srlhip_jpeg_probe_baseline.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    lib.srlhip_jpeg_decode_baseline_host.argtypes = [vp, ctypes.c_size_t, vp, i32, ctypes.c_size_t, ctypes.POINTER(i32)]
+    lib.srlhip_jpeg_decode_baseline_workspace_bytes.restype = ctypes.c_size_t
+    lib.srlhip_jpeg_decode_baseline_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.srlhip_jpeg_decode_baseline.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -836,6 +842,58 @@ def jpeg_decode(blob_dev_ptr, offsets_dev_ptr, n_streams, h, w, c, images_dev_pt
     return load().srlhip_jpeg_decode(int(device_id), _ptr(blob_dev_ptr), _ptr(offsets_dev_ptr), int(n_streams), int(h), int(w), int(c),
                                      _ptr(images_dev_ptr), _ptr(status_dev_ptr), _ptr(workspace_dev_ptr),
                                      ctypes.c_void_p(stream) if stream else None)
+
+
+def jpeg_probe_baseline(data):
+    """srlhip_jpeg_probe_baseline: (h, w, sampling) with sampling 420 or 444 when `data` (bytes) is a baseline stream of the accepted
+    layout (what libjpeg writes by default, the library's own streams included), else None; no GPU needed"""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    h, w, mode = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    rc = load().srlhip_jpeg_probe_baseline(ctypes.c_void_p(buf.ctypes.data if len(buf) else None), len(buf), ctypes.byref(h), ctypes.byref(w),
+                                           ctypes.byref(mode))
+    return (int(h.value), int(w.value), int(mode.value)) if rc == 0 else None
+
+
+def jpeg_decode_baseline_host(data, out=None, return_status=False, shape=None):
+    """srlhip_jpeg_decode_baseline_host: one stream through the kernels' own source on the CPU -> uint8 [h][w][3]; `out` and the errors
+    as jpeg_decode_host.  With `shape` = (h, w) the stream is decoded as a device call for these sides would: a header that is refused
+    or carries other sides gives a frame of zeros and status 1 (2 for an empty stream), returned with return_status, raised without."""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    probed = jpeg_probe_baseline(data)
+    if probed is None or (shape is not None and tuple(shape) != probed[:2]):
+        if shape is None or not return_status:
+            raise ValueError("not a baseline stream of the accepted layout" + ("" if shape is None else " for {}x{} frames".format(*shape)))
+        if out is None:
+            out = np.zeros(tuple(shape) + (3,), np.uint8)
+        out[...] = 0
+        return out, (JPEG_EMPTY if len(buf) == 0 else JPEG_BAD_HEADER)
+    h, w = probed[:2]
+    if out is None:
+        out = np.zeros((h, w, 3), np.uint8)
+    assert out.dtype == np.uint8 and out.shape == (h, w, 3) and out.strides[2] == 1 and out.strides[0] == w * out.strides[1]
+    stride = int(out.strides[1])
+    status = ctypes.c_int32(-1)
+    rc = load().srlhip_jpeg_decode_baseline_host(ctypes.c_void_p(buf.ctypes.data), len(buf), ctypes.c_void_p(out.ctypes.data), stride,
+                                                 (h * w - 1) * stride + 3, ctypes.byref(status))
+    if rc:
+        raise SrlHipError("srlhip_jpeg_decode_baseline_host failed ({})".format(rc))
+    if return_status:
+        return out, int(status.value)
+    if status.value:
+        raise SrlHipError("srlhip_jpeg_decode_baseline_host: malformed entropy-coded data (status {})".format(status.value))
+    return out
+
+
+def jpeg_decode_baseline_workspace_bytes(n_streams, h, w):
+    return int(load().srlhip_jpeg_decode_baseline_workspace_bytes(int(n_streams), int(h), int(w)))
+
+
+def jpeg_decode_baseline(blob_dev_ptr, offsets_dev_ptr, n_streams, h, w, c, images_dev_ptr, status_dev_ptr, workspace_dev_ptr, device_id=0, stream=0):
+    """srlhip_jpeg_decode_baseline, raw: device pointers as jpeg_decode's, jpeg_decode_baseline_workspace_bytes of scratch; only enqueues
+    on `stream`.  Returns the library's status code."""
+    return load().srlhip_jpeg_decode_baseline(int(device_id), _ptr(blob_dev_ptr), _ptr(offsets_dev_ptr), int(n_streams), int(h), int(w), int(c),
+                                              _ptr(images_dev_ptr), _ptr(status_dev_ptr), _ptr(workspace_dev_ptr),
+                                              ctypes.c_void_p(stream) if stream else None)
 
 
 def encoder_supported(img_h, img_w, n_channels):

@@ -20,6 +20,7 @@ bit for bit, and everything else is the same numpy code: fit_pca(backend="hip") 
 
     python -m state_representation.pca_fit --data-folder <recorded dataset> --state-dim K [--max-frames 4096] [--device-id 0] --log-folder <out>
         [--decode-backend hip]    (datasets of `dataset_generator --device-jpeg`: the files are decoded on the GPU and never exist decoded on the host)
+        [--decode-backend hip-baseline]    (the same for datasets of the default recorder, Pillow's or OpenCV's files)
 """
 import argparse
 import glob
@@ -176,9 +177,12 @@ def load_dataset_frames(data_folder, max_frames=4096, backend="pillow", device_i
     """the record_*/frame*.jpg of a dataset `dataset_generator` wrote, subsampled evenly down to max_frames -> uint8 [N][H][W][3].
     backend "pillow": decoded on the host, a numpy array; "hip": the files' bytes are uploaded and decoded on the GPU
     (srlhip.jpeg_io.decode_files: only streams of this library's encoder, `dataset_generator --device-jpeg`; ValueError names the first
-    file that is not one), a device tensor; "auto": hip when a GPU is visible and every selected file is such a stream, else pillow."""
-    if backend not in ("pillow", "hip", "auto"):
-        raise ValueError("backend must be pillow, hip or auto")
+    file that is not one), a device tensor; "auto": hip when a GPU is visible and every selected file is such a stream, else pillow;
+    "hip-baseline": decoded on the GPU by srlhip_jpeg_decode_baseline, which also reads what the default recorder (Pillow) and the
+    reference's (OpenCV) write — baseline JPEG, 4:2:0 or 4:4:4, standard Huffman tables; ValueError names the first file that is not
+    one and says why."""
+    if backend not in ("pillow", "hip", "auto", "hip-baseline"):
+        raise ValueError("backend must be pillow, hip, auto or hip-baseline")
     paths = sorted(glob.glob(os.path.join(data_folder, "record_*", "frame*.jpg")))
     if not paths:
         raise ValueError("no record_*/frame*.jpg under {}".format(data_folder))
@@ -188,8 +192,10 @@ def load_dataset_frames(data_folder, max_frames=4096, backend="pillow", device_i
     if backend != "pillow":
         import torch
         from srlhip import jpeg_io
-        if backend == "hip" and not torch.cuda.is_available():
-            raise RuntimeError("load_dataset_frames(backend='hip') needs a GPU")
+        if backend in ("hip", "hip-baseline") and not torch.cuda.is_available():
+            raise RuntimeError("load_dataset_frames(backend='{}') needs a GPU".format(backend))
+        if backend == "hip-baseline":
+            return jpeg_io.decode_files(paths, torch.device("cuda", torch.cuda.current_device() if device_id is None else device_id), accept="baseline")
         if backend == "hip" or (torch.cuda.is_available() and jpeg_io.all_accepted(paths)):
             return jpeg_io.decode_files(paths, torch.device("cuda", torch.cuda.current_device() if device_id is None else device_id))
     from PIL import Image
@@ -203,8 +209,9 @@ def main(argv=None):
     parser.add_argument("--max-frames", type=int, default=4096)
     parser.add_argument("--device-id", type=int, default=0)
     parser.add_argument("--backend", default="auto", choices=("auto", "hip", "host"))
-    parser.add_argument("--decode-backend", default="pillow", choices=("pillow", "hip", "auto"),
-                        help="who decodes the recorded JPEG files: Pillow on the host, or the GPU (streams of --device-jpeg datasets only)")
+    parser.add_argument("--decode-backend", default="pillow", choices=("pillow", "hip", "auto", "hip-baseline"),
+                        help="who decodes the recorded JPEG files: Pillow on the host, or the GPU (hip: streams of --device-jpeg datasets only; "
+                             "hip-baseline: also the default recorder's files)")
     parser.add_argument("--log-folder", required=True, help="the model goes to <log-folder>/baselines/pca_ST_DIM<k>/pca.pkl")
     args = parser.parse_args(argv)
     frames = load_dataset_frames(args.data_folder, args.max_frames, backend=args.decode_backend, device_id=args.device_id)
