@@ -1017,6 +1017,46 @@ int srlhip_pca_gram_host(const uint8_t *frames, int32_t n, int64_t n_features,
                          int64_t *gram, int64_t *rowsum);                     /* host only */
 const char *srlhip_pca_gram_last_error(void);
 
+/* ---- scoring a state representation: exact k nearest neighbours and the KNN-MSE terms ----------------------
+ * What state_representation/evaluate.py measures a learned state space with (csrc/knn.hpp is the one text of the
+ * arithmetic for the kernels of csrc/knn.hip, the host twin and the host check program).
+ * INPUTS.  states [n][s] float64, or float32 with states_f32 = 1 (each value widened exactly to float64 on load).
+ * queries int32 [q], indices into 0 .. n - 1, duplicates allowed; NULL means q = n and queries[i] = i (the q argument is
+ * not read then).  ground truth optional, float64 [n][g].
+ * DISTANCE.  For query row i and candidate j: diff_s = x[i][s] - x[j][s] in float64, d = fma(diff_s, diff_s, d) for
+ * s = 0 .. S - 1 in ascending order from +0.0.  No Gram-trick expansion, no reassociation: d(i, j) and d(j, i) are the
+ * same bits.
+ * NEIGHBOURS.  The k neighbours of i are the k smallest elements of {(d(i, j), j) : j != i} under the total order
+ * "smaller d first, then smaller j", listed ascending.  j == i is excluded by index, not by distance: a duplicate
+ * state at another index is a legitimate neighbour at distance 0.  A candidate enters a list only through
+ * d < worst || (d == worst && j < worst_j), so a NaN distance never enters (nor +inf: the empty slot is (-1, +inf)),
+ * and a list that cannot be filled keeps (-1, +inf) in its tail.
+ * OUTPUTS.  idx int32 [q][k], dist float64 [q][k].  With a ground truth, err float64 [q]: i = queries[r], e from +0.0,
+ * n = 0 .. k - 1 outer and c = 0 .. g - 1 inner, t = gt[idx[r][n]][c] - gt[i][c], e = fma(t, t, e); err[r] = e / (double)k.
+ * Slots with index -1 are skipped, the divisor stays k.  gt and err are both given or both NULL.
+ * SHAPES.  2 <= n <= 2^20, 1 <= s <= 64, 1 <= k <= min(32, n - 1), 1 <= q <= 2^20, 1 <= g <= 32:
+ * srlhip_knn_supported tells beforehand (g = 0: no ground truth), anything else -> SRLHIP_ENOTSUP.  A null required
+ * pointer, a negative split, one of gt / err without the other, or — on the host twin — a query index outside
+ * 0 .. n - 1 -> SRLHIP_EINVAL.  A refused call touches no output.  The order is total and every operation is an IEEE
+ * float64 operation in a fixed sequence, so the result is unique: it does not depend on q, on a query's place in the
+ * list, on the launch shape or on split, and the device equals the host twin bit for bit.
+ * THE DEVICE CALL only enqueues on hip_stream (NULL = the default stream): one launch of partial lists over candidate
+ * slices (split = 0 chooses their number, split >= 1 asks for that many, slices that would be empty are not launched)
+ * and, with more than one slice, one launch that merges them.  It allocates nothing and presets nothing on the stream,
+ * so it may be captured into a graph.  The partial lists live in workspace_dev: srlhip_knn_workspace_bytes(n, s, k, q,
+ * split) bytes (0 = the shape is refused), 8-byte aligned, required also when one slice ends up being used.  All
+ * pointers are DEVICE pointers on device_id; states need only their element's alignment.  The device call does not read
+ * queries on the host: an index outside 0 .. n - 1 there neither reads nor writes out of bounds — its load is clamped
+ * and its rows are (-1, +inf) (err 0). */
+int srlhip_knn_supported(int32_t n, int32_t s, int32_t k, int32_t q, int32_t g);          /* host only; g = 0: no ground truth */
+size_t srlhip_knn_workspace_bytes(int32_t n, int32_t s, int32_t k, int32_t q, int32_t split);
+int srlhip_knn(int32_t device_id, const void *states_dev, int32_t states_f32, int32_t n, int32_t s,
+               const int32_t *queries_dev, int32_t q, int32_t k, const double *gt_dev, int32_t g, int32_t split,
+               int32_t *idx_dev, double *dist_dev, double *err_dev, void *workspace_dev, void *hip_stream);   /* enqueue-only */
+int srlhip_knn_host(const void *states, int32_t states_f32, int32_t n, int32_t s, const int32_t *queries, int32_t q,
+                    int32_t k, const double *gt, int32_t g, int32_t *idx, double *dist, double *err);          /* host only */
+const char *srlhip_knn_last_error(void);                                                  /* the calling thread's */
+
 
 #ifdef __cplusplus
 }

@@ -49,6 +49,7 @@ EXPORTS = [
     "srlhip_jpeg_probe_baseline", "srlhip_jpeg_decode_baseline_host", "srlhip_jpeg_decode_baseline_workspace_bytes", "srlhip_jpeg_decode_baseline",
     "srlhip_pca_supported", "srlhip_pca_create", "srlhip_pca_forward", "srlhip_pca_project_host", "srlhip_pca_destroy", "srlhip_pca_last_error",
     "srlhip_pca_gram_supported", "srlhip_pca_gram", "srlhip_pca_gram_host", "srlhip_pca_gram_last_error",
+    "srlhip_knn_supported", "srlhip_knn_workspace_bytes", "srlhip_knn", "srlhip_knn_host", "srlhip_knn_last_error",
 ]
 
 
@@ -225,6 +226,13 @@ def load():
     lib.srlhip_pca_gram_host.argtypes = [vp, i32, ctypes.c_int64, vp, vp]
     lib.srlhip_pca_gram_last_error.restype = ctypes.c_char_p
     lib.srlhip_pca_gram_last_error.argtypes = []
+    lib.srlhip_knn_supported.argtypes = [i32] * 5
+    lib.srlhip_knn_workspace_bytes.restype = ctypes.c_size_t
+    lib.srlhip_knn_workspace_bytes.argtypes = [i32] * 5
+    lib.srlhip_knn.argtypes = [i32, vp, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp]
+    lib.srlhip_knn_host.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, i32, vp, vp, vp]
+    lib.srlhip_knn_last_error.restype = ctypes.c_char_p
+    lib.srlhip_knn_last_error.argtypes = []
     lib.srlhip_encoder_pack_bytes.restype = ctypes.c_size_t
     lib.srlhip_encoder_pack_bytes.argtypes = []
     lib.srlhip_encoder_pack.argtypes = [vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
@@ -1094,3 +1102,60 @@ def pca_gram_host(frames):
     if rc:
         _gram_fail("srlhip_pca_gram_host", rc)
     return gram, rowsum
+
+
+KNN_MAX_N, KNN_MAX_S, KNN_MAX_K, KNN_MAX_G = 1 << 20, 64, 32, 32
+
+
+def knn_supported(n, s, k, q, g=0):
+    """host only: does srlhip_knn take this shape (2 <= n <= 2^20, 1 <= s <= 64, 1 <= k <= min(32, n - 1), 1 <= q <= 2^20, g = 0 for no
+    ground truth or 1..32)"""
+    return bool(load().srlhip_knn_supported(int(n), int(s), int(k), int(q), int(g)))
+
+
+def knn_workspace_bytes(n, s, k, q, split=0):
+    """bytes of device workspace srlhip_knn needs for this shape and split (0: the shape is refused)"""
+    return int(load().srlhip_knn_workspace_bytes(int(n), int(s), int(k), int(q), int(split)))
+
+
+def _knn_fail(what, rc):
+    raise SrlHipError("{} failed ({}): {}".format(what, rc, load().srlhip_knn_last_error().decode()))
+
+
+def knn(device_id, states_ptr, states_f32, n, s, queries_ptr, q, k, gt_ptr, g, idx_ptr, dist_ptr, err_ptr, workspace_ptr, split=0, stream=None):
+    """srlhip_knn: idx int32 [q][k] and dist float64 [q][k], the exact k nearest neighbours of the query rows among the device-resident
+    states [n][s] (float64, or float32 with states_f32), and with a ground truth [n][g] err float64 [q] (csrc/knn.hip; the contract is in
+    include/srlhip.h).  Raw device pointers (e.g. torch.Tensor.data_ptr()), None for queries (every row), ground truth and err;
+    workspace of knn_workspace_bytes; enqueue-only on `stream`; split 0 = automatic."""
+    rc = load().srlhip_knn(int(device_id), _ptr(states_ptr), int(bool(states_f32)), int(n), int(s), _ptr(queries_ptr), int(q), int(k),
+                           _ptr(gt_ptr), int(g), int(split), _ptr(idx_ptr), _ptr(dist_ptr), _ptr(err_ptr), _ptr(workspace_ptr),
+                           ctypes.c_void_p(stream) if stream else None)
+    if rc:
+        _knn_fail("srlhip_knn", rc)
+
+
+def knn_host(states, k, queries=None, ground_truth=None):
+    """srlhip_knn_host: the same planes on the CPU.  states float64 or float32 [n][s], queries int32 [q] or None (every row),
+    ground_truth float64 [n][g] or None -> (idx int32 [q][k], dist float64 [q][k][, err float64 [q]]); raises SrlHipError on a refusal."""
+    states = np.asarray(states)
+    states = np.ascontiguousarray(states, dtype=np.float32 if states.dtype == np.float32 else np.float64)
+    if states.ndim != 2:
+        raise ValueError("knn_host takes states [n][s]")
+    n, s = states.shape
+    if queries is not None:
+        queries = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)
+    q = n if queries is None else len(queries)
+    g = 0
+    if ground_truth is not None:
+        ground_truth = np.ascontiguousarray(ground_truth, dtype=np.float64)
+        if ground_truth.ndim != 2 or ground_truth.shape[0] != n:
+            raise ValueError("knn_host takes ground_truth [n][g]")
+        g = ground_truth.shape[1]
+    k = int(k)
+    idx, dist = np.zeros((q, max(k, 0)), np.int32), np.zeros((q, max(k, 0)), np.float64)
+    err = np.zeros(q, np.float64) if ground_truth is not None else None
+    rc = load().srlhip_knn_host(_ptr(states), int(states.dtype == np.float32), n, s, _ptr(queries), q, k, _ptr(ground_truth), g,
+                                _ptr(idx), _ptr(dist), _ptr(err))
+    if rc:
+        _knn_fail("srlhip_knn_host", rc)
+    return (idx, dist) if err is None else (idx, dist, err)

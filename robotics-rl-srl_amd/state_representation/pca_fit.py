@@ -21,6 +21,8 @@ bit for bit, and everything else is the same numpy code: fit_pca(backend="hip") 
     python -m state_representation.pca_fit --data-folder <recorded dataset> --state-dim K [--max-frames 4096] [--device-id 0] --log-folder <out>
         [--decode-backend hip]    (datasets of `dataset_generator --device-jpeg`: the files are decoded on the GPU and never exist decoded on the host)
         [--decode-backend hip-baseline]    (the same for datasets of the default recorder, Pillow's or OpenCV's files)
+        [--evaluate]    (score the saved model on the frames it was fitted on: state_representation/evaluate.py, KNN-MSE and ground-truth
+                         correlation into <log-folder>/baselines/pca_ST_DIM<k>/knn_mse.json)
 """
 import argparse
 import glob
@@ -213,13 +215,26 @@ def main(argv=None):
                         help="who decodes the recorded JPEG files: Pillow on the host, or the GPU (hip: streams of --device-jpeg datasets only; "
                              "hip-baseline: also the default recorder's files)")
     parser.add_argument("--log-folder", required=True, help="the model goes to <log-folder>/baselines/pca_ST_DIM<k>/pca.pkl")
+    parser.add_argument("--evaluate", action="store_true", default=False,
+                        help="score the saved model on the frames it was fitted on (state_representation.evaluate: knn_mse.json next to the model)")
     args = parser.parse_args(argv)
-    frames = load_dataset_frames(args.data_folder, args.max_frames, backend=args.decode_backend, device_id=args.device_id)
+    indices = None
+    if args.evaluate:                    # the frames in ground_truth.npz's order, so that each keeps its ground-truth row
+        from state_representation import evaluate
+        paths, indices = evaluate.dataset_items(args.data_folder, min(int(args.max_frames), MAX_FRAMES))
+        frames = evaluate.decode_items(paths, args.decode_backend, args.device_id)
+    else:
+        frames = load_dataset_frames(args.data_folder, args.max_frames, backend=args.decode_backend, device_id=args.device_id)
     model = fit_pca(frames, args.state_dim, backend=args.backend, device_id=args.device_id)
     path = model.save(args.log_folder)
     print("fitted {} components on {} frames of {} ({}): explained variance ratio {:.4f} -> {}".format(
         model.n_components_, len(frames), "x".join(str(d) for d in frames.shape[1:]), model.backend,
         float(model.explained_variance_ratio_.sum()), path))
+    if args.evaluate:
+        out = evaluate.evaluate_model(args.data_folder, path, backend=args.backend, device_id=args.device_id, log_folder=os.path.dirname(path),
+                                      frames=frames, indices=indices)
+        print("knn_mse {:.6g} (k = {}, {} queries; ground truth as states {:.6g}), gtc_mean {:.4f}".format(
+            out["knn_mse"], out["k"], out["n_queries"], out["knn_mse_ground_truth"], out["gtc_mean"]))
     return path
 
 
