@@ -1057,6 +1057,55 @@ int srlhip_knn_host(const void *states, int32_t states_f32, int32_t n, int32_t s
                     int32_t k, const double *gt, int32_t g, int32_t *idx, double *dist, double *err);          /* host only */
 const char *srlhip_knn_last_error(void);                                                  /* the calling thread's */
 
+/* ---- the trainable linear state encoder: forward, and gradient + Adam in one launch ----------------------------------
+ * state = fc(flatten(preprocess(frame))): srl_zoo's `--model-type linear` [srl_zoo is an empty submodule of the
+ * reference checkout: recalled, UNVERIFIED].  What state_representation/linear_srl.py trains with (csrc/linear_srl.hpp
+ * is the one text of the arithmetic for the kernels of csrc/linear_srl.hip, the host twins and the host check program).
+ * SHAPES: frames uint8 [n][F], flattened NHWC as srlhip_render leaves them; feature f belongs to channel f mod C;
+ * V [F][S], m [F][S], v [F][S], c [S], G [n][S], states [n][S], all float64.  F >= 1, 1 <= S <= 64, 1 <= C <= 8
+ * (srlhip_linear_srl_supported tells beforehand, anything else -> SRLHIP_ENOTSUP), 1 <= n <= 1024 (n < 1 -> SRLHIP_EINVAL,
+ * n > 1024 -> SRLHIP_ENOTSUP).  scale [C] and offset [C] are HOST tables, read during the call: the caller passes
+ * 1 / (255 std) and mean / std.  A null pointer, a table entry that is not finite, an lr that is not finite, a beta
+ * outside [0, 1), a negative or non-finite eps, a bias correction outside (0, 1], a workspace that is null or not
+ * 16-byte aligned -> SRLHIP_EINVAL.  A refused call touches nothing; its message is the calling thread's
+ * srlhip_linear_srl_last_error.
+ * THE ARITHMETIC, every operation an IEEE float64 operation in a fixed sequence:
+ *   xn       = fma(scale[ch], (double) x, -offset[ch])                                   (fused)
+ *   forward    the order of srlhip_pca_forward with xn in the byte's place: chunks of 512 features, within a chunk
+ *              ascending acc = fma(xn, V[f][s], acc) from +0.0 (fused); the chunk sums added in ascending chunk
+ *              order starting with chunk 0's, then + c[s] (separate additions).  A function of F alone.
+ *   gradient   g[f][s] from +0.0, for i = 0 .. n - 1 ascending g = fma(xn[i][f], G[i][s], g) (fused).  No atomics and
+ *              no split over i: a function of n alone, not of the launch shape.
+ *   Adam       every operation SEPARATE, division and square root correctly rounded; the caller passes
+ *              bc1 = 1 - beta1^t and bc2 = 1 - beta2^t:
+ *                m = (beta1 * m) + ((1 - beta1) * g)
+ *                v = (beta2 * v) + (((1 - beta2) * g) * g)
+ *                V = V - ((lr / bc1) * (m / ((sqrt(v) / sqrt(bc2)) + eps)))
+ * so the device equals the host twin bit for bit, in the states, in grad_out and in V, m, v after any number of steps.
+ * THE DEVICE CALLS only enqueue on hip_stream (NULL = the default stream), allocate nothing and preset nothing: they
+ * may be captured into a graph.  srlhip_linear_srl_forward is two launches (chunk sums into workspace_dev:
+ * srlhip_linear_srl_workspace_bytes(F, S, n) bytes, 0 = the shape is refused; then the join).
+ * srlhip_linear_srl_step is ONE launch that forms g and updates V, m, v in place; with a non-null grad_out_dev g is
+ * also stored [F][S].  c and the loss heads are the caller's.  All pointers but the tables are DEVICE pointers on
+ * device_id; the *_host twins take host pointers and need no GPU. */
+int srlhip_linear_srl_supported(int64_t n_features, int32_t state_dim, int32_t n_channels);    /* host only */
+size_t srlhip_linear_srl_workspace_bytes(int64_t n_features, int32_t state_dim, int32_t n);
+int srlhip_linear_srl_forward(int32_t device_id, const uint8_t *frames_dev, int32_t n, int64_t n_features, int32_t state_dim,
+                              int32_t n_channels, const double *scale, const double *offset, const double *v_dev,
+                              const double *c_dev, double *states_dev, void *workspace_dev, void *hip_stream);   /* enqueue-only */
+int srlhip_linear_srl_step(int32_t device_id, const uint8_t *frames_dev, int32_t n, int64_t n_features, int32_t state_dim,
+                           int32_t n_channels, const double *scale, const double *offset, const double *g_dev, double *v_dev,
+                           double *m_dev, double *v2_dev, double lr, double beta1, double beta2, double eps, double bc1,
+                           double bc2, double *grad_out_dev, void *hip_stream);                                  /* enqueue-only */
+int srlhip_linear_srl_forward_host(const uint8_t *frames, int32_t n, int64_t n_features, int32_t state_dim, int32_t n_channels,
+                                   const double *scale, const double *offset, const double *v, const double *c,
+                                   double *states);                                                            /* host only */
+int srlhip_linear_srl_step_host(const uint8_t *frames, int32_t n, int64_t n_features, int32_t state_dim, int32_t n_channels,
+                                const double *scale, const double *offset, const double *g, double *v, double *m,
+                                double *v2, double lr, double beta1, double beta2, double eps, double bc1, double bc2,
+                                double *grad_out);                                                             /* host only */
+const char *srlhip_linear_srl_last_error(void);                                               /* the calling thread's */
+
 
 #ifdef __cplusplus
 }

@@ -50,6 +50,8 @@ EXPORTS = [
     "srlhip_pca_supported", "srlhip_pca_create", "srlhip_pca_forward", "srlhip_pca_project_host", "srlhip_pca_destroy", "srlhip_pca_last_error",
     "srlhip_pca_gram_supported", "srlhip_pca_gram", "srlhip_pca_gram_host", "srlhip_pca_gram_last_error",
     "srlhip_knn_supported", "srlhip_knn_workspace_bytes", "srlhip_knn", "srlhip_knn_host", "srlhip_knn_last_error",
+    "srlhip_linear_srl_supported", "srlhip_linear_srl_workspace_bytes", "srlhip_linear_srl_forward", "srlhip_linear_srl_step",
+    "srlhip_linear_srl_forward_host", "srlhip_linear_srl_step_host", "srlhip_linear_srl_last_error",
 ]
 
 
@@ -233,6 +235,16 @@ def load():
     lib.srlhip_knn_host.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, i32, vp, vp, vp]
     lib.srlhip_knn_last_error.restype = ctypes.c_char_p
     lib.srlhip_knn_last_error.argtypes = []
+    f64 = ctypes.c_double
+    lib.srlhip_linear_srl_supported.argtypes = [ctypes.c_int64, i32, i32]
+    lib.srlhip_linear_srl_workspace_bytes.restype = ctypes.c_size_t
+    lib.srlhip_linear_srl_workspace_bytes.argtypes = [ctypes.c_int64, i32, i32]
+    lib.srlhip_linear_srl_forward.argtypes = [i32, vp, i32, ctypes.c_int64, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.srlhip_linear_srl_step.argtypes = [i32, vp, i32, ctypes.c_int64, i32, i32, vp, vp, vp, vp, vp, vp] + [f64] * 6 + [vp, vp]
+    lib.srlhip_linear_srl_forward_host.argtypes = [vp, i32, ctypes.c_int64, i32, i32, vp, vp, vp, vp, vp]
+    lib.srlhip_linear_srl_step_host.argtypes = [vp, i32, ctypes.c_int64, i32, i32, vp, vp, vp, vp, vp, vp] + [f64] * 6 + [vp]
+    lib.srlhip_linear_srl_last_error.restype = ctypes.c_char_p
+    lib.srlhip_linear_srl_last_error.argtypes = []
     lib.srlhip_encoder_pack_bytes.restype = ctypes.c_size_t
     lib.srlhip_encoder_pack_bytes.argtypes = []
     lib.srlhip_encoder_pack.argtypes = [vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
@@ -1159,3 +1171,104 @@ def knn_host(states, k, queries=None, ground_truth=None):
     if rc:
         _knn_fail("srlhip_knn_host", rc)
     return (idx, dist) if err is None else (idx, dist, err)
+
+
+# ---- the trainable linear state encoder (csrc/linear_srl.hip; the contract is in include/srlhip.h) ---------------------------------------
+LINEAR_SRL_MAX_FRAMES = 1024
+
+
+def linear_srl_supported(n_features, state_dim, n_channels=3):
+    """host only: does srlhip_linear_srl_* take this shape (n_features >= 1, 1 <= state_dim <= 64, 1 <= n_channels <= 8)"""
+    return bool(load().srlhip_linear_srl_supported(int(n_features), int(state_dim), int(n_channels)))
+
+
+def linear_srl_workspace_bytes(n_features, state_dim, n):
+    """bytes of device workspace srlhip_linear_srl_forward needs (0: the shape is refused)"""
+    return int(load().srlhip_linear_srl_workspace_bytes(int(n_features), int(state_dim), int(n)))
+
+
+def linear_srl_tables(n_channels, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+    """-> (scale, offset) float64 [n_channels]: 1 / (255 std) and mean / std of the channel's ImageNet constant, repeated per 3-channel
+    group (state_representation.models.preprocess)"""
+    mean = np.array([mean[k % len(mean)] for k in range(n_channels)], np.float64)
+    std = np.array([std[k % len(std)] for k in range(n_channels)], np.float64)
+    return 1.0 / (255.0 * std), mean / std
+
+
+def _linear_srl_fail(what, rc):
+    raise SrlHipError("{} failed ({}): {}".format(what, rc, load().srlhip_linear_srl_last_error().decode()))
+
+
+def _tables(scale, offset):
+    scale, offset = np.ascontiguousarray(scale, dtype=np.float64).reshape(-1), np.ascontiguousarray(offset, dtype=np.float64).reshape(-1)
+    if len(scale) != len(offset):
+        raise ValueError("scale and offset must have one entry per channel")
+    return scale, offset
+
+
+def _adam_args(adam):
+    return [ctypes.c_double(float(adam[k])) for k in ("lr", "beta1", "beta2", "eps", "bc1", "bc2")]
+
+
+def adam_at(t, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):
+    """the hyper-parameters of Adam's step t = 1, 2, ... as srlhip_linear_srl_step takes them: bc1 = 1 - beta1^t, bc2 = 1 - beta2^t
+    (Python float powers, the way torch.optim.Adam computes them)"""
+    return {"lr": lr, "beta1": beta1, "beta2": beta2, "eps": eps, "bc1": 1 - beta1 ** t, "bc2": 1 - beta2 ** t}
+
+
+def linear_srl_forward(device_id, frames_ptr, n, n_features, state_dim, scale, offset, v_ptr, c_ptr, states_ptr, workspace_ptr, stream=None):
+    """srlhip_linear_srl_forward: states float64 [n][S] of the device-resident uint8 frames [n][F].  Raw device pointers; scale / offset
+    are host arrays [C]; a workspace of linear_srl_workspace_bytes, 16-byte aligned; enqueue-only on `stream`."""
+    scale, offset = _tables(scale, offset)
+    rc = load().srlhip_linear_srl_forward(int(device_id), _ptr(frames_ptr), int(n), int(n_features), int(state_dim), len(scale), _ptr(scale),
+                                          _ptr(offset), _ptr(v_ptr), _ptr(c_ptr), _ptr(states_ptr), _ptr(workspace_ptr),
+                                          ctypes.c_void_p(int(stream)) if stream else None)
+    if rc:
+        _linear_srl_fail("srlhip_linear_srl_forward", rc)
+
+
+def linear_srl_step(device_id, frames_ptr, n, n_features, state_dim, scale, offset, g_ptr, v_ptr, m_ptr, v2_ptr, adam, grad_out_ptr=None, stream=None):
+    """srlhip_linear_srl_step: ONE launch that forms g = xn^T G and applies Adam to V, m, v [F][S] in place (adam: the dict of adam_at);
+    with grad_out_ptr g is also stored.  Raw device pointers; enqueue-only on `stream`."""
+    scale, offset = _tables(scale, offset)
+    rc = load().srlhip_linear_srl_step(int(device_id), _ptr(frames_ptr), int(n), int(n_features), int(state_dim), len(scale), _ptr(scale),
+                                       _ptr(offset), _ptr(g_ptr), _ptr(v_ptr), _ptr(m_ptr), _ptr(v2_ptr), *(_adam_args(adam) + [
+                                           _ptr(grad_out_ptr), ctypes.c_void_p(int(stream)) if stream else None]))
+    if rc:
+        _linear_srl_fail("srlhip_linear_srl_step", rc)
+
+
+def linear_srl_forward_host(frames, scale, offset, V, c):
+    """srlhip_linear_srl_forward_host: the kernel's own arithmetic (csrc/linear_srl.hpp) on the CPU.  frames uint8 [n][...] (flattened to
+    [n][F]), V float64 [F][S], c [S] -> float64 [n][S]"""
+    scale, offset = _tables(scale, offset)
+    V, c = np.ascontiguousarray(V, dtype=np.float64), np.ascontiguousarray(c, dtype=np.float64)
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    n = len(frames)
+    frames = frames.reshape(n, -1)
+    if V.ndim != 2 or frames.shape[1] != V.shape[0] or c.shape != (V.shape[1],):
+        raise ValueError("linear_srl_forward_host takes frames [n][F], V [F][S], c [S]")
+    out = np.zeros((n, V.shape[1]), np.float64)
+    rc = load().srlhip_linear_srl_forward_host(_ptr(frames), n, V.shape[0], V.shape[1], len(scale), _ptr(scale), _ptr(offset), _ptr(V), _ptr(c), _ptr(out))
+    if rc:
+        _linear_srl_fail("srlhip_linear_srl_forward_host", rc)
+    return out
+
+
+def linear_srl_step_host(frames, scale, offset, G, V, m, v, adam, grad_out=None):
+    """srlhip_linear_srl_step_host: gradient + Adam on the CPU, IN PLACE on the float64 C-contiguous arrays V, m, v [F][S]; grad_out
+    (float64 [F][S], optional) receives g"""
+    scale, offset = _tables(scale, offset)
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    n = len(frames)
+    frames = frames.reshape(n, -1)
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    for a in (V, m, v) + (() if grad_out is None else (grad_out,)):
+        if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.shape == V.shape):
+            raise ValueError("linear_srl_step_host updates float64 C-contiguous arrays [F][S] in place")
+    if V.ndim != 2 or frames.shape[1] != V.shape[0] or G.shape != (n, V.shape[1]):
+        raise ValueError("linear_srl_step_host takes frames [n][F], G [n][S], V [F][S]")
+    rc = load().srlhip_linear_srl_step_host(_ptr(frames), n, V.shape[0], V.shape[1], len(scale), _ptr(scale), _ptr(offset), _ptr(G), _ptr(V),
+                                            _ptr(m), _ptr(v), *(_adam_args(adam) + [_ptr(grad_out)]))
+    if rc:
+        _linear_srl_fail("srlhip_linear_srl_step_host", rc)

@@ -225,10 +225,14 @@ class SRLPCA(object):
         w = comp.T.copy()
         if getattr(pca, "whiten", False):
             w = w / np.sqrt(np.asarray(pca.explained_variance_, dtype=np.float64))[None, :]
+        self._set_projection(w, -(mean @ w), "the pickled PCA")                  # folded: X @ w - mean @ w
+
+    def _set_projection(self, w, b, what):
+        """states = frames (raw bytes) @ w [n_features][state_dim] + b [state_dim]: the tensors of the torch formulation and, on a GPU,
+        the projector's handle"""
         self._w = th.from_numpy(w).to(self.device)                               # [n_features][state_dim]
-        b = -(mean @ w)                                                          # folded: X @ w - mean @ w
         self._b = th.from_numpy(b).to(self.device)
-        assert self._w.shape[1] == self.state_dim, "exp_config.json state-dim does not match the pickled PCA"
+        assert self._w.shape[1] == self.state_dim, "exp_config.json state-dim does not match " + what
         if self.hip is not None:
             self.hip.close()
         self.hip, self.backend = None, "gemm"
@@ -277,6 +281,80 @@ class SRLPCA(object):
         return self.getStates(np.asarray(observation)[None])[0].to("cpu").numpy()
 
 
+def linear_tables(n_channels):
+    """(scale, offset) float64 [n_channels] with preprocess(x) = scale x - offset per channel: 1 / (255 std) and mean / std of the
+    ImageNet constants, repeated per 3-channel group — the tables srlhip_linear_srl_* take"""
+    mean = np.array([IMAGENET_MEAN[k % 3] for k in range(n_channels)], dtype=np.float64)
+    std = np.array([IMAGENET_STD[k % 3] for k in range(n_channels)], dtype=np.float64)
+    return 1.0 / (255.0 * std), mean / std
+
+
+def linear_to_checkpoint(V, img_shape, n_channels):
+    """V [F][S], F in the frame's own NHWC flatten order -> fc.weight [S][F'], F' in the reference's order: preprocess() hands the
+    network [N][C][W][H] (width and height swapped, models.py:185-188), so f' = (ch W + w) H + h"""
+    H, W = img_shape
+    V = np.asarray(V, dtype=np.float64)
+    return np.ascontiguousarray(V.reshape(H, W, n_channels, V.shape[1]).transpose(3, 2, 1, 0).reshape(V.shape[1], -1))
+
+
+def linear_from_checkpoint(weight, img_shape, n_channels):
+    """fc.weight [S][F'] -> V [F][S]: linear_to_checkpoint's inverse"""
+    H, W = img_shape
+    weight = np.asarray(weight, dtype=np.float64)
+    return np.ascontiguousarray(weight.reshape(weight.shape[0], n_channels, W, H).transpose(3, 2, 1, 0).reshape(-1, weight.shape[0]))
+
+
+class SRLLinear(SRLPCA):
+    """srl_zoo's linear encoder, `--model-type linear`: state = fc(flatten(preprocess(frame))) [srl_zoo is an empty submodule of the
+    reference checkout: recalled, UNVERIFIED] — the model state_representation/linear_srl.py trains.  Inference folds the preprocessing
+    into the weights: with V [F][S] in the frame's NHWC order, c [S] and preprocess(x) = scale x - offset per channel,
+    states = x @ (scale V) + (c - offset^T V) on the RAW bytes, which is the PCA baseline's projection: the same kernel
+    (srlhip_pca_forward through PcaProjector) on a GPU, the same addmm elsewhere, float64 states."""
+
+    def __init__(self, state_dim, cuda=False, device=None, backend="auto", img_shape=(224, 224), n_channels=3):
+        super(SRLLinear, self).__init__(state_dim, cuda, device=device, backend=backend)
+        self.img_shape, self.n_channels = tuple(img_shape), int(n_channels)
+        self.V, self.c = None, None
+
+    def replicate(self, device):
+        twin = SRLLinear(self.state_dim, device=device, backend=self._backend_arg, img_shape=self.img_shape, n_channels=self.n_channels)
+        twin.set_weights(self.V, self.c)
+        for name in ("losses", "n_actions", "split_dimensions", "inverse_model_type"):
+            if hasattr(self, name):
+                setattr(twin, name, getattr(self, name))
+        return twin
+
+    def set_weights(self, V, c):
+        """V float64 [F][S] (NHWC order), c [S]"""
+        self.V, self.c = np.ascontiguousarray(V, dtype=np.float64), np.ascontiguousarray(c, dtype=np.float64)
+        F = self.img_shape[0] * self.img_shape[1] * self.n_channels
+        if self.V.shape != (F, self.state_dim) or self.c.shape != (self.state_dim,):
+            raise ValueError("SRLLinear: V {} and c {} do not fit {} x {} x {} frames and {} state dimensions".format(
+                self.V.shape, self.c.shape, self.img_shape[0], self.img_shape[1], self.n_channels, self.state_dim))
+        scale, offset = linear_tables(self.n_channels)
+        ch = np.arange(F) % self.n_channels
+        self.model = {"fc.weight": linear_to_checkpoint(self.V, self.img_shape, self.n_channels), "fc.bias": self.c}
+        self._set_projection(scale[ch][:, None] * self.V, self.c - (offset[ch][:, None] * self.V).sum(axis=0), "the linear checkpoint")
+
+    def set_model(self, state_dict):
+        """a bare {fc.weight [S][F'], fc.bias [S]} state dict, F' in the reference's C, W, H order"""
+        keys = sorted(state_dict)
+        if keys != ["fc.bias", "fc.weight"]:
+            raise KeyError("a linear srl encoder has fc.weight and fc.bias (got {})".format(keys[:6]))
+        weight, bias = (np.asarray(state_dict[k].detach().cpu().numpy() if isinstance(state_dict[k], th.Tensor) else state_dict[k],
+                                   dtype=np.float64) for k in ("fc.weight", "fc.bias"))
+        F = self.img_shape[0] * self.img_shape[1] * self.n_channels
+        if weight.ndim != 2 or weight.shape[1] != F:
+            raise ValueError("SRLLinear: fc.weight {} does not fit {} x {} x {} frames".format(weight.shape, self.img_shape[0], self.img_shape[1], self.n_channels))
+        self.set_weights(linear_from_checkpoint(weight, self.img_shape, self.n_channels), bias)
+
+    def load(self, path):
+        state_dict = th.load(path, map_location="cpu")
+        if isinstance(state_dict, dict) and "state_dict" in state_dict:
+            state_dict = state_dict["state_dict"]
+        self.set_model(_encoder_state_dict(state_dict, getattr(self, "losses", None), getattr(self, "split_dimensions", None)))
+
+
 _SRL_HEADS = ("forward_net.", "inverse_net.", "reward_net.")
 
 
@@ -310,7 +388,8 @@ def loadSRLModel(path=None, cuda=False, state_dim=None, env_object=None, img_sha
     `multi-view` (-> 6 input channels: srl_zoo sets preprocessing.N_CHANNELS = 6), `inverse-model-type`, `split-dimensions` (a dict whose
     values sum to 0 means "combine the losses": None) — and the checkpoint is loaded: a `baselines/.../pca` path is a pickled PCA
     (SRLPCA), anything else a torch state_dict — a bare CustomCNN's, or srl_zoo's SRLModules layout (`model.*` + loss heads, which are
-    dropped: _encoder_state_dict).  Only the `custom_cnn` encoder is restated (srl_zoo is an empty
+    dropped: _encoder_state_dict).  Only the `custom_cnn` encoder and the `linear` one (SRLLinear, which
+    state_representation/linear_srl.py trains) are restated (srl_zoo is an empty
     submodule in the reference checkout): other model types raise NotImplementedError instead of silently building a different
     network.  img_shape / n_channels: the frame shape the batched encoder is built for (the reference fixes it through srl_zoo
     globals); device: the GPU a multi-GPU caller wants this replica on (default cuda:0 when cuda)."""
@@ -349,9 +428,15 @@ def loadSRLModel(path=None, cuda=False, state_dim=None, env_object=None, img_sha
     if model is None:
         if use_multi_view:
             n_channels = 6                                   # preprocessing.preprocess.N_CHANNELS = 6
+        if model_type == "linear":
+            assert path is not None, "a linear srl model is loaded from a checkpoint (state_representation.linear_srl trains one)"
+            model = SRLLinear(state_dim, cuda, device=device, img_shape=img_shape, n_channels=n_channels)
+            model.losses, model.n_actions, model.split_dimensions, model.inverse_model_type = losses, n_actions, split_dimensions, inverse_model_type
+            model.load(path)
+            return model
         if model_type != "custom_cnn":
-            raise NotImplementedError("srl model type {!r}: only srl_zoo's custom_cnn encoder (and the pca baseline) are restated here "
-                                      "(srl_zoo is an empty submodule of the reference checkout)".format(model_type))
+            raise NotImplementedError("srl model type {!r}: only srl_zoo's custom_cnn and linear encoders (and the pca baseline) are restated "
+                                      "here (srl_zoo is an empty submodule of the reference checkout)".format(model_type))
         state_dict = th.load(path, map_location="cpu") if path is not None else None
         if isinstance(state_dict, dict) and "state_dict" in state_dict:
             state_dict = state_dict["state_dict"]
